@@ -10,7 +10,12 @@ ONE flat-bucket RCCL all-reduce of the gradients and an Adam step.  Graphs are p
 A "graph-edge" = one edge node processed by one forward call.
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full               # + stage roofline, CPU baseline, batch-1 blocks
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps and prints the line; the line's other blocks run only under --full (in a
+plain run their keys are null or absent).
 """
 import argparse
 import json
@@ -57,10 +62,11 @@ def make_adam(model):
         return torch.optim.Adam(model.parameters(), **kw)
 
 
-def step(model, plans, xs, targets, opt, bucket, world):
+def step(model, plans, xs, targets, opt, bucket, world, outs=None):
     """fwd over every call of the window batch, one backward, (all-reduce), Adam.  Loss: BCE with logits over ALL logits of
     every call against fixed {0,1} targets, summed -- trackmpnn_amd.loss.bce_with_logits_sum, one launch per
-    direction (equal to torch.nn.functional.binary_cross_entropy_with_logits(reduction='sum'), tests/test_loss.py)."""
+    direction (equal to torch.nn.functional.binary_cross_entropy_with_logits(reduction='sum'), tests/test_loss.py).
+    `outs` (a dict, or None): receives what the step computed -- every call's (scores, logits), the last h and the loss."""
     from trackmpnn_amd.functional import weight_cache
     from trackmpnn_amd.loss import bce_with_logits_sum
     h = None
@@ -70,6 +76,8 @@ def step(model, plans, xs, targets, opt, bucket, world):
             nxt = plans[c + 1].n_new if c + 1 < len(plans) else 0
             scores, logits, h, _ = model.forward_graph(x, h, plan, reserve_rows=nxt)
             loss = loss + bce_with_logits_sum(logits, t)
+            if outs is not None:
+                outs.setdefault('calls', []).append((scores, logits))
     opt.zero_grad(set_to_none=False)
     loss.backward()
     if world > 1:
@@ -77,6 +85,8 @@ def step(model, plans, xs, targets, opt, bucket, world):
         from trackmpnn_amd.dist import allreduce_grads
         allreduce_grads(model, bucket, world)
     opt.step()
+    if outs is not None:
+        outs.update(h=h, loss=loss)
     return loss
 
 
@@ -658,9 +668,9 @@ WORKLOADS = {
 }
 
 
-def static_step(model, plan0, planr, x, targets, iters, opt, bucket, world):
+def static_step(model, plan0, planr, x, targets, iters, opt, bucket, world, outs=None):
     """The static window mode of SURVEY 8(d): first call with every row new, then iters - 1 empty-x calls on the same graph,
-    one backward of the BCE loss over every call's logits, (all-reduce), Adam."""
+    one backward of the BCE loss over every call's logits, (all-reduce), Adam.  `outs`: as in step()."""
     from trackmpnn_amd.loss import bce_with_logits_sum
     from trackmpnn_amd.functional import weight_cache
     h = None
@@ -669,12 +679,16 @@ def static_step(model, plan0, planr, x, targets, iters, opt, bucket, world):
         for it in range(iters):
             scores, logits, h, _ = model.forward_graph(x if it == 0 else x[:0], h, plan0 if it == 0 else planr)
             loss = loss + bce_with_logits_sum(logits, targets)
+            if outs is not None:
+                outs.setdefault('calls', []).append((scores, logits))
     opt.zero_grad(set_to_none=False)
     loss.backward()
     if world > 1:
         from trackmpnn_amd.dist import allreduce_grads
         allreduce_grads(model, bucket, world)
     opt.step()
+    if outs is not None:
+        outs.update(h=h, loss=loss)
     return loss
 
 
@@ -698,8 +712,8 @@ def make_workload(name, rank, dev, windows=None, frames=None, dets=None):
         targets = [(torch.rand(p.graph.N, 1, generator=gen) < 0.3).float().to(dev) for p in plans]
         cfg = dict(workload=f"{w['label']}; {B} windows/GPU batched block-diagonally (64 distinct seeds tiled)",
                    windows_per_gpu=B, edge_iterations_per_gpu_step=edge_iters, rows_final=plans[-1].graph.N)
-        return dict(step=lambda: step(model, plans, xs, targets, opt, bucket, world), edge_iters=edge_iters, model=model,
-                    bucket=bucket, plans=plans, H=H, F=F, config=cfg, frames=fr, shape=w)
+        return dict(step=lambda outs=None: step(model, plans, xs, targets, opt, bucket, world, outs), edge_iters=edge_iters,
+                    model=model, bucket=bucket, plans=plans, H=H, F=F, config=cfg, frames=fr, shape=w)
     from trackmpnn_amd.graph import dense_static_graph, plan_single
     fr, D = int(frames or w['frames']), int(dets or w['dets'])
     g = dense_static_graph(fr, D, 'cpu').to(dev)
@@ -711,13 +725,13 @@ def make_workload(name, rank, dev, windows=None, frames=None, dets=None):
     iters = w['iters']
     cfg = dict(workload=f"{w['label']} ({fr} x {D}: Dn={g.Dn}, E={g.E})", windows_per_gpu=1,
                edge_iterations_per_gpu_step=g.E * iters, rows_final=g.N)
-    return dict(step=lambda: static_step(model, plan0, planr, x, targets, iters, opt, bucket, world), edge_iters=g.E * iters,
-                model=model, bucket=bucket, plans=[plan0], H=H, F=F, config=cfg, frames=fr, shape=w)
+    return dict(step=lambda outs=None: static_step(model, plan0, planr, x, targets, iters, opt, bucket, world, outs),
+                edge_iters=g.E * iters, model=model, bucket=bucket, plans=[plan0], H=H, F=F, config=cfg, frames=fr, shape=w)
 
 
-def timed_steps(fn, steps, warmup, world, dev, setup=0):
+def timed_steps(fn, steps, warmup, world, dev, setup=0, outs=None):
     """`setup` + `warmup` untimed steps, then EXACTLY `steps` steps bracketed by barrier + device sync on both sides;
-    returns the MAX over ranks of the elapsed seconds."""
+    returns the MAX over ranks of the elapsed seconds.  `outs` (a dict, or None) receives what the last timed step computed."""
     import torch.distributed as dist
     for _ in range(setup):
         fn()
@@ -729,8 +743,11 @@ def timed_steps(fn, steps, warmup, world, dev, setup=0):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        fn()
+    for i in range(steps):
+        if i == steps - 1 and outs is not None:
+            fn(outs)
+        else:
+            fn()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -741,6 +758,41 @@ def timed_steps(fn, steps, warmup, world, dev, setup=0):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     return dt
+
+
+DUMP_ROWS = 1 << 16             # --dump-outputs: rows kept of a per-row output (a fixed, seeded sample where it has more)
+DUMP_HIDDEN_BYTES = 1 << 24     # ... and at most this much of the hidden state
+
+
+def dump_outputs(path, outs, model, bucket):
+    """--dump-outputs DIR: what the last timed step handed back, as .npy files -- loss (float64), every call's scores and
+    logits, the hidden state of the last call, the gradients and the parameters after the optimizer step (float32).  Per-row
+    outputs larger than DUMP_ROWS rows are sampled at rows fixed by a seeded generator (the same rows in every run with the
+    same arguments).  Returns {file: shape}."""
+    os.makedirs(path, exist_ok=True)
+    written = {}
+
+    def save(name, t, nrows=None, seed=0):
+        t = t.detach()
+        if nrows is not None and t.shape[0] > nrows:
+            idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))[:nrows].sort().values
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(path, name + '.npy'), a)
+        written[name + '.npy'] = list(a.shape)
+        return a.nbytes
+
+    nbytes = save('loss', outs['loss'].double().reshape(1))
+    for c, (scores, logits) in enumerate(outs['calls']):
+        nbytes += save(f'call{c}_scores', scores, DUMP_ROWS, seed=2 * c)
+        nbytes += save(f'call{c}_logits', logits, DUMP_ROWS, seed=2 * c + 1)
+    h = outs['h']
+    nbytes += save('hidden_last', h, max(1, DUMP_HIDDEN_BYTES // (4 * h[0].numel())), seed=1 << 20)
+    nbytes += save('grads', bucket.flat)
+    nbytes += save('params', torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
+    assert nbytes <= 64 << 20, f'--dump-outputs wrote {nbytes} bytes (limit 64 MB)'
+    return written
 
 
 def total_over_ranks(v, world, dev):
@@ -813,6 +865,14 @@ def main():
                          'c5 = configs[4]')
     ap.add_argument('--windows', type=int, default=None, help='tracking windows per GPU per step (rolling workloads; default '
                     '16384 for c2, 4096 for c4)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every block beyond the headline line: the per-stage roofline profile, '
+                         'at N = 1 the CPU baseline and the batch-1 latency and loop blocks, at N > 1 the all-reduce and C4 / C5 '
+                         'blocks; the --no-* options below drop single blocks of it.  Off: set up, warm up, time the steps, print '
+                         'the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (rank 0; a fixed, seeded sample of large '
+                         'per-row outputs, under 64 MB in all)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-stage-profile', action='store_true')
     ap.add_argument('--no-latency', action='store_true', help='skip the batch-1 latency block')
@@ -862,18 +922,23 @@ def main():
     # builds the per-graph caches (edge tiles, index records) and brings a fresh box's clocks and allocator up (a first process
     # on a cold box was seen at 36 ms per step with W = 2 where every later run gave 29)
     SETUP_STEPS = 2
-    dt = timed_steps(wl['step'], args.steps, args.warmup, world, dev, setup=SETUP_STEPS)
+    last = {} if args.dump_outputs and rank == 0 else None
+    dt = timed_steps(wl['step'], args.steps, args.warmup, world, dev, setup=SETUP_STEPS, outs=last)
     cfg_main = wl['config']
     total_edges = total_over_ranks(edge_iters, world, dev)
     value = total_edges * args.steps / dt
+    if last is not None:
+        written = dump_outputs(args.dump_outputs, last, model, bucket)
+        print(f'[bench] outputs of the last timed step -> {args.dump_outputs}: {written}', file=sys.stderr, flush=True)
+        last = None
 
     roofline = None
     extra = {}
-    if world > 1:
+    if world > 1 and args.full:
         extra['allreduce'] = allreduce_block(bucket, world, dev, args.backend)
-    if rank == 0 and not args.no_stage_profile and wl['shape']['kind'] == 'static':
+    if rank == 0 and args.full and not args.no_stage_profile and wl['shape']['kind'] == 'static':
         roofline, extra['stage_roofs'] = wide_stage_profile(plans[-1].graph, H)
-    elif rank == 0 and not args.no_stage_profile:
+    elif rank == 0 and args.full and not args.no_stage_profile:
         t, flops, nbytes = stage_profile(model, plans[-1], H)
         # the dominant kernel AMONG THOSE THE STEP RUNS: with the one-pass backward (default) the two stand-alone
         # backward kernels are measured for comparison only
@@ -962,14 +1027,14 @@ def main():
                 'MFMAs alone hold the pipe for ~45 % of the kernel), not by HBM -- DESIGN.md section 4')
         extra['stage_graph'] = dict(N=plans[-1].graph.N, E=plans[-1].graph.E, Dn=plans[-1].graph.Dn)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and wl['shape']['kind'] == 'rolling':
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and wl['shape']['kind'] == 'rolling':
         cpu = cpu_baseline(frames, mean_dets, max_dets, F, H, seed=1)
 
     lat = None
-    if rank == 0 and world == 1 and not args.no_latency and args.workload == 'c2':
+    if rank == 0 and world == 1 and args.full and not args.no_latency and args.workload == 'c2':
         lat = latency_batch1()
 
-    if world > 1 and args.workload == 'c2' and not args.no_scaling_extras:
+    if world > 1 and args.full and args.workload == 'c2' and not args.no_scaling_extras:
         # BASELINE.json configs[3] / configs[4] behind the timed C2 region (every rank takes part: barriers + all-reduces)
         wl = model = bucket = None
         plans = None
@@ -984,11 +1049,11 @@ def main():
                    higher_is_better=True, scaling='weak', vs_baseline=None, dtype='f32', data='synthetic',
                    arithmetic=('fp32 in/out; GRU GEMMs as bf16x6 split products on the bf16 matrix pipe, fp32 accumulate, '
                                'error <= the f32 MFMA chain (tools/pilot_split.py)') if split_enabled() else 'fp32 MFMA',
-                   config=dict(cfg_main, parallelism=f'sequence-dp{world}'),
+                   config=dict(cfg_main, parallelism=f'sequence-dp{world}'), full=args.full,
                    roofline=roofline, cpu_baseline=cpu)
         out.update(extra)
         out['latency_batch1'] = lat
-        out['loop_batch1'] = loop_batch1() if (world == 1 and not args.no_loops and args.workload == 'c2') else None
+        out['loop_batch1'] = loop_batch1() if (world == 1 and args.full and not args.no_loops and args.workload == 'c2') else None
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

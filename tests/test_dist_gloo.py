@@ -222,7 +222,7 @@ def test_bench_two_rank_branch_runs_end_to_end():
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', 'gloo',
-           '--single-device', '--windows', '256', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-latency',
+           '--single-device', '--windows', '256', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-latency',
            '--no-loops', '--extras-c4-windows', '64', '--extras-c5-frames', '6', '--extras-c5-dets', '40']
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
