@@ -288,6 +288,18 @@ int tmpnn_gru_bwd_fused(const int32_t* rows, int R, int xmode, const int32_t* sr
                         const int32_t* add_src, const int32_t* add_dst, const float* add_msg, int ld_add,
                         float* dW_ih, float* dW_hh, float* db_ih, float* db_hh,
                         void* ws, size_t ws_bytes, tmpnn_stream stream);
+/* The same backward for rows whose incoming state h[row] is ZERO -- a forward call's new edge rows (xmode 1: x = h[src] -
+ * h[dst]; available when tmpnn_gru_bwd_fused_zero_state_available(H, IN, xmode) != 0, i.e. H = IN = 64, xmode 1).  It does
+ * not read h[row] nor the fourth gate plane (ghn = b_hn exactly: b_hn = b_hh + 2H), writes d_msg and accumulates dW_ih,
+ * db_ih and db_hh (dW_hh gets nothing); d_h[row] is NOT formed, so the row-F adjoint is not taken either: for a call's new
+ * rows it lies behind d_h_in.  ws: tmpnn_gru_bwd_fused_ws(R, IN, H) bytes. */
+int tmpnn_gru_bwd_fused_zero_state_available(int H, int IN, int xmode);
+int tmpnn_gru_bwd_fused_zero_state(const int32_t* rows, int R, const int32_t* src, const int32_t* dst, int IN,
+                                   const float* h, int ld_h, int H, const float* w_ih, const float* b_hn,
+                                   const float* gates, size_t gate_plane, const float* d_hout, int ld_dhout,
+                                   const float* dy, const float* w_head, float* d_msg, int ld_dmsg,
+                                   float* dW_ih, float* db_ih, float* db_hh,
+                                   void* ws, size_t ws_bytes, tmpnn_stream stream);
 
 /* tmpnn_gru_fwd's xmode 3 (edge cell over the projected det rows `proj` [Dn][ld_proj >= 3H] of tmpnn_rows_linear) over
  * EDGE TILES (rows_per_tile = 32, covering the graph's R edge rows): the distinct projected rows of a tile are staged in

@@ -130,6 +130,11 @@ _SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    'tmpnn_gru_bwd_fused_zero_state_available': (c_int, [c_int, c_int, c_int]),
+    'tmpnn_gru_bwd_fused_zero_state': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p,
+                                               c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_size_t, c_void_p]),
     'tmpnn_rows_linear': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     'tmpnn_transpose': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'tmpnn_input_bn_fwd': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -1959,6 +1959,257 @@ __global__ __launch_bounds__(512) void k_gru_bwd_two(GruBwdFusedArgs a, int ntil
     }
 }
 
+// ==========================================================================================
+// The one-pass backward of rows whose incoming state is ZERO (k_gru_bwd_zs: H = IN = 64, diff message): a forward call's new
+// edge rows (functional.py mp_forward zero-fills them).  With h_prev = 0: dW_hh gets nothing, ghn = b_hn exactly (the fourth
+// gate plane is not read), dz = -d0 n z (1-z), and d_h is not formed -- the rows' d_h lies at or behind the call's first new
+// row, which no one reads (d_h_in is d_hcat[:N_old]; the row-F adjoint lands in d_h too and is dropped with it).  What is left
+// is the W_ih side of k_gru_bwd_two, spread over all eight waves of the block:
+//   * wave (role, q): data product d_msg = d_gi W_ih for the 16 columns 16 q .. of the tile's rows 16 role .. + 15 (the same
+//     W^T slice in registers as k_gru_bwd_two), and dW_ih tiles jt0 + {0,1,2} / tt for the K-step (row half) `role` only; the
+//     role-1 partials go to the slab's (unused) W_hh columns and the reduction adds the two halves (k_gru_reduce_w_zs);
+//   * the bias gradients are f32 column sums taken in the staging: a thread keeps the four sums of its row position and
+//     columns (dr, dz, dn, dn r; db_ih = [dr|dz|dn], db_hh = [dr|dz|dn r]) and the block folds its 32 row positions in order
+//     at the end;
+//   * LDS: the images of k_gru_bwd_two at the same offsets without the E image (72 KiB per buffer; the dn r and h halves
+//     stay unwritten).
+// Every wave runs the same straight-line code: role only moves addresses (no role branch, no scratch in the loop).
+// ==========================================================================================
+template <int UP>
+__global__ __launch_bounds__(512) void k_gru_bwd_zs(GruBwdFusedArgs a, const float* __restrict__ b_hn, int ntiles) {
+    constexpr int H = 64;
+    constexpr int SUB = 32 * 128;
+    constexpr int PA = 2 * SUB, PB = SUB;
+    constexpr int OFF_B = 3 * PA;
+    constexpr int BUF = OFF_B + 3 * PB;            // 72 KiB per buffer (uint16 elements)
+    extern __shared__ float lds[];
+    uint16_t* const lds16 = reinterpret_cast<uint16_t*>(lds);
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int role = wave >> 2, q = wave & 3;                 // role: row half of the data product, K-step of dW
+    const int j16 = lane & 15, kq = lane >> 4;
+    const int srow = 4 * wave + kq, f4 = 4 * j16;
+    const int n0 = 16 * q;
+    uint4 wq[6][3];
+#pragma unroll
+    for (int s6 = 0; s6 < 6; ++s6) {
+        const int ch = s6 < 4 ? 4 * kq + s6 : 16 + 4 * (s6 - 4) + kq;
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = a.w_ih[(size_t)(8 * ch + i) * a.ld_wih + n0 + j16];
+        const Split8 sp = split8_arr(v);
+        wq[s6][0] = sp.p1; wq[s6][1] = sp.p2; wq[s6][2] = sp.p3;
+    }
+    const float headl = (UP & 2) ? a.up.w_head[lane] : 0.f;
+    const float4 bhn = *reinterpret_cast<const float4*>(b_hn + f4);
+    const int st0 = dui_off(srow, f4);
+    const int swzj = dui_swz(j16), rowj = (16 * role + j16) * 128;
+    const int half = lane >> 5, c32 = lane & 31;
+    const int jt0 = (q >> 1) * 3, tt = q & 1;
+    const int i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3, tg = (lane >> 4) & 1;
+    const int trow = (8 * half + tq) * 128, tsw0 = (tq << 2) | (2 * half);
+    const int kofs = role * 2048;                              // K-step `role`: rows 16 role .. + 15
+    int offA[3], offB;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int col = (jt0 + j) * 32;
+        const int ch = ((col & 127) >> 3) + 2 * tg + (tp >> 1);
+        offA[j] = kofs + (col >> 7) * SUB + trow + ((ch ^ tsw0) << 3) + 4 * (tp & 1);
+    }
+    {
+        const int ch = ((tt * 32) >> 3) + 2 * tg + (tp >> 1);
+        offB = kofs + OFF_B + trow + ((ch ^ tsw0) << 3) + 4 * (tp & 1);
+    }
+    f32x16 acc[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+    float bs_r[4] = {0.f, 0.f, 0.f, 0.f}, bs_z[4] = {0.f, 0.f, 0.f, 0.f};
+    float bs_n[4] = {0.f, 0.f, 0.f, 0.f}, bs_nr[4] = {0.f, 0.f, 0.f, 0.f};
+
+    const int G = gridDim.x;
+    const int nmine = (ntiles - (int)blockIdx.x + G - 1) / G;       // >= 1
+    struct { float4 dh, r, z, n, xa, xb; float dy; } raw;
+    float d0[4], tv[4];
+    auto row_of = [&](int tile, bool tvld, bool& vld) -> int {
+        const int lr = tile * 32 + srow;
+        vld = tvld && lr < a.R;
+        return vld ? lr : a.R - 1;
+    };
+    // staging of one row: slice 0 dr (+ the r, n, n r sums), 1 dz, 3 dn, 5 x; rows past R stage zeros (d0 = 0)
+#define ZS_SLICE(SL, img, vld)                                                                               \
+    do {                                                                                                     \
+        float o_[4];                                                                                         \
+        if ((SL) == 0) {                                                                                     \
+            const float dh_[4] = {raw.dh.x, raw.dh.y, raw.dh.z, raw.dh.w}, r_[4] = {raw.r.x, raw.r.y, raw.r.z, raw.r.w}; \
+            const float z_[4] = {raw.z.x, raw.z.y, raw.z.z, raw.z.w}, n_[4] = {raw.n.x, raw.n.y, raw.n.z, raw.n.w}; \
+            const float hn_[4] = {bhn.x, bhn.y, bhn.z, bhn.w};                                               \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                  \
+                float d_ = (UP & 1) ? dh_[i] : 0.f;                                                          \
+                if (UP & 2) d_ += raw.dy * __shfl(headl, f4 + i);                                            \
+                d0[i] = (vld) ? d_ : 0.f;                                                                    \
+                tv[i] = d0[i] * (1.0f - z_[i]) * (1.0f - n_[i] * n_[i]);                                     \
+                const float q_ = tv[i] * r_[i];                                                              \
+                o_[i] = q_ * hn_[i] * (1.0f - r_[i]);                                                        \
+                bs_r[i] += o_[i]; bs_n[i] += tv[i]; bs_nr[i] += q_;                                          \
+            }                                                                                                \
+            half_put((img), st0, PA, o_);                                                                    \
+        } else if ((SL) == 1) {                                                                              \
+            const float z_[4] = {raw.z.x, raw.z.y, raw.z.z, raw.z.w}, n_[4] = {raw.n.x, raw.n.y, raw.n.z, raw.n.w}; \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                  \
+                o_[i] = d0[i] * (0.0f - n_[i]) * z_[i] * (1.0f - z_[i]);                                     \
+                bs_z[i] += o_[i];                                                                            \
+            }                                                                                                \
+            half_put((img), st0 ^ 64, PA, o_);                                                               \
+        } else if ((SL) == 3) {                                                                              \
+            half_put((img), SUB + st0, PA, tv);                                                              \
+        } else if ((SL) == 5) {                                                                              \
+            const float xa_[4] = {raw.xa.x, raw.xa.y, raw.xa.z, raw.xa.w}, xb_[4] = {raw.xb.x, raw.xb.y, raw.xb.z, raw.xb.w}; \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) o_[i] = xa_[i] - xb_[i];                           \
+            half_put((img) + OFF_B, st0, PB, o_);                                                            \
+        }                                                                                                    \
+    } while (0)
+#define ZS_ISSUE_MAIN(SL, orow_)                                                                             \
+    do {                                                                                                     \
+        const size_t gp_ = a.gate_plane;                                                                     \
+        const float* g0_ = a.gates + (size_t)(orow_) * H + f4;                                               \
+        if ((SL) == 0) {                                                                                     \
+            if (UP & 1) raw.dh = *reinterpret_cast<const float4*>(a.up.d_hout + (size_t)(orow_) * a.up.ld_dhout + f4); \
+            if (UP & 2) raw.dy = a.up.dy[(orow_)];                                                           \
+            raw.r = TWO_LD4(g0_);                                                                            \
+        } else if ((SL) == 1) {                                                                              \
+            raw.n = TWO_LD4(g0_ + 2 * gp_);                                                                  \
+            raw.z = TWO_LD4(g0_ + gp_);                                                                      \
+        }                                                                                                    \
+    } while (0)
+#define ZS_ISSUE_GATHER(gs_, gd_)                                                                            \
+    do {                                                                                                     \
+        raw.xa = *reinterpret_cast<const float4*>(a.h + (size_t)(gs_) * a.ld_h + f4);                        \
+        raw.xb = *reinterpret_cast<const float4*>(a.h + (size_t)(gd_) * a.ld_h + f4);                        \
+    } while (0)
+
+    // ---- prologue: tile 0 staged into buffer 0, tile 1's planes requested (as k_gru_bwd_two)
+    bool valid_cur, valid_n;
+    int gs_cur, gd_cur;
+    int orow_n;
+    {
+        bool v0, v1;
+        const int lp0 = row_of(blockIdx.x, true, v0);
+        const int o0 = a.rows[lp0];
+        gs_cur = a.src[lp0]; gd_cur = a.dst[lp0];
+        ZS_ISSUE_MAIN(0, o0); ZS_ISSUE_MAIN(1, o0); ZS_ISSUE_GATHER(gs_cur, gd_cur);
+        const int lp1 = row_of(blockIdx.x + G, 1 < nmine, v1);
+        const int o1 = a.rows[lp1];
+        ZS_SLICE(0, lds16, v0); ZS_ISSUE_MAIN(0, o1);
+        ZS_SLICE(1, lds16, v0); ZS_ISSUE_MAIN(1, o1);
+        ZS_SLICE(3, lds16, v0);
+        ZS_SLICE(5, lds16, v0);
+        valid_cur = v1;
+        gs_cur = a.src[lp1]; gd_cur = a.dst[lp1];
+        const int lp2 = row_of(blockIdx.x + 2 * G, 2 < nmine, valid_n);
+        orow_n = a.rows[lp2];
+    }
+    __syncthreads();
+
+    for (int it = 0; it < nmine; ++it) {
+        const int tile = blockIdx.x + it * G;
+        uint16_t* const cur = lds16 + (it & 1) * BUF;
+        uint16_t* const nxt = lds16 + ((it & 1) ^ 1) * BUF;
+        const int er = a.rows[min(tile * 32 + 16 * role + j16, a.R - 1)];
+        const bool el = tile * 32 + 16 * role + j16 < a.R;
+        f32x4 accd;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) accd[i] = 0.f;
+#pragma unroll
+        for (int s6 = 0; s6 < 6; ++s6) {
+            uint4 bd[3];
+            const uint16_t* pd;
+            {
+                const int chunk = s6 < 4 ? 4 * kq + s6 : 4 * (s6 - 4) + kq;
+                pd = cur + (s6 >= 4 ? SUB : 0) + rowj + ((chunk ^ swzj) << 3);
+            }
+            if (s6 < 3) {                                       // dW_ih tile jt0 + s6, K-step `role`
+                uint4 aw[3], bt[3];
+                {       // (the x operand is read again for each dW tile: held over the three groups it costs a spill)
+                    const uint16_t* p0 = cur + offB;
+                    const uint16_t* p1 = cur + (offB ^ 8) + 4 * 128;
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) {
+                        const uint2 u0 = lds_read_tr(p0 + pc * PB), u1 = lds_read_tr(p1 + pc * PB);
+                        bt[pc] = make_uint4(u0.x, u0.y, u1.x, u1.y);
+                    }
+                }
+                const uint16_t* p0 = cur + offA[s6];
+                const uint16_t* p1 = cur + (offA[s6] ^ 8) + 4 * 128;
+#pragma unroll
+                for (int pc = 0; pc < 3; ++pc) {
+                    const uint2 u0 = lds_read_tr(p0 + pc * PA), u1 = lds_read_tr(p1 + pc * PA);
+                    aw[pc] = make_uint4(u0.x, u0.y, u1.x, u1.y);
+                }
+                ZS_SLICE(s6, nxt, valid_cur);
+                ZS_ISSUE_MAIN(s6, orow_n);
+                acc[s6] = mfma32_c<0>(aw, bt, acc[s6]); acc[s6] = mfma32_c<1>(aw, bt, acc[s6]);
+                acc[s6] = mfma32_c<2>(aw, bt, acc[s6]); acc[s6] = mfma32_c<3>(aw, bt, acc[s6]);
+                acc[s6] = mfma32_c<4>(aw, bt, acc[s6]); acc[s6] = mfma32_c<5>(aw, bt, acc[s6]);
+            } else {
+                ZS_SLICE(s6, nxt, valid_cur);
+                if (s6 == 3) ZS_ISSUE_GATHER(gs_cur, gd_cur);
+            }
+#pragma unroll
+            for (int pc = 0; pc < 3; ++pc) bd[pc] = *reinterpret_cast<const uint4*>(pd + pc * PA);
+            accd = mfma16_c<0>(wq[s6], bd, accd); accd = mfma16_c<1>(wq[s6], bd, accd);
+            accd = mfma16_c<2>(wq[s6], bd, accd); accd = mfma16_c<3>(wq[s6], bd, accd);
+            accd = mfma16_c<4>(wq[s6], bd, accd); accd = mfma16_c<5>(wq[s6], bd, accd);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        {
+            bool vnn;
+            const int lp2 = row_of(tile + 2 * G, it + 2 < nmine, vnn);
+            gs_cur = a.src[lp2]; gd_cur = a.dst[lp2];
+            valid_cur = valid_n;
+            const int lp3 = row_of(tile + 3 * G, it + 3 < nmine, valid_n);
+            orow_n = a.rows[lp3];
+            (void)vnn;
+        }
+        // ---- epilogue: lane (j16, kq) holds columns n0 + 4 kq .. + 3 of row 16 role + j16
+        int cofs = n0 + 4 * kq;
+        asm volatile("" : "+v"(cofs));
+        if (el) *reinterpret_cast<float4*>(a.d_msg + ((size_t)er * a.ld_dmsg + cofs)) =
+                    make_float4(accd[0], accd[1], accd[2], accd[3]);
+        __syncthreads();
+    }
+#undef ZS_ISSUE_GATHER
+#undef ZS_ISSUE_MAIN
+#undef ZS_SLICE
+    // ---- one slab per block: [3H][2H] (columns 0..H-1: K-step 0 of dW_ih, H..2H-1: K-step 1), then [2][3H] biases
+    float* sw = a.slab_w + (size_t)blockIdx.x * (3 * H) * (2 * H);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int jj = (jt0 + j) * 32 + acc_row(reg, half);
+            sw[(size_t)jj * (2 * H) + role * H + tt * 32 + c32] = acc[j][reg];
+        }
+    // bias sums: the 32 row positions of each column folded in order through the now idle LDS ([32][4][64] floats)
+    {
+        float* red = lds;
+        *reinterpret_cast<float4*>(red + srow * 256 + 0 * 64 + f4) = make_float4(bs_r[0], bs_r[1], bs_r[2], bs_r[3]);
+        *reinterpret_cast<float4*>(red + srow * 256 + 1 * 64 + f4) = make_float4(bs_z[0], bs_z[1], bs_z[2], bs_z[3]);
+        *reinterpret_cast<float4*>(red + srow * 256 + 2 * 64 + f4) = make_float4(bs_n[0], bs_n[1], bs_n[2], bs_n[3]);
+        *reinterpret_cast<float4*>(red + srow * 256 + 3 * 64 + f4) = make_float4(bs_nr[0], bs_nr[1], bs_nr[2], bs_nr[3]);
+        __syncthreads();
+        if (tid < 256) {
+            float s = 0.f;
+            for (int r = 0; r < 32; ++r) s += red[r * 256 + tid];
+            float* sb = a.slab_b + (size_t)blockIdx.x * 6 * H;
+            const int g = tid >> 6, c = tid & 63;          // g: r, z, n, n r
+            if (g < 3) sb[g * H + c] = s;                  // db_ih = [dr | dz | dn]
+            if (g != 2) sb[3 * H + (g == 3 ? 2 : g) * H + c] = s;     // db_hh = [dr | dz | dn r]
+        }
+    }
+}
+
 
 // dW_ih[j][k] += sum_rs slab[rs][j][k], k < IN ; dW_hh[j][k-IN] += ... ; biases likewise
 __global__ void k_gru_reduce_w(const float* __restrict__ slab_w, const float* __restrict__ slab_b, int n_rs,
@@ -2015,6 +2266,25 @@ __global__ void k_fold_slabs_gru(const float* __restrict__ slabs, size_t stride,
 #pragma unroll 8
     for (int k = k0; k < k1; ++k) s += slabs[(size_t)k * stride + i];
     out[(size_t)blockIdx.y * n + i] = s;
+}
+
+// k_gru_bwd_zs's slabs: dW_ih[j][k] += sum_rs (slab[rs][j][k] + slab[rs][j][H + k]) (the two K-steps); biases as k_gru_reduce_w
+__global__ void k_gru_reduce_w_zs(const float* __restrict__ slab_w, const float* __restrict__ slab_b, int n_rs, int H,
+                                  float* __restrict__ dW_ih, float* __restrict__ db_ih, float* __restrict__ db_hh) {
+    const size_t nI = (size_t)3 * H * H, nW = 2 * nI;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nI) {
+        const size_t o = (i / H) * (2 * H) + (i % H);
+        float s = 0.f;
+        for (int k = 0; k < n_rs; ++k) s += slab_w[(size_t)k * nW + o] + slab_w[(size_t)k * nW + o + H];
+        dW_ih[i] += s;
+    } else if (i < nI + (size_t)6 * H) {
+        const int b = (int)(i - nI);
+        float s = 0.f;
+        for (int k = 0; k < n_rs; ++k) s += slab_b[(size_t)k * 6 * H + b];
+        if (b < 3 * H) db_ih[b] += s;
+        else db_hh[b - 3 * H] += s;
+    }
 }
 
 
@@ -2320,6 +2590,67 @@ int tmpnn_gru_bwd_fused(const int32_t* rows, int R, int xmode, const int32_t* sr
     hipLaunchKernelGGL(k_gru_reduce_w, dim3(ceil_div((long)(nW + nB), 256)), dim3(256), 0, st, rw, rb, nred, IN, H,
                        dW_ih, dW_hh, db_ih, db_hh);
     return check_launch("gru_reduce_w");
+}
+
+int tmpnn_gru_bwd_fused_zero_state_available(int H, int IN, int xmode) {
+    return (H == 64 && IN == 64 && xmode == 1 && device_gives_160k()) ? 1 : 0;
+}
+
+int tmpnn_gru_bwd_fused_zero_state(const int32_t* rows, int R, const int32_t* src, const int32_t* dst, int IN,
+                                   const float* h, int ld_h, int H, const float* w_ih, const float* b_hn,
+                                   const float* gates, size_t gate_plane, const float* d_hout, int ld_dhout,
+                                   const float* dy, const float* w_head, float* d_msg, int ld_dmsg, float* dW_ih,
+                                   float* db_ih, float* db_hh, void* ws, size_t ws_bytes, tmpnn_stream stream) {
+    TM_REQUIRE(tmpnn_gru_bwd_fused_zero_state_available(H, IN, 1), "gru_bwd_fused_zero_state: H=%d IN=%d not supported", H, IN);
+    if (R == 0) return TMPNN_OK;
+    TM_REQUIRE(R > 0 && rows && src && dst && h && w_ih && b_hn && gates && d_msg && dW_ih && db_ih && db_hh,
+               "gru_bwd_fused_zero_state: null pointer");
+    TM_REQUIRE(d_hout != nullptr || dy != nullptr, "gru_bwd_fused_zero_state: no upstream gradient");
+    TM_REQUIRE(dy == nullptr || (w_head != nullptr && aligned16(w_head)),
+               "gru_bwd_fused_zero_state: dy needs a 16-byte aligned w_head");
+    TM_REQUIRE((ld_h & 3) == 0 && aligned16(h) && aligned16(gates) && (gate_plane & 3) == 0 && aligned16(w_ih) &&
+                   aligned16(b_hn) && (d_hout == nullptr || ((ld_dhout & 3) == 0 && aligned16(d_hout))) &&
+                   (ld_dmsg & 3) == 0 && aligned16(d_msg) && ld_dmsg >= IN && ld_h >= H,
+               "gru_bwd_fused_zero_state: rows must be 16-byte aligned");
+    const size_t need = tmpnn_gru_bwd_fused_ws(R, IN, H);
+    if (ws == nullptr || ws_bytes < need)
+        return set_error(TMPNN_EWORKSPACE, "gru_bwd_fused_zero_state: workspace %zu < %zu bytes", ws_bytes, need);
+    const int n_rs = fused_blocks(R);
+    const size_t nW = (size_t)3 * H * (IN + H), nB = (size_t)6 * H;
+    float* slab_w = reinterpret_cast<float*>(ws);
+    float* slab_b = slab_w + (size_t)n_rs * nW;
+    float* fold = slab_b + (size_t)n_rs * nB;
+    GruBwdFusedArgs a{rows, R, src, dst, nullptr, 0, 0, h, ld_h, w_ih, nullptr, gates, gate_plane,
+                      DhSrc{d_hout, ld_dhout, dy, w_head}, d_msg, ld_dmsg, nullptr, 0, nullptr, nullptr, nullptr, 0,
+                      slab_w, slab_b, IN};
+    const int ntiles = ceil_div(R, 32);
+    const size_t shm = 147456;                               // two 72 KiB operand-image sets
+    hipStream_t st = as_stream(stream);
+    const int up = (d_hout ? 1 : 0) | (dy ? 2 : 0);
+#define LZ(U)                                                                                                \
+    do {                                                                                                     \
+        TM_SHM_ONCE((k_gru_bwd_zs<U>), shm);                                                                 \
+        hipLaunchKernelGGL((k_gru_bwd_zs<U>), dim3(n_rs), dim3(512), shm, st, a, b_hn, ntiles);              \
+    } while (0)
+    if (up == 1) LZ(1); else if (up == 2) LZ(2); else LZ(3);
+#undef LZ
+    int rc = check_launch("gru_bwd_fused_zero_state");
+    if (rc) return rc;
+    const float* rw = slab_w;
+    const float* rb = slab_b;
+    int nred = n_rs;
+    if (n_rs > 64) {
+        const int ng = ceil_div(n_rs, 32);
+        float* fw = fold;
+        float* fb = fold + (size_t)ng * nW;
+        hipLaunchKernelGGL(k_fold_slabs_gru, dim3(ceil_div((long)nW, 256), ng), dim3(256), 0, st, slab_w, nW, n_rs, fw, nW);
+        hipLaunchKernelGGL(k_fold_slabs_gru, dim3(ceil_div((long)nB, 256), ng), dim3(256), 0, st, slab_b, nB, n_rs, fb, nB);
+        if ((rc = check_launch("gru_fold"))) return rc;
+        rw = fw; rb = fb; nred = ng;
+    }
+    hipLaunchKernelGGL(k_gru_reduce_w_zs, dim3(ceil_div((long)(3 * H * H + nB), 256)), dim3(256), 0, st, rw, rb, nred, H,
+                       dW_ih, db_ih, db_hh);
+    return check_launch("gru_reduce_w_zs");
 }
 
 #ifdef TMPNN_KEEP_VARIANTS

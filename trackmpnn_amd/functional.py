@@ -28,6 +28,9 @@ ATT_DROPOUT_P = 0.5
 # environment variable TMPNN_INPLACE_GRADS=1 for every module.  Default: off -- real gradients are returned.
 INPLACE_GRADS = os.environ.get('TMPNN_INPLACE_GRADS', '0') == '1'
 FUSED_BWD = os.environ.get('TMPNN_FUSED_BWD', '1') == '1'     # one-pass cell backward (see mp_backward); its A/B is a test
+# the one-pass edge backward of a call's NEW edge rows (zero incoming state) on its own kernel (see mp_backward);
+# TMPNN_BWD_ZERO_STATE=0 runs every edge row through the full kernel
+ZERO_STATE_BWD = os.environ.get('TMPNN_BWD_ZERO_STATE', '1') != '0'
 # wide cells: the det-side branch of the backward on a second stream next to the E-row matrix kernels (tmpnn_wide_gru_bwd_diff_aux)
 # (det-side branches of the wide cells on a second stream: worth 1.5-6 ms of a 195-ms C5 step until round 4's single-read segment sum
 #  took most of what it hid -- since then the two forms are within the run-to-run spread (4 alternating pairs: 186.8 vs 188.5 ms, a
@@ -630,15 +633,32 @@ def mp_backward(spec: ModelSpec, plan: CallPlan, saved: dict, P: Dict[str, torch
                 _lib.call('tmpnn_gru_fwd_tiles', edge_tiles(g, FWD_TILE_ROWS).cref(), E, proj_s.data_ptr(), 3 * H, hg, GH, H,
                           whh_t_s.data_ptr(), P[f + 'edge_gru.bias_ih'].data_ptr(), P[f + 'edge_gru.bias_hh'].data_ptr(),
                           h_scr.data_ptr() + 4 * gi * H, GH, gp, plane, None, None, 0, st)
-            _lib.call('tmpnn_gru_bwd_fused', g.edge_row.data_ptr(), E, xmode, g.src.data_ptr(), g.dst.data_ptr(),
-                      None, 0, 0, IN_e, hg, GH, H,
-                      P[f + 'edge_gru.weight_ih'].data_ptr(), P[f + 'edge_gru.weight_hh'].data_ptr(),
-                      gp, plane, dog, GH, dyp, we, dmsg.data_ptr(), IN_e, dhg, GH,
-                      g.src.data_ptr() if fuse else None, g.dst.data_ptr() if fuse else None,
-                      dmsg.data_ptr() if fuse else None, IN_e,
-                      grads[f + 'edge_gru.weight_ih'].data_ptr(), grads[f + 'edge_gru.weight_hh'].data_ptr(),
-                      grads[f + 'edge_gru.bias_ih'].data_ptr(), grads[f + 'edge_gru.bias_hh'].data_ptr(),
-                      ws_w.data_ptr(), ws_w.numel() * 4, st)
+            # a call's new edge rows enter with h = 0 (mp_forward zero-fills h_cat[N_old:]) and form the suffix [E_old, E) of
+            # the ascending edge list: their backward has no W_hh side and no d_h (those d_hcat rows lie behind d_h_in), so it
+            # runs on its own kernel; E_old from the plan (the call's new rows less its new det rows), never from the device
+            b_hn = P[f + 'edge_gru.bias_hh'].data_ptr() + 4 * 2 * H
+            E_old = E - (n - int(plan.new_det_row.numel())) if n > 0 else E
+            zs = (ZERO_STATE_BWD and n > 0 and K == 0 and xmode == 1 and 0 <= E_old < E and b_hn % 16 == 0
+                  and not (saved.get('proj') and gi in saved['proj'])
+                  and lib.tmpnn_gru_bwd_fused_zero_state_available(H, IN_e, xmode))
+            E_full = E_old if zs else E
+            if E_full > 0:
+                _lib.call('tmpnn_gru_bwd_fused', g.edge_row.data_ptr(), E_full, xmode, g.src.data_ptr(), g.dst.data_ptr(),
+                          None, 0, 0, IN_e, hg, GH, H,
+                          P[f + 'edge_gru.weight_ih'].data_ptr(), P[f + 'edge_gru.weight_hh'].data_ptr(),
+                          gp, plane, dog, GH, dyp, we, dmsg.data_ptr(), IN_e, dhg, GH,
+                          g.src.data_ptr() if fuse else None, g.dst.data_ptr() if fuse else None,
+                          dmsg.data_ptr() if fuse else None, IN_e,
+                          grads[f + 'edge_gru.weight_ih'].data_ptr(), grads[f + 'edge_gru.weight_hh'].data_ptr(),
+                          grads[f + 'edge_gru.bias_ih'].data_ptr(), grads[f + 'edge_gru.bias_hh'].data_ptr(),
+                          ws_w.data_ptr(), ws_w.numel() * 4, st)
+            if zs:
+                _lib.call('tmpnn_gru_bwd_fused_zero_state', g.edge_row.data_ptr() + 4 * E_old, E - E_old,
+                          g.src.data_ptr() + 4 * E_old, g.dst.data_ptr() + 4 * E_old, IN_e, hg, GH, H,
+                          P[f + 'edge_gru.weight_ih'].data_ptr(), b_hn, gp, plane, dog, GH, dyp, we,
+                          dmsg.data_ptr(), IN_e, grads[f + 'edge_gru.weight_ih'].data_ptr(),
+                          grads[f + 'edge_gru.bias_ih'].data_ptr(), grads[f + 'edge_gru.bias_hh'].data_ptr(),
+                          ws_w.data_ptr(), ws_w.numel() * 4, st)
         else:
             # node GRU backward: d_es -> dmsg[det rows, 0:H], d_hcat[det rows]
             _lib.call('tmpnn_gru_bwd_data', g.det_row.data_ptr(), Dn, H, hg, GH, H,
