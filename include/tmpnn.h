@@ -308,6 +308,16 @@ int tmpnn_gru_bwd_fused_zero_state(const int32_t* rows, int R, const int32_t* sr
 int tmpnn_gru_fwd_tiles(const tmpnn_edge_tiles* tiles, int R, const float* proj, int ld_proj, const float* h, int ld_h, int H,
                         const float* whh_t, const float* b_ih, const float* b_hh, float* h_out, int ld_out, float* gates,
                         size_t gate_plane, const float* w_head, float* logit_part, size_t part_stride, tmpnn_stream stream);
+/* The same cell for tile lists whose rows all have a ZERO incoming state -- a call's new edge rows (available when
+ * tmpnn_gru_fwd_tiles_zero_state_available(H, xmode) != 0: H in {32, 64}, xmode 3, rows_per_tile = 32).  h is not read and
+ * there is no W_hh product; outputs bit-identical to tmpnn_gru_fwd_tiles on such rows.  Writes h_out, the r, z, n gate
+ * planes (when gates != NULL) and the head partials (when logit_part != NULL); the fourth plane (hn = b_hh[2H:3H]) only
+ * when write_hn != 0 -- tmpnn_gru_bwd_fused_zero_state does not read it. */
+int tmpnn_gru_fwd_tiles_zero_state_available(int H, int xmode);
+int tmpnn_gru_fwd_tiles_zero_state(const tmpnn_edge_tiles* tiles, int R, const float* proj, int ld_proj, int H,
+                                   const float* b_ih, const float* b_hh, float* h_out, int ld_out, float* gates,
+                                   size_t gate_plane, int write_hn, const float* w_head, float* logit_part, size_t part_stride,
+                                   tmpnn_stream stream);
 
 /* out[r, 0:NOUT] = in[rows[r], 0:H] @ wt[H][NOUT]  (compact output rows; H in {32, 64}, NOUT = 3H):
  * the det-row projection P of tmpnn_gru_fwd's xmode 3. */

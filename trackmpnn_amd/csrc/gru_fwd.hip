@@ -697,7 +697,8 @@ __global__ __launch_bounds__(WPB * 64) void k_gru_fwd_split_node(GruFwdArgs a) {
 // row).  A tile with more than TCAP distinct dets takes the gathers of k_gru_fwd_split.  Same products, same order, same
 // epilogue arithmetic: bit-identical results.
 #define FT_MARK(i) do { } while (0)
-struct FwdTiles { const int32_t* t_row; const int32_t* t_loc; const int32_t* t_dptr; const int32_t* t_dets; int T; };
+// (zs_hn: read by the zero-state instantiation only -- it fills the struct's tail padding, so the layout is unchanged)
+struct FwdTiles { const int32_t* t_row; const int32_t* t_loc; const int32_t* t_dptr; const int32_t* t_dets; int T; int zs_hn; };
 static constexpr int TCAP = 24, TP_LD = 100;                   // dets staged per item; floats per staged row
 static constexpr int TP_AREA = TCAP * TP_LD;                   // floats per wave (>= 32 * STG_LD: the output staging tile)
 
@@ -764,12 +765,19 @@ __device__ __forceinline__ void tiled_stage_p2(const GruFwdArgs& a, const TiledI
     }
 }
 
+// ZS: the cell of rows whose incoming state is ZERO (a call's new edge rows, tmpnn_gru_fwd_tiles_zero_state).  The W_hh
+// side is dead -- no weight image (the P areas start at LDS offset 0: three blocks of four waves per CU, 12 waves against
+// the full kernel's 8; at four waves per SIMD the epilogue would spill), no h[row] load, no split, no MFMA -- and the epilogue runs on the values the full kernel holds for such a row: acc_r = acc_z =
+// acc_hn = +0 (a bf16x6 product of a zero operand), hp = 0.  Same source, same expressions: bit-identical to the full
+// kernel on those rows.  (The ZS = false instantiation compiles to the ISA of the kernel before the flag existed.)
+// The hn plane (= b_hn) is written only when tl.zs_hn is set (the zero-state backward does not read it).
 #define FT_STAGE_P tiled_stage_p2
-template <int H, int WPB>
-__global__ __launch_bounds__(WPB * 64) void k_gru_fwd_split_tiled(GruFwdArgs a, FwdTiles tl) {
+template <int H, int WPB, bool ZS = false>
+__global__ __launch_bounds__(WPB * 64, ZS ? 3 : 1) void k_gru_fwd_split_tiled(GruFwdArgs a, FwdTiles tl) {
     extern __shared__ float lds[];
     constexpr int H3 = 3 * H, KP = H + 8, NKB = H / 16, CW = H / 32, NQ4 = H / 8;
     uint16_t* sW = reinterpret_cast<uint16_t*>(lds);                  // [3][3H][KP]
+    if constexpr (!ZS)
     for (int i = threadIdx.x; i < H * H3 / 4; i += WPB * 64) {
         const int k = i / (H3 / 4), j0 = (i % (H3 / 4)) * 4;
         const float4 w = *reinterpret_cast<const float4*>(a.whh_t + (size_t)k * H3 + j0);
@@ -783,7 +791,7 @@ __global__ __launch_bounds__(WPB * 64) void k_gru_fwd_split_tiled(GruFwdArgs a, 
             sW[(2 * H3 + j0 + e) * KP + k] = q3;
         }
     }
-    float* area_base = reinterpret_cast<float*>(sW + 3 * H3 * KP);
+    float* area_base = reinterpret_cast<float*>(sW + (ZS ? 0 : 3 * H3 * KP));
     int* next_item = reinterpret_cast<int*>(area_base + WPB * TP_AREA);
     float* sBias = reinterpret_cast<float*>(next_item + 4);
     for (int i = threadIdx.x; i < H; i += WPB * 64) {
@@ -819,7 +827,7 @@ __global__ __launch_bounds__(WPB * 64) void k_gru_fwd_split_tiled(GruFwdArgs a, 
     const uint32_t area = lds_addr_g(stg);
     if (ix.nd <= TCAP) FT_STAGE_P<H>(a, ix, cw0, lane, area);
     float4 raw[NQ4];
-    {
+    if constexpr (!ZS) {
         const float4* xr = reinterpret_cast<const float4*>(a.h + (size_t)ix.row * a.ld_h + (H / 2) * half);
 #pragma unroll
         for (int i = 0; i < NQ4; ++i) raw[i] = xr[i];
@@ -836,18 +844,22 @@ __global__ __launch_bounds__(WPB * 64) void k_gru_fwd_split_tiled(GruFwdArgs a, 
         const int row = ix.row;
         const bool staged = ix.nd <= TCAP;
         Split8 b[NKB];
+        if constexpr (!ZS) {
 #pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) b[kb] = split8(raw[2 * kb], raw[2 * kb + 1]);
+            for (int kb = 0; kb < NKB; ++kb) b[kb] = split8(raw[2 * kb], raw[2 * kb + 1]);
+        }
         const TiledIdx nix = tiled_idx(tl, a.R, nt, c, lane);
-        if (nvalid) {
-            const float4* xr = reinterpret_cast<const float4*>(a.h + (size_t)nix.row * a.ld_h + (H / 2) * half);
+        if constexpr (!ZS) {
+            if (nvalid) {
+                const float4* xr = reinterpret_cast<const float4*>(a.h + (size_t)nix.row * a.ld_h + (H / 2) * half);
 #pragma unroll
-            for (int i = 0; i < NQ4; ++i) raw[i] = xr[i];
+                for (int i = 0; i < NQ4; ++i) raw[i] = xr[i];
+            }
         }
         f32x16 acc_r, acc_z, acc_hn, acc_in;
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc_r[i] = 0.f; acc_z[i] = 0.f; acc_hn[i] = 0.f; }
-        {
+        if constexpr (!ZS) {
             const uint16_t* wp0 = sW + (cw0 + c) * KP + (H / 2) * half;
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
@@ -865,8 +877,9 @@ __global__ __launch_bounds__(WPB * 64) void k_gru_fwd_split_tiled(GruFwdArgs a, 
         }
         // the staged P rows were requested an item ago; only the loads issued since (the next item's operand and index
         // loads, at least NQ4 of them) may still be in flight
+        // (ZS: no operand loads behind the DMA, only the next item's index loads -- wait for everything)
         if (staged) {
-            if (nvalid) {
+            if (!ZS && nvalid) {
                 if constexpr (NQ4 == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             } else {
@@ -874,9 +887,14 @@ __global__ __launch_bounds__(WPB * 64) void k_gru_fwd_split_tiled(GruFwdArgs a, 
             }
         }
         float4 hp4[4];
+        if constexpr (ZS) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            hp4[q] = *reinterpret_cast<const float4*>(a.h + (size_t)row * a.ld_h + cw0 + 8 * q + 4 * half);
+            for (int q = 0; q < 4; ++q) hp4[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                hp4[q] = *reinterpret_cast<const float4*>(a.h + (size_t)row * a.ld_h + cw0 + 8 * q + 4 * half);
+        }
         f32x16 outv;
         {
             float4 gs[4], gd[4], hs[4], hd[4];
@@ -979,7 +997,7 @@ __global__ __launch_bounds__(WPB * 64) void k_gru_fwd_split_tiled(GruFwdArgs a, 
             stage_store32<true>(stg, c, half, lane, acc_r, a.gates, H, cw0, row, r0, a.R);
             stage_store32<true>(stg, c, half, lane, acc_z, a.gates + a.gate_plane, H, cw0, row, r0, a.R);
             stage_store32<true>(stg, c, half, lane, acc_in, a.gates + 2 * a.gate_plane, H, cw0, row, r0, a.R);
-            stage_store32<true>(stg, c, half, lane, acc_hn, a.gates + 3 * a.gate_plane, H, cw0, row, r0, a.R);
+            if (!ZS || tl.zs_hn) stage_store32<true>(stg, c, half, lane, acc_hn, a.gates + 3 * a.gate_plane, H, cw0, row, r0, a.R);
         }
         if (!nvalid) break;
         cw0 = ncw0; t = nt; ix = nix;
@@ -1606,6 +1624,45 @@ int tmpnn_gru_fwd_tiles(const tmpnn_edge_tiles* tiles, int R, const float* proj,
         hipLaunchKernelGGL((k_gru_fwd_split_tiled<32, 8>), pgrid, dim3(512), shm, st, a, tl);
     }
     return check_launch("gru_fwd_split_tiled");
+}
+
+int tmpnn_gru_fwd_tiles_zero_state_available(int H, int xmode) { return (H == 32 || H == 64) && xmode == 3 && split_enabled(); }
+
+int tmpnn_gru_fwd_tiles_zero_state(const tmpnn_edge_tiles* tiles, int R, const float* proj, int ld_proj, int H,
+                                   const float* b_ih, const float* b_hh, float* h_out, int ld_out, float* gates,
+                                   size_t gate_plane, int write_hn, const float* w_head, float* logit_part, size_t part_stride,
+                                   tmpnn_stream stream) {
+    TM_REQUIRE(tmpnn_gru_fwd_tiles_zero_state_available(H, 3), "gru_fwd_tiles_zero_state: H=%d (H in {32, 64}, TMPNN_SPLIT on)", H);
+    TM_REQUIRE(R >= 0, "gru_fwd_tiles_zero_state: R=%d", R);
+    if (R == 0) return TMPNN_OK;
+    TM_REQUIRE(tiles != nullptr, "gru_fwd_tiles_zero_state: tiles is null");
+    TM_REQUIRE(tiles->rows_per_tile == 32 && tiles->T > 0 && (long)tiles->T * 32 >= R && (long)(tiles->T - 1) * 32 < R &&
+                   tiles->t_row && tiles->t_loc && tiles->t_dptr && tiles->t_dets,
+               "gru_fwd_tiles_zero_state: tile list (T=%d, rows_per_tile=%d) does not cover R=%d rows in 32-row tiles", tiles->T,
+               tiles->rows_per_tile, R);
+    TM_REQUIRE(proj && b_ih && b_hh && h_out, "gru_fwd_tiles_zero_state: null pointer");
+    TM_REQUIRE(ld_proj >= 3 * H && (ld_proj & 3) == 0 && aligned16(proj) && ld_out >= H && aligned16(h_out) && (ld_out & 3) == 0 &&
+                   aligned16(b_ih) && aligned16(b_hh) &&
+                   (gates == nullptr || (aligned16(gates) && (gate_plane & 3) == 0 && gate_plane >= (size_t)H)),
+               "gru_fwd_tiles_zero_state: layout (16-byte alignment, leading dimensions)");
+    TM_REQUIRE(logit_part == nullptr || (w_head != nullptr && aligned16(w_head)),
+               "gru_fwd_tiles_zero_state: fused head needs a 16-byte aligned w_head");
+    GruFwdArgs a{nullptr, R, nullptr, nullptr, proj, ld_proj, H, 0, nullptr, 0, H, nullptr, nullptr, b_ih, b_hh, h_out, ld_out,
+                 gates, gate_plane, w_head, logit_part, part_stride};
+    FwdTiles tl{tiles->t_row, tiles->t_loc, tiles->t_dptr, tiles->t_dets, tiles->T, write_hn ? 1 : 0};
+    hipStream_t st = as_stream(stream);
+    // no weight image: 40 KB of LDS per 4-wave block and <= 168 registers per lane -- three blocks per CU
+    const int ntiles = ceil_div(R, (H == 64) ? 96 : 128);
+    dim3 pgrid(ntiles < 768 ? ntiles : 768);
+    const size_t shm = sizeof(float) * ((size_t)4 * TP_AREA + 4 + 5 * H);
+    if (H == 64) {
+        TM_SHM_ONCE((k_gru_fwd_split_tiled<64, 4, true>), shm);
+        hipLaunchKernelGGL((k_gru_fwd_split_tiled<64, 4, true>), pgrid, dim3(256), shm, st, a, tl);
+    } else {
+        TM_SHM_ONCE((k_gru_fwd_split_tiled<32, 4, true>), shm);
+        hipLaunchKernelGGL((k_gru_fwd_split_tiled<32, 4, true>), pgrid, dim3(256), shm, st, a, tl);
+    }
+    return check_launch("gru_fwd_split_tiled_zs");
 }
 
 int tmpnn_rows_linear(const int32_t* rows, int R, const float* in, int ld_in, int H, const float* wt, int NOUT,

@@ -31,6 +31,9 @@ FUSED_BWD = os.environ.get('TMPNN_FUSED_BWD', '1') == '1'     # one-pass cell ba
 # the one-pass edge backward of a call's NEW edge rows (zero incoming state) on its own kernel (see mp_backward);
 # TMPNN_BWD_ZERO_STATE=0 runs every edge row through the full kernel
 ZERO_STATE_BWD = os.environ.get('TMPNN_BWD_ZERO_STATE', '1') != '0'
+# the tiled edge forward of a call's NEW edge rows on its state-free kernel (see mp_forward); TMPNN_FWD_ZERO_STATE=0 runs
+# every edge row through the full kernel (and zero-fills the new rows of the state for it)
+ZERO_STATE_FWD = os.environ.get('TMPNN_FWD_ZERO_STATE', '1') != '0'
 # wide cells: the det-side branch of the backward on a second stream next to the E-row matrix kernels (tmpnn_wide_gru_bwd_diff_aux)
 # (det-side branches of the wide cells on a second stream: worth 1.5-6 ms of a 195-ms C5 step until round 4's single-read segment sum
 #  took most of what it hid -- since then the two forms are within the run-to-run spread (4 alternating pairs: 186.8 vs 188.5 ms, a
@@ -303,8 +306,24 @@ def mp_forward(spec: ModelSpec, plan: CallPlan, x: torch.Tensor, h_in: Optional[
             if N_old > 0:
                 h_cat[:N_old].copy_(h_in)
     saved = dict(n=n)
+    # A call's new edge rows enter the edge cell with h = 0 and form the suffix [E_old, E) of the ascending edge list (E_old
+    # from the plan: the call's new rows less its new det rows).  Decided once, here, for both directions: the forward runs
+    # them on the state-free kernel, and the backward takes its zero-state kernel on exactly those rows when zs_bwd (then the
+    # forward does not write their hn plane, nor zero-fill their state rows: no kernel reads them).
+    lib = _lib.load()
+    E_old = E - (n - int(plan.new_det_row.numel())) if n > 0 else E
+    zs_fwd = (ZERO_STATE_FWD and n > 0 and K == 0 and spec.msg_type == 'diff' and H == 64 and g.src_pos is not None
+              and Dn > 0 and FWD_TILED and FWD_TILE_ROWS == 32 and 0 <= E_old < E and not RECOMPUTE_GATES
+              and all((P[f'factor_grus.{gi}.edge_gru.bias_hh'].data_ptr() + 4 * 2 * H) % 16 == 0 for gi in range(G))
+              and bool(lib.tmpnn_gru_fwd_tiles_zero_state_available(H, 3)))
+    zs_bwd = (zs_fwd and save and ZERO_STATE_BWD and FUSED_BWD and bool(lib.tmpnn_gru_bwd_fused_available(H, H, 0))
+              and bool(lib.tmpnn_gru_bwd_fused_available(H, spec.IN_e, 1))
+              and bool(lib.tmpnn_gru_bwd_fused_zero_state_available(H, spec.IN_e, 1)))
+    if zs_fwd and save:
+        saved['zs_bwd'] = zs_bwd
     if n > 0:
-        h_cat[N_old:].zero_()                       # new edge rows start at 0 (track_mpnn.py:61)
+        if not (zs_fwd and (zs_bwd or not save)):
+            h_cat[N_old:].zero_()                   # new edge rows start at 0 (track_mpnn.py:61)
         nd = int(plan.new_det_row.numel())
         S = plan.S
         if training and plan.min_seg_cnt <= 1:
@@ -370,7 +389,6 @@ def mp_forward(spec: ModelSpec, plan: CallPlan, x: torch.Tensor, h_in: Optional[
     att_saved = []
     xmode = 2 if spec.msg_type == 'concat' else 1
     plane = N * H
-    lib = _lib.load()
     use_proj = spec.msg_type == 'diff' and H <= 64 and g.src_pos is not None and Dn > 0
     # concat: [h_src | h_dst] W_ih^T = P1[src] + P2[dst] -- the same tiled kernel on a stacked table [P1; -P2] and tile lists
     # whose dst entries are offset by Dn (TMPNN_CONCAT_PROJ=0 keeps the per-edge GEMM over IN = 2H)
@@ -387,8 +405,8 @@ def mp_forward(spec: ModelSpec, plan: CallPlan, x: torch.Tensor, h_in: Optional[
         # (None for graphs without window labels).  Opt-in: measured slower than the CSR kernel
         win_plan(g)
     wide_preps = []
-    # the call's new EDGE rows enter the state as zeros (h_cat[N_old:] zero-filled above, only det rows written since): the
-    # segment sum does not read them.  (Measured and dropped in round 6: the tiled edge forward skipping the 72 MFMAs of tiles
+    # the call's new EDGE rows enter the state as zeros (h_cat[N_old:] zero-filled above unless no kernel reads those rows, only
+    # det rows written since): the segment sum does not read them.  (Measured and dropped in round 6: the tiled edge forward skipping the 72 MFMAs of tiles
     # made of such rows -- bit-equal, 8.10 -> 8.09 ms per step: the matrix pipe is not what an item waits for.)
     zero_from = N_old if n > 0 else N
     # output head fused into the cells' epilogues where the LDS-resident kernel runs (else tmpnn_heads_fwd)
@@ -455,9 +473,17 @@ def mp_forward(spec: ModelSpec, plan: CallPlan, x: torch.Tensor, h_in: Optional[
                       proj.data_ptr(), 3 * H, st)
             if FWD_TILED and E > 0:
                 recompute = RECOMPUTE_GATES and save
-                _lib.call('tmpnn_gru_fwd_tiles', edge_tiles(g, FWD_TILE_ROWS).cref(), E, proj.data_ptr(), 3 * H, hg, GH, H,
-                          e_whh_t.data_ptr(), P[f + 'edge_gru.bias_ih'].data_ptr(), P[f + 'edge_gru.bias_hh'].data_ptr(),
-                          og, GH, None if recompute else gp, plane, we_g, part_g, N, st)
+                E_full = E_old if zs_fwd else E
+                if E_full > 0:
+                    tiles = edge_tiles(g, FWD_TILE_ROWS, e1=E_full)
+                    _lib.call('tmpnn_gru_fwd_tiles', tiles.cref(), E_full, proj.data_ptr(), 3 * H, hg, GH, H,
+                              e_whh_t.data_ptr(), P[f + 'edge_gru.bias_ih'].data_ptr(), P[f + 'edge_gru.bias_hh'].data_ptr(),
+                              og, GH, None if recompute else gp, plane, we_g, part_g, N, st)
+                if zs_fwd:
+                    _lib.call('tmpnn_gru_fwd_tiles_zero_state', edge_tiles(g, FWD_TILE_ROWS, e0=E_old).cref(), E - E_old,
+                              proj.data_ptr(), 3 * H, H, P[f + 'edge_gru.bias_ih'].data_ptr(),
+                              P[f + 'edge_gru.bias_hh'].data_ptr(), og, GH, gp, plane, int(save and not zs_bwd), we_g,
+                              part_g, N, st)
                 if recompute:
                     saved.setdefault('proj', {})[gi] = (proj, e_whh_t)
             else:
@@ -638,9 +664,13 @@ def mp_backward(spec: ModelSpec, plan: CallPlan, saved: dict, P: Dict[str, torch
             # runs on its own kernel; E_old from the plan (the call's new rows less its new det rows), never from the device
             b_hn = P[f + 'edge_gru.bias_hh'].data_ptr() + 4 * 2 * H
             E_old = E - (n - int(plan.new_det_row.numel())) if n > 0 else E
-            zs = (ZERO_STATE_BWD and n > 0 and K == 0 and xmode == 1 and 0 <= E_old < E and b_hn % 16 == 0
-                  and not (saved.get('proj') and gi in saved['proj'])
-                  and lib.tmpnn_gru_bwd_fused_zero_state_available(H, IN_e, xmode))
+            if 'zs_bwd' in saved:
+                # the forward's decision: with it set, those rows' hn plane and state rows were never written
+                zs = saved['zs_bwd']
+            else:
+                zs = (ZERO_STATE_BWD and n > 0 and K == 0 and xmode == 1 and 0 <= E_old < E and b_hn % 16 == 0
+                      and not (saved.get('proj') and gi in saved['proj'])
+                      and lib.tmpnn_gru_bwd_fused_zero_state_available(H, IN_e, xmode))
             E_full = E_old if zs else E
             if E_full > 0:
                 _lib.call('tmpnn_gru_bwd_fused', g.edge_row.data_ptr(), E_full, xmode, g.src.data_ptr(), g.dst.data_ptr(),

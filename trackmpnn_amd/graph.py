@@ -131,7 +131,8 @@ class EdgeTiles:
 
 
 def build_edge_tiles(graph: FrameGraph, rows_per_tile: int = 128, src_group: int = 8, dst_group: int = 16,
-                     stats: bool = False, order: str = 'blocks', dst_offset: int = 0) -> EdgeTiles:
+                     stats: bool = False, order: str = 'blocks', dst_offset: int = 0,
+                     e0: int = 0, e1: Optional[int] = None) -> EdgeTiles:
     """Cut the graph's edge rows into tiles of `rows_per_tile` rows that touch few distinct dets.
 
     A frame block of the rolling graph is a dense [A srcs x D_t dsts] set of rows in src-major order
@@ -144,24 +145,30 @@ def build_edge_tiles(graph: FrameGraph, rows_per_tile: int = 128, src_group: int
     device, no host round trip unless `stats`).
 
     `dst_offset`: added to every dst entry of the det lists -- the concat message reads its src half and its dst half from two
-    different projected tables, stacked as rows [0, Dn) and [Dn, 2 Dn) of one (dst_offset = Dn)."""
+    different projected tables, stacked as rows [0, Dn) and [Dn, 2 Dn) of one (dst_offset = Dn).
+
+    `[e0, e1)`: tile only that range of the edge list (default: all of it) -- no tile mixes rows of two ranges."""
     if graph.src_pos is None or graph.dst_pos is None:
         raise ValueError('build_edge_tiles: the graph carries no src_pos / dst_pos')
     dev = graph.device
-    E, R = graph.E, int(rows_per_tile)
+    e1 = graph.E if e1 is None else int(e1)
+    e0 = int(e0)
+    if not 0 <= e0 <= e1 <= graph.E:
+        raise ValueError(f'build_edge_tiles: edge range [{e0}, {e1}) outside [0, {graph.E})')
+    E, R = e1 - e0, int(rows_per_tile)
     T = (E + R - 1) // R
     i32 = lambda t: t.to(torch.int32).contiguous()
     if T == 0:
         z = torch.zeros(0, dtype=torch.int32, device=dev)
         return EdgeTiles(0, R, z, z.clone(), torch.zeros(1, dtype=torch.int32, device=dev), z.clone())
-    s, d = graph.src_pos.long(), graph.dst_pos.long()
+    s, d = graph.src_pos[e0:e1].long(), graph.dst_pos[e0:e1].long()
     ns = graph.Dn // src_group + 1
     if order == 'rows':
-        so, do, ro = s, d, graph.edge_row.long()
+        so, do, ro = s, d, graph.edge_row[e0:e1].long()
     else:
         key = (((d // dst_group) * ns + s // src_group) * src_group + s % src_group) * dst_group + d % dst_group
         perm = torch.argsort(key)
-        so, do, ro = s[perm], d[perm], graph.edge_row.long()[perm]
+        so, do, ro = s[perm], d[perm], graph.edge_row[e0:e1].long()[perm]
     pad = T * R - E
     if pad:
         so = torch.cat([so, so[-1:].expand(pad)])            # padding slots repeat the last edge's dets (no new det)
@@ -184,14 +191,19 @@ def build_edge_tiles(graph: FrameGraph, rows_per_tile: int = 128, src_group: int
     return tiles
 
 
-def edge_tiles(graph: FrameGraph, rows_per_tile: int = 128, dst_offset: int = 0) -> EdgeTiles:
-    """The graph's cached tile list (built on first use)."""
+def edge_tiles(graph: FrameGraph, rows_per_tile: int = 128, dst_offset: int = 0, e0: int = 0,
+               e1: Optional[int] = None) -> EdgeTiles:
+    """The graph's cached tile list (built on first use); `[e0, e1)` tiles only that range of the edge list."""
     cache = graph.__dict__.setdefault('_tiles', {})
+    e1 = graph.E if e1 is None else int(e1)
     key = rows_per_tile if not dst_offset else (rows_per_tile, int(dst_offset))
+    if (int(e0), e1) != (0, graph.E):
+        key = (key, int(e0), e1)
     t = cache.get(key)
     if t is None:
         # dense frame blocks (a src's run of edges spans a good part of a tile) are cut into src x dst sub-blocks; graphs of
-        # small windows keep their row order.  The mean run length costs one host round trip, once per graph.
+        # small windows keep their row order (decided over the whole graph, whatever the range).  The mean run length costs
+        # one host round trip, once per graph and tile size.
         runs = 1
         if graph.E > 1:
             if graph.src_pos.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -201,12 +213,13 @@ def edge_tiles(graph: FrameGraph, rows_per_tile: int = 128, dst_offset: int = 0)
             runs = 1 + int((graph.src_pos[1:] != graph.src_pos[:-1]).sum())
         blocks = graph.E / runs >= rows_per_tile / 2
         od = 'blocks' if blocks else 'rows'
+        rng = dict(order=od, dst_offset=dst_offset, e0=e0, e1=e1)
         if rows_per_tile == 128:
-            t = build_edge_tiles(graph, 128, 8, 16, order=od, dst_offset=dst_offset)
+            t = build_edge_tiles(graph, 128, 8, 16, **rng)
         elif rows_per_tile == 16:
-            t = build_edge_tiles(graph, 16, 4, 4, order=od, dst_offset=dst_offset)
+            t = build_edge_tiles(graph, 16, 4, 4, **rng)
         else:
-            t = build_edge_tiles(graph, rows_per_tile, 4, 8, order=od, dst_offset=dst_offset)
+            t = build_edge_tiles(graph, rows_per_tile, 4, 8, **rng)
         cache[key] = t
     return t
 
