@@ -35,9 +35,10 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 4 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 5 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
-                               left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_* */
+                               left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
+                               5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -457,6 +458,37 @@ int tmpnn_train_losses_fwd(const tmpnn_graph* g, const float* logits, const floa
 int tmpnn_train_losses_bwd(const tmpnn_graph* g, const int32_t* src_pos, const int32_t* dst_pos, const float* logits,
                            const float* scores, const uint8_t* targets, const float* stats, const float* d_c, const float* d_f,
                            int tp_classifier, float* d_logits, float* d_scores, tmpnn_stream stream);
+/* The same losses for MANY windows of one call of a block-diagonal batch (trackmpnn_amd.train_batch.build_train_batch): per window
+ * its own create_targets, cross-entropy sum, focal sums and loss_f (= mean over its det rows + mean over its edge rows with the
+ * TP classifier, the edge mean without; NaN over an empty selection), the reference's per-chunk bookkeeping (train.py:70-81)
+ * kept apart for every window.  A window's lists name the det / edge INDICES (positions in det_row / edge_row) of its rows,
+ * ascending; every det of a listed det's CSR run and every endpoint of a listed edge must belong to the same window (the
+ * block-diagonal layout guarantees it).  A window with no rows at all (finished, or not in the batch) gets 0 in every output
+ * and its rows' gradients are 0.  Values and sums are formed exactly as tmpnn_train_losses_fwd forms them on the window's own
+ * subgraph (128-row chunks, four interleaved sums, the chunks in sequence), with no row limit per window.
+ * out [4][W]: loss_c, focal sum over the edge rows, focal sum over the det rows, loss_f -- one row of W values each.  targets [N] is written on the rows of
+ * the listed windows only; stats [Dn][2][4] on their dets.  ws: tmpnn_train_losses_win_ws floats.
+ * Backward: element-wise over the call's E + Dn rows, each row of d_logits / d_scores (either may be NULL) WRITTEN once;
+ * d_c [W] / d_f [W]: the seeds per window (device). */
+typedef struct tmpnn_loss_windows {
+    int32_t W;                /* windows */
+    int32_t n_det;            /* det_ptr[W] (host copy: sizes the workspace) */
+    int32_t n_edge;           /* edge_ptr[W] */
+    const int32_t* det_ptr;   /* [W + 1] */
+    const int32_t* det_idx;   /* [n_det]  det indices, window by window, ascending within a window */
+    const int32_t* edge_ptr;  /* [W + 1] */
+    const int32_t* edge_idx;  /* [n_edge] edge indices, likewise */
+    const int32_t* det_win;   /* [Dn] window of every det, -1 = none */
+    const int32_t* edge_win;  /* [E]  window of every edge, -1 = none */
+} tmpnn_loss_windows;
+size_t tmpnn_train_losses_win_ws(const tmpnn_loss_windows* w);
+int tmpnn_train_losses_win_fwd(const tmpnn_graph* g, const tmpnn_loss_windows* w, const float* logits, const float* scores,
+                               const uint8_t* labels, int tp_classifier, uint8_t* targets, float* stats, float* out, float* ws,
+                               size_t ws_floats, tmpnn_stream stream);
+int tmpnn_train_losses_win_bwd(const tmpnn_graph* g, const tmpnn_loss_windows* w, const int32_t* src_pos, const int32_t* dst_pos,
+                               const float* logits, const float* scores, const uint8_t* targets, const float* stats,
+                               const float* d_c, const float* d_f, int tp_classifier, float* d_logits, float* d_scores,
+                               tmpnn_stream stream);
 
 /* ======================================================================================================
  * Batch-1 path (the reference's real call pattern, train.py:92-107 / infer.py:60-87: ONE small

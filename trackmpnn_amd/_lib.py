@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -83,9 +83,16 @@ class CTrackRows(C.Structure):
                 ('dst', c_void_p), ('labels', c_void_p)]
 
 
+class CLossWindows(C.Structure):
+    """struct tmpnn_loss_windows (include/tmpnn.h): the loss windows of one call of a block-diagonal training batch."""
+    _fields_ = [('W', C.c_int32), ('n_det', C.c_int32), ('n_edge', C.c_int32), ('det_ptr', c_void_p), ('det_idx', c_void_p),
+                ('edge_ptr', c_void_p), ('edge_idx', c_void_p), ('det_win', c_void_p), ('edge_win', c_void_p)]
+
+
 _DGP = C.POINTER(CDGraph)
 _MPP = C.POINTER(CMpParams)
 _TRP = C.POINTER(CTrackRows)
+_LWP = C.POINTER(CLossWindows)
 
 # name -> (restype, argtypes); must mirror include/tmpnn.h (tests/test_abi.py cross-checks the names)
 _SIGNATURES = {
@@ -185,6 +192,11 @@ _SIGNATURES = {
                                        c_size_t, c_void_p]),
     'tmpnn_train_losses_bwd': (c_int, [_GP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p, c_void_p, c_void_p]),
+    'tmpnn_train_losses_win_ws': (c_size_t, [_LWP]),
+    'tmpnn_train_losses_win_fwd': (c_int, [_GP, _LWP, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_size_t, c_void_p]),
+    'tmpnn_train_losses_win_bwd': (c_int, [_GP, _LWP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

@@ -292,6 +292,187 @@ __global__ __launch_bounds__(256) void k_train_losses_bwd(tmpnn_graph g, const i
     }
 }
 
+// ---- the same losses for many windows of one call of a block-diagonal batch (tmpnn_loss_windows) -----------------------------
+// One wave64 workgroup per window: its phases (targets, cross-entropy, focal terms, the three sums) are the ones of
+// k_train_losses_fwd over the window's det / edge lists, every value formed by the same expression, and the sums taken in
+// tl_ordered_sum's order -- 128-row chunks, four interleaved running sums per chunk, the chunks in sequence -- folded 16 chunks
+// per pass of the wave, so a window of any size gives what the one-launch loss gives on its own subgraph.  The per-row terms go
+// through the workspace (position in the window lists); out [4][W]: the four values of k_train_losses_fwd's out per window.
+static constexpr int TLW_THREADS = 64;
+
+__device__ float tlw_ordered_sum(const float* __restrict__ v, int R, float* s_part /* [64] */, float* s_chunk /* [16] */) {
+    const int tid = threadIdx.x;
+    const int nch = (R + 127) / 128;
+    float total = 0.f;
+    for (int c0 = 0; c0 < nch; c0 += TLW_THREADS / 4) {
+        const int j = c0 + (tid >> 2), slot = tid & 3;
+        float acc = 0.f;
+        if (j < nch) {
+            const int r1 = min(R, j * 128 + 128);
+            for (int r = j * 128 + slot; r < r1; r += 4) acc += v[r];
+        }
+        s_part[tid] = acc;
+        __syncthreads();
+        if (tid < TLW_THREADS / 4) s_chunk[tid] = s_part[4 * tid] + s_part[4 * tid + 1] + s_part[4 * tid + 2] + s_part[4 * tid + 3];
+        __syncthreads();
+        if (tid == 0)
+            for (int k = 0; k < TLW_THREADS / 4 && c0 + k < nch; ++k) total += s_chunk[k];
+        __syncthreads();
+    }
+    return total;                                            // valid on thread 0
+}
+
+__global__ __launch_bounds__(TLW_THREADS) void k_train_losses_win_fwd(tmpnn_graph g, tmpnn_loss_windows lw,
+                                                                      const float* __restrict__ logits,
+                                                                      const float* __restrict__ scores,
+                                                                      const uint8_t* __restrict__ labels, int tp,
+                                                                      uint8_t* __restrict__ targets, float* __restrict__ stats,
+                                                                      float* __restrict__ out, float* __restrict__ ws) {
+    __shared__ float s_part[TLW_THREADS], s_chunk[TLW_THREADS / 4];
+    const int w = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int d0 = lw.det_ptr[w], Dn = lw.det_ptr[w + 1] - d0;
+    const int e0 = lw.edge_ptr[w], E = lw.edge_ptr[w + 1] - e0;
+    const int32_t* __restrict__ dl = lw.det_idx + d0;
+    const int32_t* __restrict__ el = lw.edge_idx + e0;
+    float* loss_det = ws + d0;                               // [n_det]
+    float* fd = ws + lw.n_det + d0;                          // [n_det]
+    float* fe = ws + 2 * (size_t)lw.n_det + e0;              // [n_edge]
+    if (Dn == 0 && E == 0) {                                 // no rows: not a live window of this call
+        if (tid < 4) out[(size_t)tid * lw.W + w] = 0.f;
+        return;
+    }
+    for (int i = tid; i < E; i += TLW_THREADS) targets[g.edge_row[el[i]]] = 0;
+    __syncthreads();
+    // create_targets (k_targets)
+    for (int i = tid; i < Dn; i += TLW_THREADS) {
+        const int d = dl[i];
+        const int drow = g.det_row[d];
+        targets[drow] = labels[drow];
+        int last_past = -1, first_future = -1;
+        for (int p = g.rowptr[d]; p < g.rowptr[d + 1]; ++p) {
+            const int v = g.inc[p];
+            const int row = v & 0x7fffffff;
+            if (!labels[row]) continue;
+            if (v < 0) last_past = row;
+            else if (first_future < 0) first_future = row;
+        }
+        if (last_past >= 0) targets[last_past] = 1;
+        if (first_future >= 0) targets[first_future] = 1;
+    }
+    __syncthreads();
+    // cross-entropy per det (k_ce_fwd)
+    for (int i = tid; i < Dn; i += TLW_THREADS) {
+        const int d = dl[i];
+        const int p0 = g.rowptr[d], p1 = g.rowptr[d + 1];
+        float loss = 0.f;
+        for (int s = 0; s < 2; ++s) {
+            const bool want_neg = (s == 0);
+            float mx = -INFINITY;
+            int n = 0, trow = -1;
+            for (int p = p0; p < p1; ++p) {
+                const int v = g.inc[p];
+                if ((v < 0) != want_neg) continue;
+                const int row = v & 0x7fffffff;
+                mx = fmaxf(mx, logits[row]);
+                ++n;
+                if (targets[row]) {
+                    if (want_neg) trow = row;
+                    else if (trow < 0) trow = row;
+                }
+            }
+            float z = 0.f;
+            if (trow >= 0) {
+                for (int p = p0; p < p1; ++p) {
+                    const int v = g.inc[p];
+                    if ((v < 0) != want_neg) continue;
+                    z += expf(logits[v & 0x7fffffff] - mx);
+                }
+                loss += (logf(z) + mx - logits[trow]) / (float)n;
+            }
+            float* st = stats + ((size_t)d * 2 + s) * 4;
+            st[0] = mx; st[1] = z; st[2] = (float)trow; st[3] = (float)n;
+        }
+        loss_det[i] = loss;
+    }
+    // focal terms per row (k_focal_fwd with gamma = 0, no alpha)
+    for (int i = tid; i < E + (tp ? Dn : 0); i += TLW_THREADS) {
+        const int row = i < E ? g.edge_row[el[i]] : g.det_row[dl[i - E]];
+        const bool t = targets[row] != 0;
+        const float sc = scores[row];
+        const float logpt = logf((t ? sc : 1.0f - sc) + 1e-10f);
+        const float v = -1.0f * logpt * 1.0f;
+        if (i < E) fe[i] = v; else fd[i - E] = v;
+    }
+    __syncthreads();
+    const float lc = tlw_ordered_sum(loss_det, Dn, s_part, s_chunk);
+    const float se = tlw_ordered_sum(fe, E, s_part, s_chunk);
+    const float sd = tp ? tlw_ordered_sum(fd, Dn, s_part, s_chunk) : 0.f;
+    if (tid == 0) {
+        const float inv_e = E > 0 ? (float)(1.0 / E) : 0.f, inv_d = Dn > 0 ? (float)(1.0 / Dn) : 0.f;
+        const float me = E > 0 ? se * inv_e : __builtin_nanf("");
+        const float md = Dn > 0 ? sd * inv_d : __builtin_nanf("");
+        const size_t W = (size_t)lw.W;
+        out[w] = lc; out[W + w] = se; out[2 * W + w] = sd;
+        out[3 * W + w] = tp ? md + me : me;
+    }
+}
+
+// the adjoint, every row of the call written once: items [0, E) are the edge rows, [E, E + Dn) the det rows; a row takes its
+// window's seeds and 1 / E, 1 / Dn (k_train_losses_bwd per window), rows of no listed window get 0
+__global__ __launch_bounds__(256) void k_train_losses_win_bwd(tmpnn_graph g, tmpnn_loss_windows lw,
+                                                              const int32_t* __restrict__ src_pos,
+                                                              const int32_t* __restrict__ dst_pos,
+                                                              const float* __restrict__ logits, const float* __restrict__ scores,
+                                                              const uint8_t* __restrict__ targets,
+                                                              const float* __restrict__ stats, const float* __restrict__ d_c,
+                                                              const float* __restrict__ d_f, int tp, float* __restrict__ d_logits,
+                                                              float* __restrict__ d_scores) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int E = g.E, Dn = g.Dn;
+    if (i >= E + Dn) return;
+    const bool is_e = i < E;
+    const int row = is_e ? g.edge_row[i] : g.det_row[i - E];
+    const int w = is_e ? lw.edge_win[i] : lw.det_win[i - E];
+    if (w < 0) {
+        if (d_logits) d_logits[row] = 0.f;
+        if (d_scores) d_scores[row] = 0.f;
+        return;
+    }
+    if (d_logits) {
+        float v = 0.f;
+        if (is_e) {                                          // k_ce_bwd
+            const float l = logits[row];
+            float acc = 0.f;
+            {
+                const float* st = stats + ((size_t)src_pos[i] * 2 + 1) * 4;
+                const int trow = (int)st[2];
+                if (trow >= 0) acc += (expf(l - st[0]) / st[1] - (trow == row ? 1.f : 0.f)) / st[3];
+            }
+            {
+                const float* st = stats + ((size_t)dst_pos[i] * 2 + 0) * 4;
+                const int trow = (int)st[2];
+                if (trow >= 0) acc += (expf(l - st[0]) / st[1] - (trow == row ? 1.f : 0.f)) / st[3];
+            }
+            v = 0.f + d_c[w] * acc;
+        }
+        d_logits[row] = v;
+    }
+    if (d_scores) {
+        float v = 0.f;
+        if (is_e || tp) {                                    // k_focal_bwd, gamma = 0: dq = -1 / q
+            const int n = is_e ? lw.edge_ptr[w + 1] - lw.edge_ptr[w] : lw.det_ptr[w + 1] - lw.det_ptr[w];
+            const float inv = (float)(1.0 / n);
+            const bool t = targets[row] != 0;
+            const float sc = scores[row];
+            const float q = (t ? sc : 1.0f - sc) + 1e-10f;
+            const float dq = -1.0f / q;
+            v = 0.f + d_f[w] * inv * dq * (t ? 1.0f : -1.0f);
+        }
+        d_scores[row] = v;
+    }
+}
+
 // ---- binary cross-entropy with logits, summed (the loss of SURVEY 8(d)'s metric: BCE on ALL logits of a call against fixed
 // {0,1} targets) in one pass each way instead of torch's six element-wise launches + reduction per call ----------------------
 // loss_i = max(l, 0) - l t + log(1 + exp(-|l|)) ; d loss_i / d l = sigmoid(l) - t.  Thread -> contiguous run of 16 elements,
@@ -484,6 +665,41 @@ int tmpnn_train_losses_bwd(const tmpnn_graph* g, const int32_t* src_pos, const i
     hipLaunchKernelGGL(k_train_losses_bwd, dim3(ceil_div(g->N, 256)), dim3(256), 0, as_stream(stream), *g, src_pos, dst_pos,
                        logits, scores, targets, stats, d_c, d_f, tp_classifier ? 1 : 0, inv_e, inv_d, d_logits, d_scores);
     return check_launch("train_losses_bwd");
+}
+
+size_t tmpnn_train_losses_win_ws(const tmpnn_loss_windows* w) {
+    if (!w || w->n_det < 0 || w->n_edge < 0) return 0;
+    return (size_t)2 * w->n_det + (size_t)w->n_edge + 1;
+}
+
+int tmpnn_train_losses_win_fwd(const tmpnn_graph* g, const tmpnn_loss_windows* w, const float* logits, const float* scores,
+                               const uint8_t* labels, int tp_classifier, uint8_t* targets, float* stats, float* out, float* ws,
+                               size_t ws_floats, tmpnn_stream stream) {
+    TM_REQUIRE(g && w && logits && scores && labels && targets && stats && out && ws, "train_losses_win_fwd: null pointer");
+    TM_REQUIRE(w->W >= 0 && w->n_det >= 0 && w->n_edge >= 0 && w->n_det <= g->Dn && w->n_edge <= g->E,
+               "train_losses_win_fwd: W=%d n_det=%d n_edge=%d against Dn=%d E=%d", w->W, w->n_det, w->n_edge, g->Dn, g->E);
+    TM_REQUIRE(w->W == 0 || (w->det_ptr && w->edge_ptr), "train_losses_win_fwd: window pointers are null");
+    TM_REQUIRE((w->n_det == 0 || w->det_idx) && (w->n_edge == 0 || w->edge_idx), "train_losses_win_fwd: window lists are null");
+    if (ws_floats < tmpnn_train_losses_win_ws(w)) return set_error(TMPNN_EWORKSPACE, "train_losses_win_fwd: workspace too small");
+    if (w->W == 0) return TMPNN_OK;
+    hipLaunchKernelGGL(k_train_losses_win_fwd, dim3(w->W), dim3(TLW_THREADS), 0, as_stream(stream), *g, *w, logits, scores, labels,
+                       tp_classifier ? 1 : 0, targets, stats, out, ws);
+    return check_launch("train_losses_win_fwd");
+}
+
+int tmpnn_train_losses_win_bwd(const tmpnn_graph* g, const tmpnn_loss_windows* w, const int32_t* src_pos, const int32_t* dst_pos,
+                               const float* logits, const float* scores, const uint8_t* targets, const float* stats,
+                               const float* d_c, const float* d_f, int tp_classifier, float* d_logits, float* d_scores,
+                               tmpnn_stream stream) {
+    TM_REQUIRE(g && w && logits && scores && targets && stats, "train_losses_win_bwd: null pointer");
+    TM_REQUIRE((d_logits == nullptr || d_c) && (d_scores == nullptr || d_f), "train_losses_win_bwd: a gradient without its seeds");
+    TM_REQUIRE(g->E == 0 || (src_pos && dst_pos && w->edge_win), "train_losses_win_bwd: edge endpoints / windows are required");
+    TM_REQUIRE(g->Dn == 0 || w->det_win, "train_losses_win_bwd: det windows are required");
+    TM_REQUIRE(w->W == 0 || (w->det_ptr && w->edge_ptr), "train_losses_win_bwd: window pointers are null");
+    if (g->N == 0 || (!d_logits && !d_scores)) return TMPNN_OK;
+    hipLaunchKernelGGL(k_train_losses_win_bwd, dim3(ceil_div(g->E + g->Dn, 256)), dim3(256), 0, as_stream(stream), *g, *w, src_pos,
+                       dst_pos, logits, scores, targets, stats, d_c, d_f, tp_classifier ? 1 : 0, d_logits, d_scores);
+    return check_launch("train_losses_win_bwd");
 }
 
 }  // extern "C"

@@ -589,7 +589,10 @@ class WindowBuilder:
     def __init__(self, y: np.ndarray):
         self.y = np.asarray(y, dtype=np.int64)
 
-    def calls(self) -> List[WindowCall]:
+    def calls(self, empty_calls: bool = False) -> List[WindowCall]:
+        """empty_calls=False: one call per non-empty timestep.  empty_calls=True: the calls train.py:88-107 makes -- the first call
+        plus one for EVERY timestep in range(t1 + 1, tN + 1); a timestep without detections is a call with no new rows (the
+        reference runs the model on the unchanged graph and adds that call's losses again)."""
         y = self.y
         times = np.unique(y[:, 0])
         if times.size < 2:
@@ -611,8 +614,12 @@ class WindowBuilder:
         # which det pairs have an edge (for the association rule): set of (src det id, dst det id)
         has_edge = set((int(a), int(b)) for a in ids0 for b in ids1)
         t_prev = t1
-        for t in times[2:]:
+        for t in (range(t1 + 1, int(times[-1]) + 1) if empty_calls else times[2:]):
             t = int(t)
+            if empty_calls and not (y[:, 0] == t).any():
+                e = np.zeros(0, np.int64)
+                out.append(WindowCall(0, np.zeros(0, bool), e, e.copy(), e.copy()))
+                continue
             trk = y[det_ids, 1]
             # y_pred[:, 2] update (utils/graph.py:229-245): a TP det is associated iff one of its
             # FUTURE edges leads to a det of the same track; FPs self-associate (stay inactive)

@@ -3,6 +3,9 @@
     train_chunk     reference/train.py:54-135   one tracking chunk: initialize_graph -> model -> targets + CE + focal
                                                 losses, then per timestep update_graph(mode='train') -> model -> losses
                                                 (hidden state carried, BPTT), ONE backward for the chunk
+    train_chunks    the same for B chunks at once: a prebuilt block-diagonal TrainBatch (train_batch.py), one forward per
+                    call of the batch, the losses of every chunk kept apart (one windowed loss launch per call), ONE
+                    backward for the B chunks
     infer_sequence  reference/infer.py:35-87    one sequence: per timestep update_graph(mode='test', greedy or Hungarian)
                                                 -> model -> decode_tracks (track finalisation + rolling-window deletion)
 
@@ -22,7 +25,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from .loss import CELoss, FocalLoss, train_losses
+from .loss import CELoss, FocalLoss, train_losses, train_losses_windows
 from .tracking import TrackGraph
 
 
@@ -93,6 +96,43 @@ def train_chunk(model, X: torch.Tensor, y: torch.Tensor, device='cuda:0', tp_cla
     loss.backward()
     st.stop('backward')
     return loss, ncalls, edge_iters
+
+
+def train_chunks(model, batch, Xs, tp_classifier: bool = True, stages: Optional[Dict[str, float]] = None):
+    """B chunks of train.py:54-135 up to and including loss.backward(), on a TrainBatch (trackmpnn_amd.train_batch.
+    build_train_batch: built once per set of chunks -- train-mode graphs depend on the labels only).  Xs: the chunks'
+    features in the order of the `ys` the batch was built from (TrainBatch.stacked_features).  Every call of the batch runs
+    through model.forward_graph with the state carried (reserve_rows set); after each call the windowed losses add every live
+    chunk's terms; one backward.  The optimizer is not stepped (train_chunk's contract).
+
+    Returns (loss, per_chunk [B, 2] (loss_c, loss_f of every chunk of the batch, detached), ncalls, edge_iters) where ncalls /
+    edge_iters are the sums over the chunks of what train_chunk returns.  Semantics:
+      * the gradient is the sum of the B chunks' gradients: one optimizer step per B chunks (at B = 1 exactly the reference's
+        schedule: one chunk per step);
+      * BatchNorm running statistics are updated once per (call, chunk with new rows) in call-major order, so after a batch
+        they differ from running the B chunks one after another, except at B = 1."""
+    from .functional import weight_cache
+    st = _Stages(stages)
+    st.start()
+    Xz = batch.stacked_features(Xs)
+    st.stop('features')
+    h = None
+    acc_c = acc_f = None
+    n = len(batch.plans)
+    with weight_cache():        # the weights do not change between the forward calls of one step
+        for c, plan in enumerate(batch.plans):
+            x = Xz.index_select(0, batch.feat_src[c])
+            nxt = batch.plans[c + 1].n_new if c + 1 < n else 0
+            scores, logits, h, _ = model.forward_graph(x, h, plan, reserve_rows=nxt)
+            st.stop('model_fwd')
+            lc, lf = train_losses_windows(scores, logits, batch.call_labels(c), plan, batch.windows[c], tp_classifier)
+            acc_c = lc if acc_c is None else acc_c + lc
+            acc_f = lf if acc_f is None else acc_f + lf
+            st.stop('targets_losses')
+    loss = acc_c.sum() + acc_f.sum()
+    loss.backward()
+    st.stop('backward')
+    return loss, torch.stack([acc_c.detach(), acc_f.detach()], 1), batch.ncalls, batch.edge_iters
 
 
 def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 5, ret_win_size: int = 0,

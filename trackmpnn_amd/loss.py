@@ -346,6 +346,67 @@ def train_losses(scores: torch.Tensor, logits: torch.Tensor, labels: torch.Tenso
     return _TrainLosses.apply(logits, sc, lab, g, bool(tp_classifier))
 
 
+
+class _TrainLossesWin(torch.autograd.Function):
+    """train.py:70-81 for one call of a block-diagonal training batch, every window kept apart: ONE autograd node, one launch
+    each way (csrc/loss.hip k_train_losses_win_fwd / _bwd).  Returns (loss_c [W], loss_f [W]); per window the values and
+    gradients of `_TrainLosses` on that window's own subgraph."""
+
+    @staticmethod
+    def forward(ctx, logits, scores, labels_u8, graph, windows, tp_classifier):
+        g: FrameGraph = graph
+        lib = _lib.load()
+        dev = logits.device
+        W = int(windows.W)
+        lg = logits.detach().reshape(-1).float().contiguous()
+        sc = scores.detach().reshape(-1).float().contiguous()
+        targets = torch.empty_like(labels_u8)
+        nd8 = max(g.Dn, 1) * 8
+        n_ws = int(lib.tmpnn_train_losses_win_ws(windows.cref()))
+        buf = torch.empty((nd8 + 4 * W + n_ws,), dtype=torch.float32, device=dev)
+        stats, out = buf[:nd8], buf[nd8:nd8 + 4 * W].view(4, W)
+        _lib.call('tmpnn_train_losses_win_fwd', g.cref(), windows.cref(), lg.data_ptr(), sc.data_ptr(), labels_u8.data_ptr(),
+                  1 if tp_classifier else 0, targets.data_ptr(), stats.data_ptr(), out.data_ptr(),
+                  buf.data_ptr() + 4 * (nd8 + 4 * W), n_ws, _stream())
+        ctx.g, ctx.w, ctx.lg, ctx.sc, ctx.targets, ctx.stats = g, windows, lg, sc, targets, stats
+        ctx.tp, ctx.shapes = bool(tp_classifier), (logits.shape, scores.shape)
+        return out[0], out[3]
+
+    @staticmethod
+    def backward(ctx, d_c, d_f):
+        g: FrameGraph = ctx.g
+        d_logits = d_scores = None
+        if d_c is not None:
+            d_logits = torch.empty_like(ctx.lg)
+            d_c = d_c.reshape(-1).float().contiguous()
+        if d_f is not None:
+            d_scores = torch.empty_like(ctx.sc)
+            d_f = d_f.reshape(-1).float().contiguous()
+        _lib.call('tmpnn_train_losses_win_bwd', g.cref(), ctx.w.cref(), _lib.ptr(g.src_pos), _lib.ptr(g.dst_pos),
+                  ctx.lg.data_ptr(), ctx.sc.data_ptr(), ctx.targets.data_ptr(), ctx.stats.data_ptr(), _lib.ptr(d_c),
+                  _lib.ptr(d_f), 1 if ctx.tp else 0, _lib.ptr(d_logits), _lib.ptr(d_scores), _stream())
+        return (None if d_logits is None else d_logits.reshape(ctx.shapes[0]),
+                None if d_scores is None else d_scores.reshape(ctx.shapes[1]), None, None, None, None)
+
+
+def train_losses_windows(scores: torch.Tensor, logits: torch.Tensor, labels_u8: torch.Tensor, plan, windows,
+                         tp_classifier: bool = True):
+    """(loss_c [W], loss_f [W]) of one call of a block-diagonal training batch (trackmpnn_amd.train_batch): for every window w
+    of `windows` (a LossWindows) what `train_losses` gives on that window's own subgraph -- CELoss summed over its det rows;
+    FocalLoss(gamma=0) as the mean over its edge rows, plus the mean over its det rows with the TP classifier.  A window with no
+    rows at this call gives 0 in both.  plan: the call's CallPlan (or its FrameGraph); labels_u8: uint8 [N] row labels."""
+    _need_cuda(scores, 'scores')
+    g = plan.graph if isinstance(plan, CallPlan) else plan
+    if not isinstance(g, FrameGraph) or g.src_pos is None or g.dst_pos is None:
+        raise ValueError('train_losses_windows: the call graph must be a FrameGraph with src_pos / dst_pos')
+    lab = labels_u8.reshape(-1)
+    lab = lab if (lab.dtype == torch.uint8 and lab.is_contiguous()) else (lab != 0).to(torch.uint8).contiguous()
+    if lab.numel() != g.N:
+        raise ValueError(f'train_losses_windows: {lab.numel()} labels for {g.N} rows')
+    sc = (scores.reshape(-1) if scores.shape[1] == 1 else scores[:, 0]) if scores.dim() == 2 else scores
+    return _TrainLossesWin.apply(logits, sc, lab, g, windows, bool(tp_classifier))
+
+
 _fast_state = {}
 
 
