@@ -35,10 +35,11 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 5 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 6 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
                                left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
-                               5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed) */
+                               5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed);
+                               6: + struct tmpnn_train_build, tmpnn_train_build_* (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -489,6 +490,58 @@ int tmpnn_train_losses_win_bwd(const tmpnn_graph* g, const tmpnn_loss_windows* w
                                const float* logits, const float* scores, const uint8_t* targets, const float* stats,
                                const float* d_c, const float* d_f, int tp_classifier, float* d_logits, float* d_scores,
                                tmpnn_stream stream);
+
+/* The training batch of trackmpnn_amd.train_batch.build_train_batch, built on the device (build_train_batch_device): the
+ * train-mode graphs of every call of a block-diagonal batch of chunks (utils/graph.py:96-186, 189-334 with mode='train').
+ * Input: chunk i is y[offsets[i] .. offsets[i+1]) of the stacked labels y [ND][2] = (timestep, track id); a value that was not
+ * an integer is passed as TMPNN_TB_NONINT.  Three steps, one workgroup per chunk, the chunk's dets and per-det state in LDS:
+ *   tmpnn_train_build_count: per input chunk, info[i][4] = {status (TMPNN_TB_* bits, 0 = valid), calls of the chunk (0 = the
+ *     reference skips it: fewer than two timesteps or every track id -1), t0, t1}.  The host reads info once.
+ *   tmpnn_train_build_calls: per kept chunk b and call c < ncalls_b, counts[cptr[b] + c] = {new edge rows, new det rows}.
+ *     The host forms the call-major offsets (blk, cb_tab, call_tab) from them and reads the per-call totals once.
+ *   tmpnn_train_build_fill phase 0: every index array except inc; rowptr holds {0, degree of every det} per call, which the
+ *     caller turns into offsets with an inclusive scan per call; phase 1: inc (needs those offsets).
+ * calls / fill check every kept chunk against max_dets, max_slots and C on the device: one that does not fit gets nothing
+ * written and TMPNN_TB_ST_LDS in info[i][0], which the caller reads with the per-call totals.
+ * Placement comes from the offsets: no atomics in global memory, the output is deterministic.  Limits per chunk: at most
+ * TMPNN_TB_MAX_DETS detections and TMPNN_TB_MAX_CALLS calls (1 + tN - t1); rows and edges of the batch fit in int32. */
+#define TMPNN_TB_MAX_DETS 4096
+#define TMPNN_TB_MAX_CALLS 1024
+#define TMPNN_TB_NONINT INT64_MIN          /* marks a non-integral label value */
+#define TMPNN_TB_ST_NONINT 1               /* status bits of tmpnn_train_build_count */
+#define TMPNN_TB_ST_NEGTS 2
+#define TMPNN_TB_ST_RANGE 4
+#define TMPNN_TB_ST_DETS 8
+#define TMPNN_TB_ST_CALLS 16
+#define TMPNN_TB_ST_OFFSETS 32
+#define TMPNN_TB_ST_LDS 64                 /* set by calls / fill: the chunk exceeds max_dets, max_slots or C (nothing written) */
+typedef struct tmpnn_train_build {
+    int32_t n;                  /* input chunks */
+    int32_t B;                  /* kept chunks (calls / fill) */
+    int32_t C;                  /* calls of the batch = max ncalls_b (fill) */
+    int32_t max_dets;           /* a power of two >= every kept chunk's detections (calls / fill: sizes the LDS) */
+    int32_t max_slots;          /* >= 2 + every kept chunk's calls */
+    int64_t n_feat;             /* rows of y (= offsets[n]; count: offsets beyond it are invalid; fill: feat_src of edge rows) */
+    const int64_t* y;           /* [ND][2] */
+    const int64_t* offsets;     /* [n + 1] */
+    int64_t* info;              /* [n][4] count output */
+    const int32_t* kept;        /* [B] input chunk of batch chunk b */
+    const int32_t* cptr;        /* [B + 1] first entry of chunk b in the per-(chunk, call) tables */
+    int32_t* counts;            /* [cptr[B]][2] calls output */
+    const int32_t* blk;         /* [cptr[B]][4] block (b, c): first row, edge, det of the call-major layout, segment in call c */
+    const int64_t* call_tab;    /* [7][C] rows before call c; first element of call c in rowptr, inc, det_order / det_win,
+                                   edge_win, det_idx, edge_idx */
+    const int32_t* cb_tab;      /* [3][C][B] first element of chunk b in call c's det_order, det_idx, edge_idx */
+    /* prefix-stable outputs, sized for the last call */
+    int32_t* src; int32_t* dst; int32_t* edge_row; int32_t* src_pos; int32_t* dst_pos;     /* [E] */
+    int32_t* det_row; int32_t* seg_of_det; int64_t* new_det_local; int64_t* det_group;     /* [Dn] */
+    uint8_t* is_edge; int32_t* pos; uint8_t* labels; int64_t* feat_src; int64_t* seg_of_new;   /* [N] */
+    /* per call, concatenated */
+    int32_t* rowptr; int32_t* inc; int32_t* det_order; int32_t* det_win; int32_t* edge_win; int32_t* det_idx; int32_t* edge_idx;
+} tmpnn_train_build;
+int tmpnn_train_build_count(const tmpnn_train_build* d, tmpnn_stream stream);
+int tmpnn_train_build_calls(const tmpnn_train_build* d, tmpnn_stream stream);
+int tmpnn_train_build_fill(const tmpnn_train_build* d, int phase, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Batch-1 path (the reference's real call pattern, train.py:92-107 / infer.py:60-87: ONE small

@@ -9,8 +9,9 @@ from .loss import CELoss, FocalLoss, create_targets, train_losses_windows
 from .loops import train_chunk, train_chunks
 from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
-from .train_batch import LossWindows, TrainBatch, build_train_batch
+from .train_batch import LossWindows, TrainBatch, build_train_batch, build_train_batch_device
 
 __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'create_targets', 'CELoss', 'FocalLoss', 'FrameGraph', 'CallPlan', 'graph_from_adjacency', 'graph_from_edges',
            'plan_single', 'DeviceGraph', 'device_graph_from_adjacency', 'WindowBuilder', 'batch_windows', 'synth_window', 'dense_static_graph', 'concat_static_graphs',
-           'train_losses_windows', 'train_chunk', 'train_chunks', 'TrainBatch', 'LossWindows', 'build_train_batch']
+           'train_losses_windows', 'train_chunk', 'train_chunks', 'TrainBatch', 'LossWindows', 'build_train_batch',
+           'build_train_batch_device']

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -89,10 +89,21 @@ class CLossWindows(C.Structure):
                 ('edge_ptr', c_void_p), ('edge_idx', c_void_p), ('det_win', c_void_p), ('edge_win', c_void_p)]
 
 
+class CTrainBuild(C.Structure):
+    """struct tmpnn_train_build (include/tmpnn.h): the device build of a training batch."""
+    _fields_ = [('n', C.c_int32), ('B', C.c_int32), ('C', C.c_int32), ('max_dets', C.c_int32), ('max_slots', C.c_int32),
+                ('n_feat', C.c_int64)] + [(f, c_void_p) for f in (
+                    'y', 'offsets', 'info', 'kept', 'cptr', 'counts', 'blk', 'call_tab', 'cb_tab',
+                    'src', 'dst', 'edge_row', 'src_pos', 'dst_pos', 'det_row', 'seg_of_det', 'new_det_local', 'det_group',
+                    'is_edge', 'pos', 'labels', 'feat_src', 'seg_of_new',
+                    'rowptr', 'inc', 'det_order', 'det_win', 'edge_win', 'det_idx', 'edge_idx')]
+
+
 _DGP = C.POINTER(CDGraph)
 _MPP = C.POINTER(CMpParams)
 _TRP = C.POINTER(CTrackRows)
 _LWP = C.POINTER(CLossWindows)
+_TBP = C.POINTER(CTrainBuild)
 
 # name -> (restype, argtypes); must mirror include/tmpnn.h (tests/test_abi.py cross-checks the names)
 _SIGNATURES = {
@@ -197,6 +208,9 @@ _SIGNATURES = {
                                            c_void_p, c_size_t, c_void_p]),
     'tmpnn_train_losses_win_bwd': (c_int, [_GP, _LWP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'tmpnn_train_build_count': (c_int, [_TBP, c_void_p]),
+    'tmpnn_train_build_calls': (c_int, [_TBP, c_void_p]),
+    'tmpnn_train_build_fill': (c_int, [_TBP, c_int, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

@@ -22,6 +22,7 @@
 // HBM/latency bound, graphs of <= TMPNN_TRACK_MAX_ROWS rows: single-workgroup kernels with LDS scans.
 #include <algorithm>
 
+#include "block_scan.h"
 #include "common.h"
 #include "graphconv_dev.h"
 #include "small_bn_dev.h"
@@ -30,27 +31,7 @@ namespace tmpnn {
 
 static constexpr int TK_THREADS = 1024;
 
-__device__ __forceinline__ int tk_block_scan(int v, int* s_wave, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int w = 0; w < TK_THREADS / 64; ++w) { const int t = s_wave[w]; s_wave[w] = run; run += t; }
-        s_wave[TK_THREADS / 64] = run;
-    }
-    __syncthreads();
-    const int res = s_wave[wave] + inc - v;
-    *total = s_wave[TK_THREADS / 64];
-    __syncthreads();
-    return res;
-}
+__device__ __forceinline__ int tk_block_scan(int v, int* s_wave, int* total) { return block_scan<TK_THREADS>(v, s_wave, total); }
 
 // ---- y_pred[:, 2] by optimal assignment (reference hungarian(), utils/graph.py:33-93; README: --hungarian) -----------------
 // Swept in ascending timestep t over the timesteps that edges lead into.  Rows of the problem: the dets with an edge into t
