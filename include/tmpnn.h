@@ -35,11 +35,13 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 6 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 7 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
                                left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
                                5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed);
-                               6: + struct tmpnn_train_build, tmpnn_train_build_* (entry points added, none changed) */
+                               6: + struct tmpnn_train_build, tmpnn_train_build_* (entry points added, none changed);
+                               7: + tmpnn_cls_counts, tmpnn_cls_counts_win, struct tmpnn_train_record, tmpnn_train_record_fold
+                                  (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -490,6 +492,34 @@ int tmpnn_train_losses_win_bwd(const tmpnn_graph* g, const tmpnn_loss_windows* w
                                const float* logits, const float* scores, const uint8_t* targets, const float* stats,
                                const float* d_c, const float* d_f, int tp_classifier, float* d_logits, float* d_scores,
                                tmpnn_stream stream);
+
+/* The training monitor (train.py:86-88, :125-127, :157-171): classification counts per forward call and the running statistics of
+ * an epoch, on the device.  pred = score > 0.5f (strict: argmax((1 - s, s)) with the tie going to class 0); targets: the bytes the
+ * loss forward wrote.  The counted rows S are the det and the edge rows of the graph (window) with the TP classifier, its edge
+ * rows alone without.  A counts record is four int32: tp = #{pred and t}, fp = #{pred and not t}, fn = #{not pred and t} over S,
+ * and rows = det rows + edge rows of the graph (window) in either mode; rows > 0 is what makes a (call, window) pair a forward.
+ * Integer counts (ballot + popcount per wave, the waves combined in a fixed order), no atomics: exact and repeatable.
+ *   tmpnn_cls_counts: one graph, counts [4].
+ *   tmpnn_cls_counts_win: every window of one call of a block-diagonal batch, over the det_idx / edge_idx lists the windowed
+ *     loss walks (no row limit per window); counts [4][W], a window with no rows gets zeros.
+ *   tmpnn_train_record_fold: ONE launch that adds a step to the record: for every pair of counts [C][4][W] with rows > 0 its
+ *     F1 = 2 tp / (2 tp + fp + fn) in fp64 (0 when the denominator is 0: zero_division=0) and one forward; for every chunk
+ *     b < B its loss_c[b], loss_f[b] and float(loss_c[b] + loss_f[b]) (fp32 values, summed in fp64) and one chunk.  The sums
+ *     are taken in a fixed order.  The record is device memory the caller zeroes (an epoch boundary) and reads. */
+typedef struct tmpnn_train_record {
+    double sum_f1;       /* over the forwards */
+    int64_t forwards;
+    double sum_loss_c;   /* over the chunks */
+    double sum_loss_f;
+    double sum_loss;     /* of float(loss_c + loss_f) */
+    int64_t chunks;
+} tmpnn_train_record;
+int tmpnn_cls_counts(const tmpnn_graph* g, const float* scores, const uint8_t* targets, int tp_classifier, int32_t* counts,
+                     tmpnn_stream stream);
+int tmpnn_cls_counts_win(const tmpnn_graph* g, const tmpnn_loss_windows* w, const float* scores, const uint8_t* targets,
+                         int tp_classifier, int32_t* counts, tmpnn_stream stream);
+int tmpnn_train_record_fold(const int32_t* counts, int C, int W, const float* loss_c, const float* loss_f, int B,
+                            tmpnn_train_record* rec, tmpnn_stream stream);
 
 /* The training batch of trackmpnn_amd.train_batch.build_train_batch, built on the device (build_train_batch_device): the
  * train-mode graphs of every call of a block-diagonal batch of chunks (utils/graph.py:96-186, 189-334 with mode='train').

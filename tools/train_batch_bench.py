@@ -4,6 +4,10 @@ windows, 64 distinct seeds tiled).
     (a) bench.step: every call of the batch, BCE with logits over all logits against fixed targets, one backward, Adam
     (b) trackmpnn_amd.loops.train_chunks + Adam: the same calls with create_targets + CELoss + FocalLoss per chunk and call
         (one windowed loss launch per call each way), one backward -- the losses inside the timed region
+    (b') (b) with a TrainMonitor (trackmpnn_amd.monitor): one counting launch per call and one fold per step more, no host read.
+        (b) and (b') are timed in the same process, alternating step by step, so both see the same clocks and allocator state;
+        R = sum over the calls of (listed det rows + listed edge rows) is what the counting launches read.  Also one C2 chunk
+        through train_chunk (batch 1, where a launch per call shows) with and without a monitor, alternating likewise
     (c) the host build of (b)'s batch (build_train_batch: graphs, labels, loss windows, feature sources; once per set of chunks)
     (d) the device build of the same batch (build_train_batch_device) from one stacked [ND, 2] device tensor + offsets, and
         separately from the list of per-chunk host arrays
@@ -43,6 +47,22 @@ def timed(fn, steps, warmup):
     return np.asarray(ms)
 
 
+def timed_pair(fn_a, fn_b, steps, warmup):
+    """fn_a and fn_b alternating step by step, each step timed on its own."""
+    for _ in range(warmup):
+        fn_a()
+        fn_b()
+    torch.cuda.synchronize()
+    ms = ([], [])
+    for _ in range(steps):
+        for k, fn in enumerate((fn_a, fn_b)):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    return np.asarray(ms[0]), np.asarray(ms[1])
+
+
 def summary(ms, edges):
     med = float(np.median(ms))
     return dict(ms_median=round(med, 3), ms_min=round(float(ms.min()), 3), ms_max=round(float(ms.max()), 3),
@@ -59,8 +79,8 @@ def main():
     ap.add_argument('--skip-host-build', action='store_true', help='(c) is not run: (b) trains the device-built batch')
     args = ap.parse_args()
     import bench
-    from trackmpnn_amd import TrackMPNN, build_train_batch, build_train_batch_device, synth_window
-    from trackmpnn_amd.loops import train_chunks
+    from trackmpnn_amd import TrackMPNN, TrainMonitor, build_train_batch, build_train_batch_device, synth_window
+    from trackmpnn_amd.loops import train_chunk, train_chunks
     dev = torch.device('cuda', 0)
     w = bench.WORKLOADS['c2']
     B = int(args.windows or w['windows'])
@@ -102,8 +122,27 @@ def main():
         out['r'] = train_chunks(model, batch, Xs, tp)
         opt.step()
 
-    ms_b = timed(step_b, args.steps, args.warmup)
+    mon = TrainMonitor(dev)
+
+    def step_bm():
+        opt.zero_grad(set_to_none=False)
+        train_chunks(model, batch, Xs, tp, monitor=mon)
+        opt.step()
+
+    ms_b, ms_bm = timed_pair(step_b, step_bm, args.steps, args.warmup)
     loss, per_chunk, ncalls, edges_b = out['r']
+    stats = mon.read()
+    listed_rows = int(sum(w.n_det + w.n_edge for w in batch.windows))
+    # batch 1: one C2 chunk through train_chunk, with and without a monitor
+    y1 = torch.from_numpy(ys[0])[None]
+    X1 = Xs[:ys[0].shape[0]][None].cpu()
+    mon1 = TrainMonitor(dev)
+
+    def chunk(m):
+        opt.zero_grad(set_to_none=False)
+        train_chunk(model, X1, y1, dev, tp, monitor=m)
+
+    ms_c, ms_cm = timed_pair(lambda: chunk(None), lambda: chunk(mon1), max(args.steps, 20), max(args.warmup, 5))
     # (e): fresh batches -- K transformed label sets drawn up front (device-resident, as a collate hands them over)
     rng = np.random.RandomState(7)
 
@@ -150,10 +189,21 @@ def main():
     for _ in range(len(sets)):
         step_e(record=True)
     a, b = summary(ms_a, edges_a), summary(ms_b, edges_b)
+    bm = summary(ms_bm, edges_b)
+    rng_b = round(float(ms_b.max() - ms_b.min()), 3)
+    delta = round(bm['ms_median'] - b['ms_median'], 3)
+    med = lambda v: round(float(np.median(v)), 4)
     print(json.dumps(dict(
         workload=f"C2: {B} windows (64 distinct seeds tiled), {w['frames']} frames, H={w['H']}, K=0, diff",
         steps=args.steps, warmup=args.warmup, tp_classifier=tp,
         a_headline_bce_step=a, b_train_chunks_real_losses_step=b,
+        b_prime_with_monitor_step=bm | dict(
+            listed_rows_R=listed_rows, counted_bytes_9R=9 * listed_rows, delta_median_ms=delta, range_of_b_ms=rng_b,
+            verdict='not resolvable, <= range of (b)' if abs(delta) <= rng_b else 'outside the range of (b)',
+            monitor={k: (round(v, 6) if isinstance(v, float) else v) for k, v in stats.items()}),
+        train_chunk_c2_ms=dict(plain_median=med(ms_c), plain_min=round(float(ms_c.min()), 4), plain_max=round(float(ms_c.max()), 4),
+                               monitor_median=med(ms_cm), monitor_min=round(float(ms_cm.min()), 4),
+                               monitor_max=round(float(ms_cm.max()), 4)),
         c_host_build_s=None if build_s is None else round(build_s, 3),
         d_device_build_ms=summary(ms_d, 0) | dict(list_form_ms_median=round(float(np.median(ms_d_list)), 3)),
         e_fresh_batch_step=summary(ms_e, edges_b) | dict(draws=len(sets), split_ms_median={

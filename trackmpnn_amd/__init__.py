@@ -5,8 +5,10 @@
 from .graph import (CallPlan, DeviceGraph, FrameGraph, device_graph_from_adjacency, WindowBuilder, batch_windows, concat_static_graphs, dense_static_graph,
                     graph_from_adjacency, graph_from_edges, plan_single, synth_window)
 from .capture import CapturedWindow
-from .loss import CELoss, FocalLoss, create_targets, train_losses_windows
+from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
+                   train_losses_windows)
 from .loops import train_chunk, train_chunks
+from .monitor import TrainMonitor
 from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
 from .train_batch import LossWindows, TrainBatch, build_train_batch, build_train_batch_device
@@ -14,4 +16,4 @@ from .train_batch import LossWindows, TrainBatch, build_train_batch, build_train
 __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'create_targets', 'CELoss', 'FocalLoss', 'FrameGraph', 'CallPlan', 'graph_from_adjacency', 'graph_from_edges',
            'plan_single', 'DeviceGraph', 'device_graph_from_adjacency', 'WindowBuilder', 'batch_windows', 'synth_window', 'dense_static_graph', 'concat_static_graphs',
            'train_losses_windows', 'train_chunk', 'train_chunks', 'TrainBatch', 'LossWindows', 'build_train_batch',
-           'build_train_batch_device']
+           'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor']

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -208,6 +208,9 @@ _SIGNATURES = {
                                            c_void_p, c_size_t, c_void_p]),
     'tmpnn_train_losses_win_bwd': (c_int, [_GP, _LWP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'tmpnn_cls_counts': (c_int, [_GP, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'tmpnn_cls_counts_win': (c_int, [_GP, _LWP, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'tmpnn_train_record_fold': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'tmpnn_train_build_count': (c_int, [_TBP, c_void_p]),
     'tmpnn_train_build_calls': (c_int, [_TBP, c_void_p]),
     'tmpnn_train_build_fill': (c_int, [_TBP, c_int, c_void_p]),

@@ -12,7 +12,9 @@
 Same order of operations, same arguments' meaning and the same results as the reference's drivers (which cannot be imported:
 they parse the command line at import) -- but the graph, the hidden state, the losses' inputs and the tracks stay
 in HBM: `TrackGraph` (tracking.py), the batch-1 model path (`TrackMPNN.forward_dgraph`) and the HIP losses (loss.py).  The
-drivers' logging (F1 per forward, prints) is not part of the loop here or in the timings it is compared with.
+drivers' prints are not part of the loop here or in the timings it is compared with; their training statistics (F1 per
+forward, the epoch's loss means: train.py:86-88, :157-171) are kept on the device when `train_chunk` / `train_chunks` are
+given a `TrainMonitor` (monitor.py) -- counts after every forward, one fold per chunk / per step, no host read in the loop.
 
 `stages`, when given, is a dict that accumulates wall time per stage with a device synchronisation around each stage
 (an instrumented pass: its total is larger than an un-instrumented one).
@@ -47,18 +49,22 @@ class _Stages:
             self.t = now
 
 
-def _loss_terms(tg: TrackGraph, scores, logits, ce, focal_node, focal_edge, tp_classifier: bool):
+def _loss_terms(tg: TrackGraph, scores, logits, ce, focal_node, focal_edge, tp_classifier: bool, return_targets: bool = False):
     """train.py:70-81 / :109-120 for one forward call."""
     # one autograd node for targets + CE + the focal terms (trackmpnn_amd.loss.train_losses: the same C entry points as the
     # CELoss / FocalLoss modules `ce`, `focal_node`, `focal_edge` -- train.py's gamma = 0, alpha = None -- would call one by one)
     # (the DeviceGraph itself: the one-launch losses take its arrays through the C struct, no tensor views)
+    if return_targets:
+        return train_losses(scores, logits, tg.labels_u8(), tg.graph, tp_classifier, return_targets=True)
     return train_losses(scores, logits, tg.labels_u8(), tg.graph, tp_classifier)
 
 
 def train_chunk(model, X: torch.Tensor, y: torch.Tensor, device='cuda:0', tp_classifier: bool = True,
-                stages: Optional[Dict[str, float]] = None):
+                stages: Optional[Dict[str, float]] = None, monitor=None):
     """One chunk of train.py:54-135 up to and including loss.backward().  X [1, ND, F], y [1, ND, 2] (host or device).
-    Returns (loss, number of forward calls, sum of E over them) or None where the reference skips the chunk."""
+    Returns (loss, number of forward calls, sum of E over them) or None where the reference skips the chunk.
+    monitor: a TrainMonitor (monitor.py) that takes the counts of every forward call and, after the backward, the chunk's
+    loss_c / loss_f (train.py:86-88, :125-133); return values, loss and gradients are the ones without it."""
     st = _Stages(stages)
     ce, focal_node, focal_edge = CELoss(), FocalLoss(gamma=0, alpha=None), FocalLoss(gamma=0, alpha=None)
     st.start()
@@ -69,7 +75,12 @@ def train_chunk(model, X: torch.Tensor, y: torch.Tensor, device='cuda:0', tp_cla
     st.stop('graph')
     scores, logits, h, _ = model.forward_dgraph(feats, None, tg.graph)
     st.stop('model_fwd')
-    loss_c, loss_f = _loss_terms(tg, scores, logits, ce, focal_node, focal_edge, tp_classifier)
+    if monitor is None:
+        loss_c, loss_f = _loss_terms(tg, scores, logits, ce, focal_node, focal_edge, tp_classifier)
+    else:
+        counts = monitor.new_counts(1 + t_end - t_st, 1, zero=True)      # (one forward per timestep at the most)
+        loss_c, loss_f, targets = _loss_terms(tg, scores, logits, ce, focal_node, focal_edge, tp_classifier, True)
+        monitor.count(counts, 0, scores, targets, tg.graph, tp_classifier)
     st.stop('targets_losses')
     ncalls, edge_iters = 1, tg.E
     t_skip = t_st
@@ -87,7 +98,11 @@ def train_chunk(model, X: torch.Tensor, y: torch.Tensor, device='cuda:0', tp_cla
         st.stop('graph')
         scores, logits, h, _ = model.forward_dgraph(feats, h, tg.graph)
         st.stop('model_fwd')
-        lc, lf = _loss_terms(tg, scores, logits, ce, focal_node, focal_edge, tp_classifier)
+        if monitor is None:
+            lc, lf = _loss_terms(tg, scores, logits, ce, focal_node, focal_edge, tp_classifier)
+        else:
+            lc, lf, targets = _loss_terms(tg, scores, logits, ce, focal_node, focal_edge, tp_classifier, True)
+            monitor.count(counts, ncalls, scores, targets, tg.graph, tp_classifier)
         loss_c, loss_f = loss_c + lc, loss_f + lf
         st.stop('targets_losses')
         ncalls += 1
@@ -95,10 +110,12 @@ def train_chunk(model, X: torch.Tensor, y: torch.Tensor, device='cuda:0', tp_cla
     loss = loss_c + loss_f
     loss.backward()
     st.stop('backward')
+    if monitor is not None:
+        monitor.fold(counts, loss_c, loss_f)
     return loss, ncalls, edge_iters
 
 
-def train_chunks(model, batch, Xs, tp_classifier: bool = True, stages: Optional[Dict[str, float]] = None):
+def train_chunks(model, batch, Xs, tp_classifier: bool = True, stages: Optional[Dict[str, float]] = None, monitor=None):
     """B chunks of train.py:54-135 up to and including loss.backward(), on a TrainBatch (trackmpnn_amd.train_batch.
     build_train_batch: built once per set of chunks -- train-mode graphs depend on the labels only).  Xs: the chunks'
     features in the order of the `ys` the batch was built from (TrainBatch.stacked_features).  Every call of the batch runs
@@ -110,7 +127,10 @@ def train_chunks(model, batch, Xs, tp_classifier: bool = True, stages: Optional[
       * the gradient is the sum of the B chunks' gradients: one optimizer step per B chunks (at B = 1 exactly the reference's
         schedule: one chunk per step);
       * BatchNorm running statistics are updated once per (call, chunk with new rows) in call-major order, so after a batch
-        they differ from running the B chunks one after another, except at B = 1."""
+        they differ from running the B chunks one after another, except at B = 1.
+    monitor: a TrainMonitor (monitor.py): one counting launch per call over the targets the windowed loss wrote, one fold per
+    step (every (call, chunk) pair with rows is a forward; per_chunk's terms are the chunks' losses), `monitor.last_counts` =
+    the step's counts [calls, 4, B].  No host read; loss, per_chunk and the gradients are the ones without it."""
     from .functional import weight_cache
     st = _Stages(stages)
     st.start()
@@ -119,19 +139,28 @@ def train_chunks(model, batch, Xs, tp_classifier: bool = True, stages: Optional[
     h = None
     acc_c = acc_f = None
     n = len(batch.plans)
+    counts = None if monitor is None else monitor.new_counts(n, batch.B, zero=False)
     with weight_cache():        # the weights do not change between the forward calls of one step
         for c, plan in enumerate(batch.plans):
             x = Xz.index_select(0, batch.feat_src[c])
             nxt = batch.plans[c + 1].n_new if c + 1 < n else 0
             scores, logits, h, _ = model.forward_graph(x, h, plan, reserve_rows=nxt)
             st.stop('model_fwd')
-            lc, lf = train_losses_windows(scores, logits, batch.call_labels(c), plan, batch.windows[c], tp_classifier)
+            if monitor is None:
+                lc, lf = train_losses_windows(scores, logits, batch.call_labels(c), plan, batch.windows[c], tp_classifier)
+            else:
+                lc, lf, targets = train_losses_windows(scores, logits, batch.call_labels(c), plan, batch.windows[c],
+                                                       tp_classifier, return_targets=True)
+                monitor.count_windows(counts, c, scores, targets, plan, batch.windows[c], tp_classifier)
             acc_c = lc if acc_c is None else acc_c + lc
             acc_f = lf if acc_f is None else acc_f + lf
             st.stop('targets_losses')
     loss = acc_c.sum() + acc_f.sum()
     loss.backward()
     st.stop('backward')
+    if monitor is not None:
+        monitor.fold(counts, acc_c, acc_f)
+        monitor.last_counts = counts
     return loss, torch.stack([acc_c.detach(), acc_f.detach()], 1), batch.ncalls, batch.edge_iters
 
 

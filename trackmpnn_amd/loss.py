@@ -216,7 +216,7 @@ class _TrainLosses(torch.autograd.Function):
     separate calls bit for bit."""
 
     @staticmethod
-    def forward(ctx, logits, scores, labels_u8, graph, tp_classifier):
+    def forward(ctx, logits, scores, labels_u8, graph, tp_classifier, targets_out=None):
         g: FrameGraph = graph
         lib = _lib.load()
         dev = logits.device
@@ -224,7 +224,8 @@ class _TrainLosses(torch.autograd.Function):
         N, E, Dn = g.N, g.E, g.Dn
         lg = logits.detach().reshape(-1).float().contiguous()
         sc = scores.detach().reshape(-1).float().contiguous()
-        targets = torch.empty_like(labels_u8)
+        # (targets_out: the caller's buffer for the targets -- train_losses(..., return_targets=True))
+        targets = torch.empty_like(labels_u8) if targets_out is None else targets_out
         ctx.fused = bool(lib.tmpnn_train_losses_supported(E, Dn))
         if ctx.fused:
             # batch-1 windows: the whole section in ONE launch (csrc/loss.hip k_train_losses_fwd; same values bit for bit)
@@ -285,7 +286,7 @@ class _TrainLosses(torch.autograd.Function):
                       ctx.sc.data_ptr(), ctx.targets.data_ptr(), ctx.stats.data_ptr(), _lib.ptr(d_c), _lib.ptr(d_f),
                       1 if ctx.tp else 0, _lib.ptr(d_logits), _lib.ptr(d_scores), st)
             return (None if d_logits is None else d_logits.reshape(ctx.shapes[0]),
-                    None if d_scores is None else d_scores.reshape(ctx.shapes[1]), None, None, None)
+                    None if d_scores is None else d_scores.reshape(ctx.shapes[1]), None, None, None, None)
         if d_c is not None:
             d_logits = torch.zeros_like(ctx.lg)
             dl = d_c.reshape(1).float().contiguous()
@@ -302,7 +303,7 @@ class _TrainLosses(torch.autograd.Function):
                 _lib.call('tmpnn_focal_loss_bwd', g.det_row.data_ptr(), g.Dn, ctx.sc.data_ptr(), ctx.targets.data_ptr(), 0.0,
                           0, 1.0, 1.0, df.data_ptr(), 1.0 / g.Dn, d_scores.data_ptr(), st)
             d_scores = d_scores.reshape(ctx.shapes[1])
-        return d_logits, d_scores, None, None, None
+        return d_logits, d_scores, None, None, None, None
 
 
 class _DGView:
@@ -321,9 +322,12 @@ class _DGView:
         return ctypes.byref(self._c)
 
 
-def train_losses(scores: torch.Tensor, logits: torch.Tensor, labels: torch.Tensor, node_adj, tp_classifier: bool = True):
+def train_losses(scores: torch.Tensor, logits: torch.Tensor, labels: torch.Tensor, node_adj, tp_classifier: bool = True,
+                 return_targets: bool = False):
     """(loss_c, loss_f) of one forward call as train.py:70-81 computes them (CELoss on the logits; FocalLoss(gamma=0) on the
-    scores of the edge rows, plus that of the det rows with the TP classifier) from the row labels."""
+    scores of the edge rows, plus that of the det rows with the TP classifier) from the row labels.
+    return_targets: a third value, the uint8 [N] targets the forward wrote (create_targets' bytes; not differentiable) -- what
+    `classification_counts` takes."""
     _need_cuda(scores, 'scores')
     if (isinstance(node_adj, DeviceGraph) and node_adj._meta is not None and node_adj._meta[2] == 0
             and _lib.load().tmpnn_train_losses_supported(node_adj._meta[0], node_adj._meta[1])):
@@ -334,6 +338,11 @@ def train_losses(scores: torch.Tensor, logits: torch.Tensor, labels: torch.Tenso
     lab = lab if (lab.dtype == torch.uint8 and lab.is_contiguous()) else (lab != 0).to(torch.uint8).contiguous()
     # ([N, 1] scores: a reshape is a view both ways; scores[:, 0] would cost a zero fill + a copy in the backward)
     sc = (scores.reshape(-1) if scores.shape[1] == 1 else scores[:, 0]) if scores.dim() == 2 else scores
+    if return_targets:
+        # (the Python node, also where the native one would serve: that one keeps the targets to itself)
+        targets = torch.empty_like(lab)
+        loss_c, loss_f = _TrainLosses.apply(logits, sc, lab, g, bool(tp_classifier), targets)
+        return loss_c, loss_f, targets
     if isinstance(g, _DGView):
         fast = _fast_losses()
         if fast is not None:
@@ -353,14 +362,14 @@ class _TrainLossesWin(torch.autograd.Function):
     gradients of `_TrainLosses` on that window's own subgraph."""
 
     @staticmethod
-    def forward(ctx, logits, scores, labels_u8, graph, windows, tp_classifier):
+    def forward(ctx, logits, scores, labels_u8, graph, windows, tp_classifier, targets_out=None):
         g: FrameGraph = graph
         lib = _lib.load()
         dev = logits.device
         W = int(windows.W)
         lg = logits.detach().reshape(-1).float().contiguous()
         sc = scores.detach().reshape(-1).float().contiguous()
-        targets = torch.empty_like(labels_u8)
+        targets = torch.empty_like(labels_u8) if targets_out is None else targets_out
         nd8 = max(g.Dn, 1) * 8
         n_ws = int(lib.tmpnn_train_losses_win_ws(windows.cref()))
         buf = torch.empty((nd8 + 4 * W + n_ws,), dtype=torch.float32, device=dev)
@@ -386,15 +395,17 @@ class _TrainLossesWin(torch.autograd.Function):
                   ctx.lg.data_ptr(), ctx.sc.data_ptr(), ctx.targets.data_ptr(), ctx.stats.data_ptr(), _lib.ptr(d_c),
                   _lib.ptr(d_f), 1 if ctx.tp else 0, _lib.ptr(d_logits), _lib.ptr(d_scores), _stream())
         return (None if d_logits is None else d_logits.reshape(ctx.shapes[0]),
-                None if d_scores is None else d_scores.reshape(ctx.shapes[1]), None, None, None, None)
+                None if d_scores is None else d_scores.reshape(ctx.shapes[1]), None, None, None, None, None)
 
 
 def train_losses_windows(scores: torch.Tensor, logits: torch.Tensor, labels_u8: torch.Tensor, plan, windows,
-                         tp_classifier: bool = True):
+                         tp_classifier: bool = True, return_targets: bool = False):
     """(loss_c [W], loss_f [W]) of one call of a block-diagonal training batch (trackmpnn_amd.train_batch): for every window w
     of `windows` (a LossWindows) what `train_losses` gives on that window's own subgraph -- CELoss summed over its det rows;
     FocalLoss(gamma=0) as the mean over its edge rows, plus the mean over its det rows with the TP classifier.  A window with no
-    rows at this call gives 0 in both.  plan: the call's CallPlan (or its FrameGraph); labels_u8: uint8 [N] row labels."""
+    rows at this call gives 0 in both.  plan: the call's CallPlan (or its FrameGraph); labels_u8: uint8 [N] row labels.
+    return_targets: a third value, the uint8 [N] targets the forward wrote -- defined on the rows the windows list (the other
+    rows hold nothing meaningful); not differentiable; what `classification_counts_windows` takes."""
     _need_cuda(scores, 'scores')
     g = plan.graph if isinstance(plan, CallPlan) else plan
     if not isinstance(g, FrameGraph) or g.src_pos is None or g.dst_pos is None:
@@ -404,7 +415,57 @@ def train_losses_windows(scores: torch.Tensor, logits: torch.Tensor, labels_u8: 
     if lab.numel() != g.N:
         raise ValueError(f'train_losses_windows: {lab.numel()} labels for {g.N} rows')
     sc = (scores.reshape(-1) if scores.shape[1] == 1 else scores[:, 0]) if scores.dim() == 2 else scores
+    if return_targets:
+        targets = torch.empty_like(lab)
+        loss_c, loss_f = _TrainLossesWin.apply(logits, sc, lab, g, windows, bool(tp_classifier), targets)
+        return loss_c, loss_f, targets
     return _TrainLossesWin.apply(logits, sc, lab, g, windows, bool(tp_classifier))
+
+
+def _flat_scores(scores: torch.Tensor) -> torch.Tensor:
+    s = scores.detach()
+    s = (s.reshape(-1) if s.shape[1] == 1 else s[:, 0]) if s.dim() == 2 else s
+    return s if (s.dtype == torch.float32 and s.is_contiguous()) else s.float().contiguous()
+
+
+def classification_counts(scores: torch.Tensor, targets: torch.Tensor, node_adj, tp_classifier: bool = True,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [4] on the device: tp, fp, fn of `pred = scores > 0.5` (= argmax((1 - s, s)), train.py:86) against `targets` over
+    the det and edge rows of the graph -- its edge rows alone without the TP classifier (train.py:79,85) -- and the number of
+    det + edge rows.  No host read.  scores [N, 1] or [N]; targets [N] (create_targets' values, or the bytes of
+    `train_losses(..., return_targets=True)`); node_adj as the losses take it.  out: an int32 [4] tensor to write instead."""
+    _need_cuda(scores, 'scores')
+    if isinstance(node_adj, DeviceGraph) and node_adj._meta is not None and node_adj._meta[2] == 0:
+        g = _DGView(node_adj)
+    else:
+        g = _as_graph(node_adj)
+    sc, t8 = _flat_scores(scores), _as_u8(targets)
+    if sc.numel() != g.N or t8.numel() != g.N:
+        raise ValueError(f'classification_counts: {sc.numel()} scores, {t8.numel()} targets for {g.N} rows')
+    if out is None:
+        out = torch.empty((4,), dtype=torch.int32, device=sc.device)
+    _lib.call('tmpnn_cls_counts', g.cref(), sc.data_ptr(), t8.data_ptr(), 1 if tp_classifier else 0, out.data_ptr(), _stream())
+    return out
+
+
+def classification_counts_windows(scores: torch.Tensor, targets: torch.Tensor, plan, windows, tp_classifier: bool = True,
+                                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [4, W] on the device: per window of `windows` (a LossWindows) of one call of a training batch the counts of
+    `classification_counts` over that window's rows; zeros for a window with no rows at this call.  No host read.
+    targets: what `train_losses_windows(..., return_targets=True)` returned for the call."""
+    _need_cuda(scores, 'scores')
+    g = plan.graph if isinstance(plan, CallPlan) else plan
+    if not isinstance(g, FrameGraph):
+        raise ValueError('classification_counts_windows: the call graph must be a FrameGraph')
+    sc, t8 = _flat_scores(scores), _as_u8(targets)
+    if sc.numel() != g.N or t8.numel() != g.N:
+        raise ValueError(f'classification_counts_windows: {sc.numel()} scores, {t8.numel()} targets for {g.N} rows')
+    W = int(windows.W)
+    if out is None:
+        out = torch.empty((4, W), dtype=torch.int32, device=sc.device)
+    _lib.call('tmpnn_cls_counts_win', g.cref(), windows.cref(), sc.data_ptr(), t8.data_ptr(), 1 if tp_classifier else 0,
+              out.data_ptr(), _stream())
+    return out
 
 
 _fast_state = {}
