@@ -35,13 +35,15 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 7 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 8 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
                                left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
                                5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed);
                                6: + struct tmpnn_train_build, tmpnn_train_build_* (entry points added, none changed);
                                7: + tmpnn_cls_counts, tmpnn_cls_counts_win, struct tmpnn_train_record, tmpnn_train_record_fold
-                                  (entry points added, none changed) */
+                                  (entry points added, none changed);
+                               8: + struct tmpnn_optim_seg, struct tmpnn_adam_state, tmpnn_optim_chunk, tmpnn_adam_step,
+                                  tmpnn_grad_flow (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -520,6 +522,42 @@ int tmpnn_cls_counts_win(const tmpnn_graph* g, const tmpnn_loss_windows* w, cons
                          int tp_classifier, int32_t* counts, tmpnn_stream stream);
 int tmpnn_train_record_fold(const int32_t* counts, int C, int W, const float* loss_c, const float* loss_f, int B,
                             tmpnn_train_record* rec, tmpnn_stream stream);
+
+/* The optimizer step (train.py:135 `optimizer_trk.step()` of the `optim.Adam(model.parameters(), lr, weight_decay)` of
+ * train.py:329; the learning rate is whatever the StepLR of train.py:330 last set) and the gradient statistics of
+ * --plot-gradients (utils/gradients.py:23: `p.grad.abs().mean()` per parameter), each in ONE launch over the flat gradient
+ * bucket (trackmpnn_amd.dist.GradBucket).
+ * A parameter keeps its own storage: segment s of the table says where it lives and which slice [start, start + count) of the
+ * three flat fp32 buffers (gradient, exp_avg, exp_avg_sq; n_flat elements each, 16-byte aligned) belongs to it.  The work list
+ * holds one (segment, offset inside the segment) int32 pair per chunk of tmpnn_optim_chunk() elements (offsets are multiples of
+ * it); both tables are device memory the caller builds once.  A pair or a segment that does not fit (segment >= P, a slice
+ * outside [0, n_flat), an offset outside the segment) is skipped by the kernel.
+ *   tmpnn_adam_step: with t = state->step + 1, per element (fp32, torch.optim.Adam's L2 weight decay, not AdamW):
+ *       g = fl(grad * grad_scale) + weight_decay * p;   m += (1 - beta1) (g - m);   v = beta2 v + (1 - beta2) g g;
+ *       p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps);        grad = 0 when zero_grads
+ *     lr and the step count are read from the device record, so a captured launch replays with the current values; the two
+ *     bias corrections are formed once per workgroup in fp64.  The same launch sets state->step = t: every workgroup reads the
+ *     record before it takes an integer ticket, and the last ticket moves the count and clears the ticket.  The product
+ *     grad * grad_scale is rounded to fp32 before the decay term is added, so grad_scale = 1 / world equals
+ *     `flat.mul_(1 / world)` followed by a step with grad_scale = 1, bit for bit.  No atomics on floats; repeatable bits.
+ *     beta1, beta2, eps, weight_decay, grad_scale and zero_grads are launch arguments (a captured launch keeps them).
+ *   tmpnn_grad_flow: stats [P][3] fp64 per segment = mean |g| (an fp64 sum in a fixed order over n), max |g| (NaN if any element
+ *     is NaN, as torch.max), the number of non-finite elements.  One workgroup per segment; repeatable bits. */
+typedef struct tmpnn_optim_seg {
+    float* p;       /* the parameter's own storage */
+    int64_t start;  /* first element of its slice of the flat buffers */
+    int64_t count;  /* elements */
+} tmpnn_optim_seg;
+typedef struct tmpnn_adam_state { /* 16 bytes of device memory, 16-byte aligned; zero `step` and `ticket` before the first step */
+    double lr;
+    float step;     /* steps taken so far (what torch keeps as state['step']); exact up to 2^24 */
+    int32_t ticket; /* 0 between launches */
+} tmpnn_adam_state;
+int tmpnn_optim_chunk(void);
+int tmpnn_adam_step(const tmpnn_optim_seg* segs, int P, const int32_t* work, int nwork, float* grad, float* exp_avg,
+                    float* exp_avg_sq, int64_t n_flat, tmpnn_adam_state* state, double beta1, double beta2, double eps,
+                    double weight_decay, float grad_scale, int zero_grads, tmpnn_stream stream);
+int tmpnn_grad_flow(const tmpnn_optim_seg* segs, int P, const float* grad, int64_t n_flat, double* stats, tmpnn_stream stream);
 
 /* The training batch of trackmpnn_amd.train_batch.build_train_batch, built on the device (build_train_batch_device): the
  * train-mode graphs of every call of a block-diagonal batch of chunks (utils/graph.py:96-186, 189-334 with mode='train').

@@ -9,6 +9,7 @@ from .loss import (CELoss, FocalLoss, classification_counts, classification_coun
                    train_losses_windows)
 from .loops import train_chunk, train_chunks
 from .monitor import TrainMonitor
+from .optim import BucketAdam
 from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
 from .train_batch import LossWindows, TrainBatch, build_train_batch, build_train_batch_device
@@ -16,4 +17,4 @@ from .train_batch import LossWindows, TrainBatch, build_train_batch, build_train
 __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'create_targets', 'CELoss', 'FocalLoss', 'FrameGraph', 'CallPlan', 'graph_from_adjacency', 'graph_from_edges',
            'plan_single', 'DeviceGraph', 'device_graph_from_adjacency', 'WindowBuilder', 'batch_windows', 'synth_window', 'dense_static_graph', 'concat_static_graphs',
            'train_losses_windows', 'train_chunk', 'train_chunks', 'TrainBatch', 'LossWindows', 'build_train_batch',
-           'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor']
+           'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor', 'BucketAdam']

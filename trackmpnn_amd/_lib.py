@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -211,6 +211,10 @@ _SIGNATURES = {
     'tmpnn_cls_counts': (c_int, [_GP, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'tmpnn_cls_counts_win': (c_int, [_GP, _LWP, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'tmpnn_train_record_fold': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'tmpnn_optim_chunk': (c_int, []),
+    'tmpnn_adam_step': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p,
+                                C.c_double, C.c_double, C.c_double, C.c_double, c_float, c_int, c_void_p]),
+    'tmpnn_grad_flow': (c_int, [c_void_p, c_int, c_void_p, C.c_int64, c_void_p, c_void_p]),
     'tmpnn_train_build_count': (c_int, [_TBP, c_void_p]),
     'tmpnn_train_build_calls': (c_int, [_TBP, c_void_p]),
     'tmpnn_train_build_fill': (c_int, [_TBP, c_int, c_void_p]),

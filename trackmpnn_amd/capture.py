@@ -22,8 +22,10 @@ class CapturedWindow:
     Models on the fused batch-1 path (nhidden <= 64: 32 / 64 natively, other widths zero-padded when they have no attention
     heads) are recorded through it; every other model (nhidden 128 ..., padded widths with heads) through the staged kernels
     on plans built before the capture.
-    loss_fn(outputs, h_last) -> scalar, with outputs = [(scores, logits)] per call.  `optimizer` (optional) must be
-    capturable (e.g. torch.optim.Adam(..., capturable=True)); parameter gradients must already exist (GradBucket or
+    loss_fn(outputs, h_last) -> scalar, with outputs = [(scores, logits)] per call.  `optimizer` (optional): a
+    `trackmpnn_amd.BucketAdam` (its learning rate and step count live on the device: a scheduler step between replays takes
+    effect, `replay` pushes it) or a capturable torch optimizer (e.g. torch.optim.Adam(..., capturable=True), whose learning
+    rate the capture freezes unless it is a device tensor); parameter gradients must already exist (GradBucket or
     zero_grad(set_to_none=False)), because their addresses are baked into the graph."""
 
     def __init__(self, model, calls: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]],
@@ -135,5 +137,8 @@ class CapturedWindow:
         if xs is not None:
             for dst, src in zip(self.static_x, xs):
                 dst.copy_(src, non_blocking=True)
+        push = getattr(self.optimizer, 'push_hyper', None)
+        if push is not None:
+            push()                                      # (BucketAdam: a learning rate the scheduler changed since the last replay)
         self.graph.replay()
         return self.loss

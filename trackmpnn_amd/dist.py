@@ -50,12 +50,14 @@ class GradBucket:
         return True
 
 
-def allreduce_grads(module: torch.nn.Module, bucket: GradBucket, world: int) -> None:
-    """Sum the gradient bucket over ranks and average it (one collective)."""
+def allreduce_grads(module: torch.nn.Module, bucket: GradBucket, world: int, average: bool = True) -> None:
+    """Sum the gradient bucket over ranks and average it (one collective).  average=False leaves the plain sum in the
+    bucket: `BucketAdam.step(grad_scale=1 / world)` folds the division into the optimizer's launch (same bits)."""
     if not bucket.check_alias():
         raise RuntimeError('parameter gradients no longer alias the bucket; use zero_grad(set_to_none=False)')
     dist.all_reduce(bucket.flat, op=dist.ReduceOp.SUM)
-    bucket.flat.mul_(1.0 / world)
+    if average:
+        bucket.flat.mul_(1.0 / world)
 
 
 def shard_windows(n_windows: int, rank: int, world: int, edge_counts: Optional[Sequence[int]] = None) -> List[int]:
