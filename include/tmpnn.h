@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 8 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 9 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
                                left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
                                5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed);
@@ -43,7 +43,9 @@ extern "C" {
                                7: + tmpnn_cls_counts, tmpnn_cls_counts_win, struct tmpnn_train_record, tmpnn_train_record_fold
                                   (entry points added, none changed);
                                8: + struct tmpnn_optim_seg, struct tmpnn_adam_state, tmpnn_optim_chunk, tmpnn_adam_step,
-                                  tmpnn_grad_flow (entry points added, none changed) */
+                                  tmpnn_grad_flow (entry points added, none changed);
+                               9: + struct tmpnn_chunk_draw, tmpnn_chunk_draw_count, tmpnn_chunk_draw_fill (entry points added,
+                                  none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -610,6 +612,65 @@ typedef struct tmpnn_train_build {
 int tmpnn_train_build_count(const tmpnn_train_build* d, tmpnn_stream stream);
 int tmpnn_train_build_calls(const tmpnn_train_build* d, tmpnn_stream stream);
 int tmpnn_train_build_fill(const tmpnn_train_build* d, int phase, tmpnn_stream stream);
+
+/* A seeded draw of B augmented training chunks from a device-resident detection store (trackmpnn_amd.chunks: DetectionStore,
+ * ChunkSampler.draw; the host definition is draw_chunks_host), written in the stacked form tmpnn_train_build_* take: the
+ * reference's --random-transforms (dataset/kitti_mot.py:494-532: time reversal, horizontal flip, per-detection dropout).
+ * The store keeps the detections sorted by (sequence, frame): the detections of frame f of sequence s are
+ * first[seq_base[s] + f] .. first[seq_base[s] + f + 1).  Per detection it holds the track id and the standardised static
+ * feature row of the plain box and of the flipped box (stat[det][0 / 1][Fs]); table[t mod fr_range][2] holds the standardised
+ * temporal pair.  So the device only selects and gathers: no feature arithmetic runs here.
+ * Chunk ci of the table is chunks[ci][4 + L] = {sequence, frames in its list, detections before dropout, 0, frame list (L
+ * entries, padded with -1)}; its rows before dropout are the detections of its frames in list order.  Drawn chunk b is chunk
+ * indices[b].  Decisions come from Philox4x32-10 with key = (seed low, seed high) and counter = (j, ci, step low, step high):
+ * block j = 0 gives reversal (word 0) and flip (word 1), word w of block j >= 1 decides row 4 (j - 1) + w of the chunk; with
+ * u = (word >> 8) * 2^-24 the event happens iff u < p.  A chunk's draw depends on (seed, step, ci) only, not on the batch.
+ * Time reversal: t' = last frame of the list - t + first frame of the list.
+ *   tmpnn_chunk_draw_count: count[b] = rows kept, flags[b], and offsets[B + 1] = the exclusive scan of count (two launches:
+ *     one workgroup per chunk, then one workgroup for the scan).
+ *   tmpnn_chunk_draw_fill: the same decisions again (nothing is stored between the two); kept row k of chunk b goes to row
+ *     offsets[b] + k: y = (t', track id), X = the static row of the plain or the flipped box, then table[t' mod fr_range] when
+ *     F = Fs + 2.  Rows of X and y from offsets[B] on are not written.
+ * A chunk that does not pass the device's own checks of the tables (an index, a sequence or a frame out of range, a size that
+ * is not the table's, more than TMPNN_TB_MAX_DETS rows) is drawn as an empty chunk with TMPNN_CD_FLAG_BAD set.  No atomics;
+ * the output is deterministic. */
+#define TMPNN_CD_MAX_FRAMES 256            /* frames of one chunk's list */
+#define TMPNN_CD_FLAG_REVERSED 1
+#define TMPNN_CD_FLAG_FLIPPED 2
+#define TMPNN_CD_FLAG_BAD 128
+typedef struct tmpnn_chunk_draw {
+    int32_t B;                  /* drawn chunks */
+    int32_t nchunks;            /* chunks of the table */
+    int32_t L;                  /* entries of a chunk's frame list, 1 .. TMPNN_CD_MAX_FRAMES */
+    int32_t nseq;               /* sequences of the store */
+    int32_t F;                  /* columns of X: Fs, or Fs + 2 with the temporal pair */
+    int32_t Fs;                 /* columns of the static row */
+    int32_t fr_range;           /* rows of table */
+    int32_t transforms;         /* 0: the plain chunks (no random numbers, flags 0) */
+    int64_t ndets;              /* detections of the store */
+    int64_t nframes;            /* frames of the store = seq_base[nseq] */
+    int64_t n_max;              /* rows of X and y: the sum of the drawn chunks' sizes before dropout, < 2^31 */
+    uint64_t seed;
+    uint64_t step;
+    float p_drop;
+    float p_reverse;
+    float p_flip;
+    float reserved;
+    const int32_t* indices;     /* [B] */
+    const int32_t* chunks;      /* [nchunks][4 + L] */
+    const int32_t* seq_base;    /* [nseq + 1] */
+    const int32_t* first;       /* [nframes + 1] */
+    const int32_t* track;       /* [ndets] */
+    const float* stat;          /* [ndets][2][Fs] */
+    const float* table;         /* [fr_range][2] (F = Fs + 2) */
+    int32_t* count;             /* [B] */
+    uint8_t* flags;             /* [B] */
+    int64_t* offsets;           /* [B + 1] */
+    float* X;                   /* [n_max][F] */
+    int64_t* y;                 /* [n_max][2], 16-byte aligned */
+} tmpnn_chunk_draw;
+int tmpnn_chunk_draw_count(const tmpnn_chunk_draw* d, tmpnn_stream stream);
+int tmpnn_chunk_draw_fill(const tmpnn_chunk_draw* d, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Batch-1 path (the reference's real call pattern, train.py:92-107 / infer.py:60-87: ONE small

@@ -5,16 +5,18 @@
 from .graph import (CallPlan, DeviceGraph, FrameGraph, device_graph_from_adjacency, WindowBuilder, batch_windows, concat_static_graphs, dense_static_graph,
                     graph_from_adjacency, graph_from_edges, plan_single, synth_window)
 from .capture import CapturedWindow
+from .chunks import ChunkSampler, DetectionStore, DrawnChunks, draw_chunks_host, make_chunks
 from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
                    train_losses_windows)
-from .loops import train_chunk, train_chunks
+from .loops import train_chunk, train_chunks, train_epoch
 from .monitor import TrainMonitor
 from .optim import BucketAdam
 from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
-from .train_batch import LossWindows, TrainBatch, build_train_batch, build_train_batch_device
+from .train_batch import AllChunksSkipped, LossWindows, TrainBatch, build_train_batch, build_train_batch_device
 
 __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'create_targets', 'CELoss', 'FocalLoss', 'FrameGraph', 'CallPlan', 'graph_from_adjacency', 'graph_from_edges',
            'plan_single', 'DeviceGraph', 'device_graph_from_adjacency', 'WindowBuilder', 'batch_windows', 'synth_window', 'dense_static_graph', 'concat_static_graphs',
            'train_losses_windows', 'train_chunk', 'train_chunks', 'TrainBatch', 'LossWindows', 'build_train_batch',
-           'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor', 'BucketAdam']
+           'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor', 'BucketAdam',
+           'make_chunks', 'DetectionStore', 'ChunkSampler', 'DrawnChunks', 'draw_chunks_host', 'train_epoch', 'AllChunksSkipped']

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -99,11 +99,21 @@ class CTrainBuild(C.Structure):
                     'rowptr', 'inc', 'det_order', 'det_win', 'edge_win', 'det_idx', 'edge_idx')]
 
 
+class CChunkDraw(C.Structure):
+    """struct tmpnn_chunk_draw (include/tmpnn.h): a seeded draw of augmented training chunks from the detection store."""
+    _fields_ = ([(f, C.c_int32) for f in ('B', 'nchunks', 'L', 'nseq', 'F', 'Fs', 'fr_range', 'transforms')]
+                + [(f, C.c_int64) for f in ('ndets', 'nframes', 'n_max')] + [('seed', C.c_uint64), ('step', C.c_uint64)]
+                + [(f, c_float) for f in ('p_drop', 'p_reverse', 'p_flip', 'reserved')]
+                + [(f, c_void_p) for f in ('indices', 'chunks', 'seq_base', 'first', 'track', 'stat', 'table',
+                                           'count', 'flags', 'offsets', 'X', 'y')])
+
+
 _DGP = C.POINTER(CDGraph)
 _MPP = C.POINTER(CMpParams)
 _TRP = C.POINTER(CTrackRows)
 _LWP = C.POINTER(CLossWindows)
 _TBP = C.POINTER(CTrainBuild)
+_CDP = C.POINTER(CChunkDraw)
 
 # name -> (restype, argtypes); must mirror include/tmpnn.h (tests/test_abi.py cross-checks the names)
 _SIGNATURES = {
@@ -218,6 +228,8 @@ _SIGNATURES = {
     'tmpnn_train_build_count': (c_int, [_TBP, c_void_p]),
     'tmpnn_train_build_calls': (c_int, [_TBP, c_void_p]),
     'tmpnn_train_build_fill': (c_int, [_TBP, c_int, c_void_p]),
+    'tmpnn_chunk_draw_count': (c_int, [_CDP, c_void_p]),
+    'tmpnn_chunk_draw_fill': (c_int, [_CDP, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

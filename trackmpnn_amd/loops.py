@@ -6,6 +6,8 @@
     train_chunks    the same for B chunks at once: a prebuilt block-diagonal TrainBatch (train_batch.py), one forward per
                     call of the batch, the losses of every chunk kept apart (one windowed loss launch per call), ONE
                     backward for the B chunks
+    train_epoch     train.py's epoch over a ChunkSampler (chunks.py): per slice of the epoch's order one device draw of augmented
+                    chunks -> device batch build -> train_chunks -> optimizer step
     infer_sequence  reference/infer.py:35-87    one sequence: per timestep update_graph(mode='test', greedy or Hungarian)
                                                 -> model -> decode_tracks (track finalisation + rolling-window deletion)
 
@@ -29,6 +31,7 @@ import torch
 
 from .loss import CELoss, FocalLoss, train_losses, train_losses_windows
 from .tracking import TrackGraph
+from .train_batch import AllChunksSkipped
 
 
 class _Stages:
@@ -162,6 +165,37 @@ def train_chunks(model, batch, Xs, tp_classifier: bool = True, stages: Optional[
         monitor.fold(counts, acc_c, acc_f)
         monitor.last_counts = counts
     return loss, torch.stack([acc_c.detach(), acc_f.detach()], 1), batch.ncalls, batch.edge_iters
+
+
+def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier: bool = True, monitor=None, scheduler=None) -> int:
+    """One epoch of train.py:54-135 over a ChunkSampler (trackmpnn_amd.chunks): `sampler.epoch_order(epoch)` in slices of
+    `batch_size`, per slice draw -> DrawnChunks.batch() -> opt.zero_grad() -> train_chunks -> opt.step().  Every draw of the
+    epoch uses step = epoch: a chunk's draw is keyed by (seed, step, chunk index) and a chunk comes up once per epoch, so the
+    augmented data of an epoch do not depend on batch_size.  A slice in which the reference would skip every chunk (the
+    build's AllChunksSkipped) takes no step.  `scheduler`, if given, is stepped once at the end (train.py:330's StepLR
+    over `opt`; BucketAdam has no epoch step of its own).  Returns the number of optimizer steps.  A composition only: the
+    waits for the device are the build's two per step."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f'train_epoch: batch_size={batch_size}')
+    order = sampler.epoch_order(epoch)
+    steps = 0
+    for s in range(0, len(order), batch_size):
+        idx = order[s:s + batch_size]
+        if len(idx) == 0:
+            continue
+        drawn = sampler.draw(idx, epoch)
+        try:
+            batch = drawn.batch()
+        except AllChunksSkipped:
+            continue
+        opt.zero_grad()
+        train_chunks(model, batch, drawn.features(batch), tp_classifier, monitor=monitor)
+        opt.step()
+        steps += 1
+    if scheduler is not None:
+        scheduler.step()
+    return steps
 
 
 def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 5, ret_win_size: int = 0,

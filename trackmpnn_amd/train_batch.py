@@ -108,6 +108,11 @@ class TrainBatch:
         return torch.cat([X, X.new_zeros((1, X.shape[1]))])
 
 
+class AllChunksSkipped(ValueError):
+    """Every chunk handed to a batch build is skipped (fewer than two timesteps, or only false positives): there is no batch.
+    A ValueError, as the builds have always raised for this case; loops that redraw their chunks catch it and move on."""
+
+
 def _as_y(y) -> np.ndarray:
     if isinstance(y, torch.Tensor):
         y = y.detach().cpu().numpy()
@@ -130,7 +135,7 @@ def build_train_batch(ys: Sequence, device='cpu') -> TrainBatch:
         kept.append(i)
         wins.append(WindowBuilder(y).calls(empty_calls=True))
     if not wins:
-        raise ValueError('build_train_batch: every chunk is skipped (fewer than two timesteps, or only false positives)')
+        raise AllChunksSkipped('build_train_batch: every chunk is skipped (fewer than two timesteps, or only false positives)')
     plans, refs = batch_windows(wins, device='cpu')
     kept = np.asarray(kept, np.int64)
     B, ncalls = len(wins), len(plans)
@@ -254,7 +259,7 @@ def _stacked_labels(ys, offsets, dev):
     return y.contiguous(), off.contiguous()
 
 
-def build_train_batch_device(ys, device='cuda:0', offsets=None) -> TrainBatch:
+def build_train_batch_device(ys, device='cuda:0', offsets=None, padded: bool = False, draw_flags=None) -> TrainBatch:
     """The TrainBatch of `build_train_batch(ys)`, built by HIP kernels on `device` (csrc/trainbuild.hip): equal in every field,
     except that `chunk_calls` stays empty.  Two device-to-host reads (the per-chunk counts, then the per-call totals), the only
     points where the host waits for the device: host-side tables go up through pinned memory, asynchronously.  No loop over
@@ -262,8 +267,13 @@ def build_train_batch_device(ys, device='cuda:0', offsets=None) -> TrainBatch:
 
     ys: a list of per-chunk labels y_b [ND_b, 2] / [1, ND_b, 2] (host or device), or, with `offsets` [n + 1], one stacked
     [ND, 2] tensor whose chunk i is rows offsets[i] .. offsets[i+1].  Integer dtypes, or floating ones holding integers.
+    padded (with `offsets`): the stacked tensor may hold more rows than offsets[-1]; the rows beyond it are ignored (a draw of
+    `trackmpnn_amd.chunks.ChunkSampler`, whose kept total only the device knows).  Otherwise offsets must run from 0 to ND.
+    draw_flags: the uint8 `flags` [n] of the ChunkSampler draw the labels come from (device).  Their maximum rides along with
+    host read 1 (no further wait), and a chunk the draw kernels refused (bit 7, TMPNN_CD_FLAG_BAD: the store's or the sampler's
+    device tables failed the kernels' checks) raises RuntimeError here, where it would otherwise train as an empty chunk.
     Limits per chunk: TB_MAX_DETS detections and TB_MAX_CALLS calls (build_train_batch serves larger chunks); rows and edges of
-    the batch in int32.  Raises ValueError on malformed labels and when every chunk is skipped."""
+    the batch in int32.  Raises ValueError on malformed labels and AllChunksSkipped (a ValueError) when every chunk is skipped."""
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise RuntimeError('build_train_batch_device runs on the MI355X HIP kernels only (no CPU path): pass a cuda device')
@@ -278,29 +288,40 @@ def build_train_batch_device(ys, device='cuda:0', offsets=None) -> TrainBatch:
     y, off = _stacked_labels(ys, offsets, dev)
     n, ND = off.numel() - 1, int(y.shape[0])
     if n <= 0:
-        raise ValueError('build_train_batch_device: every chunk is skipped (fewer than two timesteps, or only false positives)')
+        raise AllChunksSkipped('build_train_batch_device: every chunk is skipped (fewer than two timesteps, or only false positives)')
     stream = _lib.raw_stream(dev)
     i64 = dict(dtype=torch.int64, device=dev)
     i32 = dict(dtype=torch.int32, device=dev)
     d = _lib.CTrainBuild()
     d.n, d.n_feat, d.y, d.offsets = n, ND, y.data_ptr(), off.data_ptr()
-    buf = torch.empty(5 * n + 1, **i64)
-    buf[4 * n:].copy_(off)
+    if draw_flags is not None and not (isinstance(draw_flags, torch.Tensor) and draw_flags.dtype == torch.uint8 and
+                                       draw_flags.numel() == n):
+        raise ValueError(f'build_train_batch_device: draw_flags must be a uint8 tensor of {n} entries')
+    buf = torch.empty(5 * n + 1 + (draw_flags is not None), **i64)           # info [n, 4], offsets [n + 1], (the draw's flags)
+    buf[4 * n:5 * n + 1].copy_(off)
+    if draw_flags is not None:
+        buf[5 * n + 1:].copy_(draw_flags.to(dev).amax().reshape(1))
     d.info = buf.data_ptr()
     _lib.call('tmpnn_train_build_count', C.byref(d), stream)
     h = buf.cpu().numpy()                                                    # host read 1: the per-chunk counts
-    info, det_offset = h[:4 * n].reshape(n, 4), h[4 * n:].copy()
+    if draw_flags is not None and h[5 * n + 1] & 128:                       # TMPNN_CD_FLAG_BAD
+        raise RuntimeError('build_train_batch_device: the draw kernels refused a chunk (flags bit 7): the device tables of '
+                           'the DetectionStore or of the ChunkSampler do not pass the kernels\' checks')
+    info, det_offset = h[:4 * n].reshape(n, 4), h[4 * n:5 * n + 1].copy()
     bad = np.nonzero(info[:, 0])[0]
     if bad.size:
         i = int(bad[0])
         msg = next(m for bit, m in _TB_STATUS if info[i, 0] & bit)
         raise ValueError(f'build_train_batch_device: chunk {i}: {msg}')
-    if det_offset[0] != 0 or det_offset[-1] != ND:
+    if padded and offsets is not None:
+        if det_offset[0] != 0:
+            raise ValueError(f'build_train_batch_device: offsets must start at 0 (and end within ND = {ND})')
+    elif det_offset[0] != 0 or det_offset[-1] != ND:
         raise ValueError(f'build_train_batch_device: offsets must run from 0 to ND = {ND}')
     kept = np.nonzero(info[:, 1] > 0)[0].astype(np.int64)
     skipped = np.nonzero(info[:, 1] == 0)[0].tolist()
     if kept.size == 0:
-        raise ValueError('build_train_batch_device: every chunk is skipped (fewer than two timesteps, or only false positives)')
+        raise AllChunksSkipped('build_train_batch_device: every chunk is skipped (fewer than two timesteps, or only false positives)')
     ncalls_b = info[kept, 1].astype(np.int64)
     B, Cn = int(kept.size), int(ncalls_b.max())
     cptr = np.zeros(B + 1, np.int64)
