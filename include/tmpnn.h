@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 9 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 10 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
                                left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
                                5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed);
@@ -45,7 +45,9 @@ extern "C" {
                                8: + struct tmpnn_optim_seg, struct tmpnn_adam_state, tmpnn_optim_chunk, tmpnn_adam_step,
                                   tmpnn_grad_flow (entry points added, none changed);
                                9: + struct tmpnn_chunk_draw, tmpnn_chunk_draw_count, tmpnn_chunk_draw_fill (entry points added,
-                                  none changed) */
+                                  none changed);
+                               10: + struct tmpnn_zs_gate_src: tmpnn_gru_bwd_fused_zero_state takes it in place of the gate
+                                   planes when gate_plane == 0 (same arguments; calls that pass planes are unchanged) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -300,7 +302,24 @@ int tmpnn_gru_bwd_fused(const int32_t* rows, int R, int xmode, const int32_t* sr
  * h[dst]; available when tmpnn_gru_bwd_fused_zero_state_available(H, IN, xmode) != 0, i.e. H = IN = 64, xmode 1).  It does
  * not read h[row] nor the fourth gate plane (ghn = b_hn exactly: b_hn = b_hh + 2H), writes d_msg and accumulates dW_ih,
  * db_ih and db_hh (dW_hh gets nothing); d_h[row] is NOT formed, so the row-F adjoint is not taken either: for a call's new
- * rows it lies behind d_h_in.  ws: tmpnn_gru_bwd_fused_ws(R, IN, H) bytes. */
+ * rows it lies behind d_h_in.  ws: tmpnn_gru_bwd_fused_ws(R, IN, H) bytes.
+ *
+ * gate_plane != 0: `gates` is the device pointer to the saved planes [r | z | n], gate_plane floats apart, as for
+ * tmpnn_gru_bwd_fused.  gate_plane == 0: the planes were NOT saved (tmpnn_gru_fwd_tiles_zero_state with gates = NULL) and
+ * `gates` is a HOST pointer to a struct tmpnn_zs_gate_src, read at launch: the kernel forms r, z, n of a row again from the
+ * projected det rows the forward read, with the forward's expressions (bit-identical planes, no matrix product):
+ *   r = sigmoid((0 + (P_r[s] - P_r[d])) + (b_ir + b_hr)), z likewise, n = tanh(fma(r, 0 + b_hn, (P_n[s] - P_n[d]) + b_in))
+ * with s = src_pos[i], d = dst_pos[i] for list position i (the lists run parallel to rows / src / dst).  A NULL struct, a
+ * NULL or misaligned field (proj, b_ih, b_hh 16-byte aligned, ld_proj >= 3H and a multiple of 4) or b_hn != b_hh + 2H
+ * fails with TMPNN_EINVAL before anything is launched.  Available whenever the entry point itself is. */
+typedef struct tmpnn_zs_gate_src {
+    const float* proj;        /* [Dn][ld_proj]: the output of tmpnn_rows_linear the forward call read (columns r | z | n) */
+    int32_t ld_proj;
+    const int32_t* src_pos;   /* [R] det positions (rows of proj) of the rows' endpoints */
+    const int32_t* dst_pos;
+    const float* b_ih;        /* [3H] the cell's biases */
+    const float* b_hh;
+} tmpnn_zs_gate_src;
 int tmpnn_gru_bwd_fused_zero_state_available(int H, int IN, int xmode);
 int tmpnn_gru_bwd_fused_zero_state(const int32_t* rows, int R, const int32_t* src, const int32_t* dst, int IN,
                                    const float* h, int ld_h, int H, const float* w_ih, const float* b_hn,

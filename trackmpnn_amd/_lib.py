@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -46,6 +46,13 @@ class CGraph(C.Structure):
 
 
 _GP = C.POINTER(CGraph)
+
+
+class CZsGateSrc(C.Structure):
+    """struct tmpnn_zs_gate_src (include/tmpnn.h): what tmpnn_gru_bwd_fused_zero_state forms r, z, n from when the forward
+    saved no gate planes (passed by address as `gates`, with gate_plane = 0)."""
+    _fields_ = [('proj', c_void_p), ('ld_proj', C.c_int32), ('src_pos', c_void_p), ('dst_pos', c_void_p),
+                ('b_ih', c_void_p), ('b_hh', c_void_p)]
 
 
 class CEdgeTiles(C.Structure):

@@ -1975,7 +1975,30 @@ __global__ __launch_bounds__(512) void k_gru_bwd_two(GruBwdFusedArgs a, int ntil
 //     stay unwritten).
 // Every wave runs the same straight-line code: role only moves addresses (no role branch, no scratch in the loop).
 // ==========================================================================================
-template <int UP>
+//
+// RC (gate_plane == 0, struct tmpnn_zs_gate_src): the forward saved no gate planes for these rows and the staging forms r, z, n
+// itself from the projected det rows P the forward read -- six 16-byte gathers per row and thread (L2 hits: a 32-row tile touches
+// about 11 det rows) instead of three streamed plane loads, and the forward's own expressions, so the planes it would have
+// stored are reproduced bit for bit (zs_gate / zs_gate_n below mirror k_gru_fwd_split_tiled<., ., true>'s epilogue; the sums
+// b_ir + b_hr, b_iz + b_hz and b_in sit in 768 B of LDS behind the two image sets, formed as the forward's sBias).  The kernel
+// is at its register limit (256), so the requests are staggered over the six groups of an iteration and never hold more
+// registers than the plane loads did: per iteration  0: slices 0 + 1, request dh | 1: slice 3, request x | 2: request the P_r
+// pair | 3: slice 5, request the P_z pair | 4: request the P_n pair, r <- P_r pair | 5: z <- P_z pair, n <- P_n pair and r  (the
+// gate arithmetic sits in the groups without dW products).  The det positions ride with orow_n, two tiles ahead.
+// The compiler's report: 256 registers for every UP, no scratch access inside the tile loop for UP = 1, 3; UP = 2 reloads one spilled
+// register (srow) per tile in the index block at the end of the iteration, where only the dh request is outstanding.
+// The gate source rides in fields of GruBwdFusedArgs this kernel does not otherwise read (ZsGateSrc names them): msg / ld_msg
+// = P and its row stride (as in the forward's arguments), add_src / add_dst = the det positions, add_msg = b_ih; b_hh = b_hn - 2H
+// (a kernel parameter of its own would change the signature of the plane-reading instantiation too, which keeps its ISA).
+struct ZsGateSrc { const float* proj; int ld_proj; const int32_t* src_pos; const int32_t* dst_pos; const float* b_ih; const float* b_hh; };
+
+// a zero-state row's r or z from its two projected rows: the accumulator of the forward is +0 there and is added first
+__device__ __forceinline__ float zs_gate(float ps, float pd, float bsum) { return sigmoidf_((0.0f + (ps - pd)) + bsum); }
+__device__ __forceinline__ float zs_gate_n(float ps, float pd, float b_in, float r, float b_hn) {
+    return tanhf_(gru_n_preact((ps - pd) + b_in, r, 0.0f + b_hn));
+}
+
+template <int UP, bool RC = false>
 __global__ __launch_bounds__(512) void k_gru_bwd_zs(GruBwdFusedArgs a, const float* __restrict__ b_hn, int ntiles) {
     constexpr int H = 64;
     constexpr int SUB = 32 * 128;
@@ -2032,6 +2055,15 @@ __global__ __launch_bounds__(512) void k_gru_bwd_zs(GruBwdFusedArgs a, const flo
     const int nmine = (ntiles - (int)blockIdx.x + G - 1) / G;       // >= 1
     struct { float4 dh, r, z, n, xa, xb; float dy; } raw;
     float d0[4], tv[4];
+    // RC: r, z, n of raw are computed from the pairs of projected-row quarters in rp; the bias sums [b_ir + b_hr | b_iz + b_hz | b_in]
+    // lie behind the two image sets (BUF floats)
+    struct { float4 pa, pb, qa, qb, na, nb; } rp;
+    const ZsGateSrc gsrc{a.msg, a.ld_msg, a.add_src, a.add_dst, a.add_msg, b_hn - 2 * H};
+    float* const sgb = lds + BUF;
+    if constexpr (RC) {
+        if (tid < 3 * H) sgb[tid] = tid < 2 * H ? gsrc.b_ih[tid] + gsrc.b_hh[tid] : gsrc.b_ih[tid];
+        __syncthreads();
+    }
     auto row_of = [&](int tile, bool tvld, bool& vld) -> int {
         const int lr = tile * 32 + srow;
         vld = tvld && lr < a.R;
@@ -2089,11 +2121,60 @@ __global__ __launch_bounds__(512) void k_gru_bwd_zs(GruBwdFusedArgs a, const flo
         raw.xb = *reinterpret_cast<const float4*>(a.h + (size_t)(gd_) * a.ld_h + f4);                        \
     } while (0)
 
+    // RC: the three pairs of projected-row quarters of one row (det positions sp_, dp_) and the gates formed from them
+#define ZS_ISSUE_P(G3, A_, B_, sp_, dp_)                                                                     \
+    do {                                                                                                     \
+        rp.A_ = *reinterpret_cast<const float4*>(gsrc.proj + (size_t)(sp_) * gsrc.ld_proj + (G3) * H + f4); \
+        rp.B_ = *reinterpret_cast<const float4*>(gsrc.proj + (size_t)(dp_) * gsrc.ld_proj + (G3) * H + f4); \
+    } while (0)
+#define ZS_GATE(G3, A_, B_, OUT_)                                                                            \
+    do {                                                                                                     \
+        const float4 b_ = *reinterpret_cast<const float4*>(sgb + (G3) * H + f4);                             \
+        raw.OUT_ = make_float4(zs_gate(rp.A_.x, rp.B_.x, b_.x), zs_gate(rp.A_.y, rp.B_.y, b_.y),             \
+                               zs_gate(rp.A_.z, rp.B_.z, b_.z), zs_gate(rp.A_.w, rp.B_.w, b_.w));            \
+    } while (0)
+#define ZS_GATE_N()                                                                                          \
+    do {                                                                                                     \
+        const float4 b_ = *reinterpret_cast<const float4*>(sgb + 2 * H + f4);                                \
+        raw.n = make_float4(zs_gate_n(rp.na.x, rp.nb.x, b_.x, raw.r.x, bhn.x),                               \
+                            zs_gate_n(rp.na.y, rp.nb.y, b_.y, raw.r.y, bhn.y),                               \
+                            zs_gate_n(rp.na.z, rp.nb.z, b_.z, raw.r.z, bhn.z),                               \
+                            zs_gate_n(rp.na.w, rp.nb.w, b_.w, raw.r.w, bhn.w));                              \
+    } while (0)
+#define ZS_ISSUE_DH(orow_)                                                                                   \
+    do {                                                                                                     \
+        if (UP & 1) raw.dh = *reinterpret_cast<const float4*>(a.up.d_hout + (size_t)(orow_) * a.up.ld_dhout + f4); \
+        if (UP & 2) raw.dy = a.up.dy[(orow_)];                                                               \
+    } while (0)
+
     // ---- prologue: tile 0 staged into buffer 0, tile 1's planes requested (as k_gru_bwd_two)
     bool valid_cur, valid_n;
     int gs_cur, gd_cur;
     int orow_n;
-    {
+    int sp_n = 0, dp_n = 0;                                     // RC: det positions of the rows of orow_n's tile
+    if constexpr (RC) {
+        bool v0, v1;
+        const int lp0 = row_of(blockIdx.x, true, v0);
+        const int o0 = a.rows[lp0];
+        gs_cur = a.src[lp0]; gd_cur = a.dst[lp0];
+        const int sp0 = gsrc.src_pos[lp0], dp0 = gsrc.dst_pos[lp0];
+        ZS_ISSUE_DH(o0); ZS_ISSUE_GATHER(gs_cur, gd_cur);
+        ZS_ISSUE_P(0, pa, pb, sp0, dp0); ZS_ISSUE_P(1, qa, qb, sp0, dp0); ZS_ISSUE_P(2, na, nb, sp0, dp0);
+        const int lp1 = row_of(blockIdx.x + G, 1 < nmine, v1);
+        const int o1 = a.rows[lp1];
+        const int sp1 = gsrc.src_pos[lp1], dp1 = gsrc.dst_pos[lp1];
+        ZS_GATE(0, pa, pb, r); ZS_GATE(1, qa, qb, z); ZS_GATE_N();
+        ZS_SLICE(0, lds16, v0); ZS_SLICE(1, lds16, v0); ZS_SLICE(3, lds16, v0); ZS_SLICE(5, lds16, v0);
+        ZS_ISSUE_DH(o1);
+        ZS_ISSUE_P(0, pa, pb, sp1, dp1); ZS_GATE(0, pa, pb, r);
+        ZS_ISSUE_P(1, qa, qb, sp1, dp1); ZS_GATE(1, qa, qb, z);
+        ZS_ISSUE_P(2, na, nb, sp1, dp1); ZS_GATE_N();
+        valid_cur = v1;
+        gs_cur = a.src[lp1]; gd_cur = a.dst[lp1];
+        const int lp2 = row_of(blockIdx.x + 2 * G, 2 < nmine, valid_n);
+        orow_n = a.rows[lp2];
+        sp_n = gsrc.src_pos[lp2]; dp_n = gsrc.dst_pos[lp2];
+    } else {
         bool v0, v1;
         const int lp0 = row_of(blockIdx.x, true, v0);
         const int o0 = a.rows[lp0];
@@ -2147,11 +2228,34 @@ __global__ __launch_bounds__(512) void k_gru_bwd_zs(GruBwdFusedArgs a, const flo
                     const uint2 u0 = lds_read_tr(p0 + pc * PA), u1 = lds_read_tr(p1 + pc * PA);
                     aw[pc] = make_uint4(u0.x, u0.y, u1.x, u1.y);
                 }
-                ZS_SLICE(s6, nxt, valid_cur);
-                ZS_ISSUE_MAIN(s6, orow_n);
+                if constexpr (RC) {
+                    if (s6 == 0) {
+                        ZS_SLICE(0, nxt, valid_cur); ZS_SLICE(1, nxt, valid_cur);
+                        ZS_ISSUE_DH(orow_n);
+                    } else if (s6 == 1) {
+                        ZS_SLICE(3, nxt, valid_cur);
+                        ZS_ISSUE_GATHER(gs_cur, gd_cur);
+                    } else {
+                        ZS_ISSUE_P(0, pa, pb, sp_n, dp_n);
+                    }
+                } else {
+                    ZS_SLICE(s6, nxt, valid_cur);
+                    ZS_ISSUE_MAIN(s6, orow_n);
+                }
                 acc[s6] = mfma32_c<0>(aw, bt, acc[s6]); acc[s6] = mfma32_c<1>(aw, bt, acc[s6]);
                 acc[s6] = mfma32_c<2>(aw, bt, acc[s6]); acc[s6] = mfma32_c<3>(aw, bt, acc[s6]);
                 acc[s6] = mfma32_c<4>(aw, bt, acc[s6]); acc[s6] = mfma32_c<5>(aw, bt, acc[s6]);
+            } else if constexpr (RC) {
+                if (s6 == 3) {
+                    ZS_SLICE(5, nxt, valid_cur);
+                    ZS_ISSUE_P(1, qa, qb, sp_n, dp_n);
+                } else if (s6 == 4) {
+                    ZS_ISSUE_P(2, na, nb, sp_n, dp_n);
+                    ZS_GATE(0, pa, pb, r);
+                } else {
+                    ZS_GATE(1, qa, qb, z);
+                    ZS_GATE_N();
+                }
             } else {
                 ZS_SLICE(s6, nxt, valid_cur);
                 if (s6 == 3) ZS_ISSUE_GATHER(gs_cur, gd_cur);
@@ -2170,6 +2274,7 @@ __global__ __launch_bounds__(512) void k_gru_bwd_zs(GruBwdFusedArgs a, const flo
             valid_cur = valid_n;
             const int lp3 = row_of(tile + 3 * G, it + 3 < nmine, valid_n);
             orow_n = a.rows[lp3];
+            if constexpr (RC) { sp_n = gsrc.src_pos[lp3]; dp_n = gsrc.dst_pos[lp3]; }
             (void)vnn;
         }
         // ---- epilogue: lane (j16, kq) holds columns n0 + 4 kq .. + 3 of row 16 role + j16
@@ -2179,6 +2284,10 @@ __global__ __launch_bounds__(512) void k_gru_bwd_zs(GruBwdFusedArgs a, const flo
                     make_float4(accd[0], accd[1], accd[2], accd[3]);
         __syncthreads();
     }
+#undef ZS_ISSUE_DH
+#undef ZS_GATE_N
+#undef ZS_GATE
+#undef ZS_ISSUE_P
 #undef ZS_ISSUE_GATHER
 #undef ZS_ISSUE_MAIN
 #undef ZS_SLICE
@@ -2605,6 +2714,19 @@ int tmpnn_gru_bwd_fused_zero_state(const int32_t* rows, int R, const int32_t* sr
     if (R == 0) return TMPNN_OK;
     TM_REQUIRE(R > 0 && rows && src && dst && h && w_ih && b_hn && gates && d_msg && dW_ih && db_ih && db_hh,
                "gru_bwd_fused_zero_state: null pointer");
+    // gate_plane == 0: no planes were saved; `gates` is a host struct naming what the kernel forms r, z, n from
+    const bool rc_gates = gate_plane == 0;
+    ZsGateSrc gsrc{};
+    if (rc_gates) {
+        const tmpnn_zs_gate_src* g = reinterpret_cast<const tmpnn_zs_gate_src*>(gates);
+        TM_REQUIRE(g->proj && g->src_pos && g->dst_pos && g->b_ih && g->b_hh,
+                   "gru_bwd_fused_zero_state: gate_plane = 0 needs proj, src_pos, dst_pos, b_ih and b_hh (struct tmpnn_zs_gate_src)");
+        TM_REQUIRE(aligned16(g->proj) && g->ld_proj >= 3 * H && (g->ld_proj & 3) == 0 && aligned16(g->b_ih) && aligned16(g->b_hh),
+                   "gru_bwd_fused_zero_state: gate source layout (16-byte alignment, ld_proj=%d)", (int)g->ld_proj);
+        TM_REQUIRE(b_hn == g->b_hh + 2 * H, "gru_bwd_fused_zero_state: b_hn is not b_hh + 2H of the gate source");
+        gsrc = ZsGateSrc{g->proj, g->ld_proj, g->src_pos, g->dst_pos, g->b_ih, g->b_hh};
+        gates = nullptr;
+    }
     TM_REQUIRE(d_hout != nullptr || dy != nullptr, "gru_bwd_fused_zero_state: no upstream gradient");
     TM_REQUIRE(dy == nullptr || (w_head != nullptr && aligned16(w_head)),
                "gru_bwd_fused_zero_state: dy needs a 16-byte aligned w_head");
@@ -2623,6 +2745,10 @@ int tmpnn_gru_bwd_fused_zero_state(const int32_t* rows, int R, const int32_t* sr
     GruBwdFusedArgs a{rows, R, src, dst, nullptr, 0, 0, h, ld_h, w_ih, nullptr, gates, gate_plane,
                       DhSrc{d_hout, ld_dhout, dy, w_head}, d_msg, ld_dmsg, nullptr, 0, nullptr, nullptr, nullptr, 0,
                       slab_w, slab_b, IN};
+    if (rc_gates) {      // (the fields k_gru_bwd_zs<., true> reads its gate source from)
+        a.msg = gsrc.proj; a.ld_msg = gsrc.ld_proj;
+        a.add_src = gsrc.src_pos; a.add_dst = gsrc.dst_pos; a.add_msg = gsrc.b_ih;
+    }
     const int ntiles = ceil_div(R, 32);
     const size_t shm = 147456;                               // two 72 KiB operand-image sets
     hipStream_t st = as_stream(stream);
@@ -2632,7 +2758,17 @@ int tmpnn_gru_bwd_fused_zero_state(const int32_t* rows, int R, const int32_t* sr
         TM_SHM_ONCE((k_gru_bwd_zs<U>), shm);                                                                 \
         hipLaunchKernelGGL((k_gru_bwd_zs<U>), dim3(n_rs), dim3(512), shm, st, a, b_hn, ntiles);              \
     } while (0)
-    if (up == 1) LZ(1); else if (up == 2) LZ(2); else LZ(3);
+#define LZR(U)                                                                                               \
+    do {                                                                                                     \
+        TM_SHM_ONCE((k_gru_bwd_zs<U, true>), shm + 3 * H * sizeof(float));                                   \
+        hipLaunchKernelGGL((k_gru_bwd_zs<U, true>), dim3(n_rs), dim3(512), shm + 3 * H * sizeof(float), st, a, b_hn, ntiles); \
+    } while (0)
+    if (rc_gates) {
+        if (up == 1) LZR(1); else if (up == 2) LZR(2); else LZR(3);
+    } else {
+        if (up == 1) LZ(1); else if (up == 2) LZ(2); else LZ(3);
+    }
+#undef LZR
 #undef LZ
     int rc = check_launch("gru_bwd_fused_zero_state");
     if (rc) return rc;

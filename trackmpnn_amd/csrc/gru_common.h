@@ -18,6 +18,10 @@ __device__ __forceinline__ float tanhf_(float x) {
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x));
 }
 
+// pre-activation of the n gate, acc_in + r * hn, as ONE fused multiply-add: the tiled forward and the zero-state backward's
+// gate recompute (k_gru_bwd_zs_rc) must round it alike, whatever the compiler would contract at either call site
+__device__ __forceinline__ float gru_n_preact(float acc_in, float r, float hn) { return __builtin_fmaf(r, hn, acc_in); }
+
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }

@@ -975,7 +975,7 @@ __global__ __launch_bounds__(WPB * 64, ZS ? 3 : 1) void k_gru_fwd_split_tiled(Gr
                     const float ro = sigmoidf_(acc_r[reg]);
                     const float zo = sigmoidf_(acc_z[reg]);
                     const float ho = acc_hn[reg] + bh[i];
-                    const float no = tanhf_(acc_in[reg] + ro * ho);
+                    const float no = tanhf_(gru_n_preact(acc_in[reg], ro, ho));
                     outv[reg] = (1.0f - zo) * no + zo * hp[i];
                     acc_r[reg] = ro; acc_z[reg] = zo; acc_hn[reg] = ho; acc_in[reg] = no;
                 }

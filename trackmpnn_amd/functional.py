@@ -73,6 +73,9 @@ INPUT_TF = _variant('TMPNN_INPUT_TF', '1') != '0'
 # reads them.  Same gradients bit for bit; measured SLOWER (numbers in DESIGN), so off by default.
 RECOMPUTE_GATES = _variant('TMPNN_RECOMPUTE_GATES', '0') == '1'
 CONCAT_PROJ = _variant('TMPNN_CONCAT_PROJ', '1') != '0'
+# a call's new (zero-state) edge rows: the forward saves NO gate planes for them and the zero-state backward forms r, z, n again
+# from the call's projected det rows (no matrix product: see k_gru_bwd_zs<., true>); TMPNN_ZS_RECOMPUTE=0 keeps the planes
+ZS_RECOMPUTE = _variant('TMPNN_ZS_RECOMPUTE', '1') != '0'
 # the window-owned segment sum (csrc/agg.hip k_segsum_win) on graphs with window labels: bit-equal to the CSR kernel, 0.9 ms
 # against its 0.43 ms per 6 M edges on MI355X -- kept opt-in
 WIN_SEGSUM = _variant('TMPNN_SEGSUM_WIN', '0') == '1'
@@ -319,8 +322,13 @@ def mp_forward(spec: ModelSpec, plan: CallPlan, x: torch.Tensor, h_in: Optional[
     zs_bwd = (zs_fwd and save and ZERO_STATE_BWD and FUSED_BWD and bool(lib.tmpnn_gru_bwd_fused_available(H, H, 0))
               and bool(lib.tmpnn_gru_bwd_fused_available(H, spec.IN_e, 1))
               and bool(lib.tmpnn_gru_bwd_fused_zero_state_available(H, spec.IN_e, 1)))
+    # ... and whether that backward forms the rows' r, z, n itself (then their gate slots are allocated but never touched, and the
+    # call's projected det rows are kept for it: 768 B per det row and feature group)
+    zs_rc = zs_bwd and ZS_RECOMPUTE
     if zs_fwd and save:
         saved['zs_bwd'] = zs_bwd
+    if zs_rc:
+        saved['zs_rc'] = dict(proj={}, src_pos=g.src_pos, dst_pos=g.dst_pos)
     if n > 0:
         if not (zs_fwd and (zs_bwd or not save)):
             h_cat[N_old:].zero_()                   # new edge rows start at 0 (track_mpnn.py:61)
@@ -482,8 +490,10 @@ def mp_forward(spec: ModelSpec, plan: CallPlan, x: torch.Tensor, h_in: Optional[
                 if zs_fwd:
                     _lib.call('tmpnn_gru_fwd_tiles_zero_state', edge_tiles(g, FWD_TILE_ROWS, e0=E_old).cref(), E - E_old,
                               proj.data_ptr(), 3 * H, H, P[f + 'edge_gru.bias_ih'].data_ptr(),
-                              P[f + 'edge_gru.bias_hh'].data_ptr(), og, GH, gp, plane, int(save and not zs_bwd), we_g,
-                              part_g, N, st)
+                              P[f + 'edge_gru.bias_hh'].data_ptr(), og, GH, None if zs_rc else gp, plane,
+                              int(save and not zs_bwd), we_g, part_g, N, st)
+                    if zs_rc:
+                        saved['zs_rc']['proj'][gi] = proj
                 if recompute:
                     saved.setdefault('proj', {})[gi] = (proj, e_whh_t)
             else:
@@ -683,9 +693,18 @@ def mp_backward(spec: ModelSpec, plan: CallPlan, saved: dict, P: Dict[str, torch
                           grads[f + 'edge_gru.bias_ih'].data_ptr(), grads[f + 'edge_gru.bias_hh'].data_ptr(),
                           ws_w.data_ptr(), ws_w.numel() * 4, st)
             if zs:
+                zg, zplane = gp, plane
+                rc = saved.get('zs_rc')
+                if rc is not None:
+                    # no planes were saved for these rows: the kernel forms the gates from the forward's projected det rows
+                    # (struct tmpnn_zs_gate_src, read at launch; gate_plane = 0 says so)
+                    src_ = _lib.CZsGateSrc(rc['proj'][gi].data_ptr(), 3 * H, rc['src_pos'].data_ptr() + 4 * E_old,
+                                           rc['dst_pos'].data_ptr() + 4 * E_old, P[f + 'edge_gru.bias_ih'].data_ptr(),
+                                           P[f + 'edge_gru.bias_hh'].data_ptr())
+                    zg, zplane = ctypes.addressof(src_), 0
                 _lib.call('tmpnn_gru_bwd_fused_zero_state', g.edge_row.data_ptr() + 4 * E_old, E - E_old,
                           g.src.data_ptr() + 4 * E_old, g.dst.data_ptr() + 4 * E_old, IN_e, hg, GH, H,
-                          P[f + 'edge_gru.weight_ih'].data_ptr(), b_hn, gp, plane, dog, GH, dyp, we,
+                          P[f + 'edge_gru.weight_ih'].data_ptr(), b_hn, zg, zplane, dog, GH, dyp, we,
                           dmsg.data_ptr(), IN_e, grads[f + 'edge_gru.weight_ih'].data_ptr(),
                           grads[f + 'edge_gru.bias_ih'].data_ptr(), grads[f + 'edge_gru.bias_hh'].data_ptr(),
                           ws_w.data_ptr(), ws_w.numel() * 4, st)
