@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 10 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 11 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
                                left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
                                5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed);
@@ -47,7 +47,8 @@ extern "C" {
                                9: + struct tmpnn_chunk_draw, tmpnn_chunk_draw_count, tmpnn_chunk_draw_fill (entry points added,
                                   none changed);
                                10: + struct tmpnn_zs_gate_src: tmpnn_gru_bwd_fused_zero_state takes it in place of the gate
-                                   planes when gate_plane == 0 (same arguments; calls that pass planes are unchanged) */
+                                   planes when gate_plane == 0 (same arguments; calls that pass planes are unchanged);
+                               11: + tmpnn_online_features (entry point added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -934,6 +935,24 @@ int tmpnn_track_retire(const tmpnn_dgraph* g, const tmpnn_track_rows* rows, cons
                        float* h_new, int ld_hn, float* s_new, int next_t, int32_t* active, int32_t* notify,
                        tmpnn_stream stream);
 
+
+/* ======================================================================================================
+ * Online tracking (trackmpnn_amd.online.OnlineTracker): the feature rows of one frame's raw detections, built on the
+ * device (csrc/online.hip).  The reference's feature arithmetic (dataset/kitti_mot.py:545-566) in float32, per new
+ * detection j < D and column c of row nd + j of X:
+ *     [0, ncat)                 one-hot of the 1-based category
+ *     [ncat, ncat + 5)          score, (x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1
+ *     has_temp: the next 2      table[t_slot][0:2]: (sin, cos) of (t mod fr_range) pi / fr_range, built by the HOST with
+ *                               numpy (t_slot = t mod fr_range; table [fr_range][2], not standardised)
+ *     vis_cols: the last ones   vis[j][0:vis_cols]
+ * and every column stored as (v - mean[c]) / std[c], each a single correctly rounded operation: the rows equal
+ * trackmpnn_amd.online.online_features_host bit for bit.  Also y_track[nd + j] = -1 and ids[nd + j] = nd + j.
+ * raw [D][6] 32-bit words: category (int32), then score, x1, y1, x2, y2 (float32 bits).  X [cap][ld_x] with nd + D <= cap
+ * (checked on the host); categories are NOT checked on the device (one outside 1..ncat gives an all-zero one-hot).
+ * One launch; D = 0 launches nothing. */
+int tmpnn_online_features(int D, int nd, int cap, int t_slot, int fr_range, int ncat, int has_temp, int vis_cols,
+                          const int32_t* raw, const float* vis, int ld_vis, const float* mean, const float* std_,
+                          const float* table, float* X, int ld_x, int32_t* y_track, int32_t* ids, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Wide cells (H = 128 / 256, diff messages; BASELINE.json C5) as LDS-tiled GEMMs on bf16x6 split products

@@ -10,6 +10,7 @@ from .loss import (CELoss, FocalLoss, classification_counts, classification_coun
                    train_losses_windows)
 from .loops import train_chunk, train_chunks, train_epoch
 from .monitor import TrainMonitor
+from .online import FeatureSpec, OnlineTracker, online_features_host
 from .optim import BucketAdam
 from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
@@ -19,4 +20,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'plan_single', 'DeviceGraph', 'device_graph_from_adjacency', 'WindowBuilder', 'batch_windows', 'synth_window', 'dense_static_graph', 'concat_static_graphs',
            'train_losses_windows', 'train_chunk', 'train_chunks', 'TrainBatch', 'LossWindows', 'build_train_batch',
            'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor', 'BucketAdam',
-           'make_chunks', 'DetectionStore', 'ChunkSampler', 'DrawnChunks', 'draw_chunks_host', 'train_epoch', 'AllChunksSkipped']
+           'make_chunks', 'DetectionStore', 'ChunkSampler', 'DrawnChunks', 'draw_chunks_host', 'train_epoch', 'AllChunksSkipped',
+           'OnlineTracker', 'FeatureSpec', 'online_features_host']

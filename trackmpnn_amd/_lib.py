@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -237,6 +237,8 @@ _SIGNATURES = {
     'tmpnn_train_build_fill': (c_int, [_TBP, c_int, c_void_p]),
     'tmpnn_chunk_draw_count': (c_int, [_CDP, c_void_p]),
     'tmpnn_chunk_draw_fill': (c_int, [_CDP, c_void_p]),
+    'tmpnn_online_features': (c_int, [c_int] * 8 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_void_p, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

@@ -97,6 +97,9 @@ class TrackGraph:
         self._t_range: dict = {}
         self._Xd: Optional[torch.Tensor] = None
         self._fin_ws: Optional[torch.Tensor] = None
+        # a stream (online.py): y_track / _pos_of_det are capacity-sized and the detections so far number _ND; None: a whole
+        # sequence, ND = y_track.numel()
+        self._ND: Optional[int] = None
 
     def __del__(self):
         # every launch that writes the mirror has been waited for by the call that issued it: the buffer is free to reuse
@@ -166,32 +169,14 @@ class TrackGraph:
         t0, t1, tN = int(later[0]), int(later[1]), int(times[-1])
         ids0, ids1 = np.nonzero(yy[:, 0] == t0)[0], np.nonzero(yy[:, 0] == t1)[0]
         n0, n1 = ids0.size, ids1.size
-        N = n0 + n0 * n1 + n1
-        if N > TRACK_MAX_ROWS:
-            raise ValueError(f'TrackGraph: {N} rows exceed the device-resident limit of {TRACK_MAX_ROWS}')
-        ts = np.full(N, -1, np.int32)
-        did = np.full(N, -1, np.int32)
-        ts[:n0], ts[n0 + n0 * n1:] = t0, t1
-        did[:n0], did[n0 + n0 * n1:] = ids0, ids1
-        is_edge = (ts == -1).astype(np.uint8)
-        src = np.full(N, -1, np.int32)
-        dst = np.full(N, -1, np.int32)
-        src[n0:n0 + n0 * n1] = np.repeat(np.arange(n0), n1)
-        dst[n0:n0 + n0 * n1] = n0 + n0 * n1 + np.tile(np.arange(n1), n0)
-        lab = np.zeros(N, np.uint8)
         trk = yy[:, 1]
-        lab[:n0] = trk[ids0] >= 0
-        lab[n0 + n0 * n1:] = trk[ids1] >= 0
-        same = (trk[ids0][:, None] == trk[ids1][None, :]) & (trk[ids1][None, :] != -1)
-        if (same.sum(0) > 1).any():
-            raise AssertionError('More than one detection from same timestep assinged to same track!')
-        lab[n0:n0 + n0 * n1] = same.reshape(-1)
+        N, (ts, did, is_edge, src, dst, lab) = cls._first_block(t0, ids0, t1, ids1, trk[ids0], trk[ids1])
         tg = cls(device)
         tg.N, tg.E, tg.Dn = N, n0 * n1, n0 + n1
         # ONE upload for the whole sequence: the block's rows, the detections sorted by time, their tracks and the features
         ND, F = int(yy.shape[0]), int(X.shape[2])
         order = np.argsort(yy[:, 0], kind='stable').astype(np.int32)
-        parts = [ts, did, is_edge.astype(np.int32), src, dst, lab.astype(np.int32), order, trk.astype(np.int32)]
+        parts = [ts, did, is_edge, src, dst, lab, order, trk.astype(np.int32)]
         x_host = not X.is_cuda
         if x_host:
             parts.append(np.ascontiguousarray(X[0].detach().float().numpy()).view(np.int32).reshape(-1))
@@ -220,6 +205,73 @@ class TrackGraph:
         tg._graph = g
         tg._pk = pk                                        # (the views above keep it alive as well)
         return tg, (feats if tg._Xd.dtype == torch.float32 else feats.to(tg._Xd.dtype)), t1 + 1, tN + 1
+
+    @staticmethod
+    def _first_block(t0: int, ids0, t1: int, ids1, trk0, trk1):
+        """The rows of initialize_graph's block `[dets t0][edges t0 x t1, src-major][dets t1]` (utils/graph.py:141-163) as the six
+        int32 arrays tmpnn_track_load takes packed: (N, (ts, det id, is_edge, src, dst, labels)).  ids*: detection ids of the two
+        timesteps; trk*: their track ids (-1: none)."""
+        ids0, ids1, trk0, trk1 = (np.asarray(a) for a in (ids0, ids1, trk0, trk1))
+        n0, n1 = ids0.size, ids1.size
+        N = n0 + n0 * n1 + n1
+        if N > TRACK_MAX_ROWS:
+            raise ValueError(f'TrackGraph: {N} rows exceed the device-resident limit of {TRACK_MAX_ROWS}')
+        ts = np.full(N, -1, np.int32)
+        did = np.full(N, -1, np.int32)
+        ts[:n0], ts[n0 + n0 * n1:] = t0, t1
+        did[:n0], did[n0 + n0 * n1:] = ids0, ids1
+        is_edge = (ts == -1).astype(np.int32)
+        src = np.full(N, -1, np.int32)
+        dst = np.full(N, -1, np.int32)
+        src[n0:n0 + n0 * n1] = np.repeat(np.arange(n0), n1)
+        dst[n0:n0 + n0 * n1] = n0 + n0 * n1 + np.tile(np.arange(n1), n0)
+        lab = np.zeros(N, np.int32)
+        lab[:n0] = trk0 >= 0
+        lab[n0 + n0 * n1:] = trk1 >= 0
+        same = (trk0[:, None] == trk1[None, :]) & (trk1[None, :] != -1)
+        if (same.sum(0) > 1).any():
+            raise AssertionError('More than one detection from same timestep assinged to same track!')
+        lab[n0:n0 + n0 * n1] = same.reshape(-1)
+        return N, (ts, did, is_edge, src, dst, lab)
+
+    @classmethod
+    def start_stream(cls, device, Xf: torch.Tensor, ids: torch.Tensor, track: torch.Tensor, y_track: torch.Tensor,
+                     pos_of_det: torch.Tensor, nd: int, t0: int, r0, t1: int, r1):
+        """initialize_graph for a STREAM (online.py): the block of two timesteps whose feature rows are already on the device.
+        Xf [cap, F] float32 feature rows by detection id, ids int32 [cap] (the identity: detection ids are arrival order), track
+        int32 [cap] (all -1), y_track / pos_of_det int32 [cap]: the caller's capacity-sized buffers, `nd` detections so far; r0 /
+        r1 = (first id, one past the last id) of timesteps t0 < t1.  y_track is NOT reset (tracks finalised before a
+        re-initialisation stay).  Returns (graph, feats [N, F]); the caller keeps `_t_range`, `_ND` and the buffers current
+        (bind_stream) before every update / decode / greedy_run_fast."""
+        ids0, ids1 = np.arange(r0[0], r0[1]), np.arange(r1[0], r1[1])
+        none0, none1 = np.full(ids0.size, -1, np.int64), np.full(ids1.size, -1, np.int64)
+        N, parts = cls._first_block(int(t0), ids0, int(t1), ids1, none0, none1)
+        tg = cls(device)
+        tg.N, tg.E, tg.Dn = N, ids0.size * ids1.size, ids0.size + ids1.size
+        tg.bind_stream(Xf, ids, track, y_track, pos_of_det, nd)
+        tg._X_src = tg._y_src = None
+        pk = torch.from_numpy(np.concatenate(parts)).to(tg.device, non_blocking=True)
+        F = int(Xf.shape[1])
+        feats = torch.empty((N, F), dtype=torch.float32, device=tg.device)
+        g, ws = tg._new_graph(N)
+        _lib.call('tmpnn_track_load', N, 0, pk.data_ptr(), C.byref(tg._crows[tg._cur]), Xf.data_ptr(), F, F, feats.data_ptr(), F,
+                  None, g.cref(), _lib.ptr(ws), 0 if ws is None else ws.numel(), _stream())
+        g._meta = (tg.E, tg.Dn, 0)
+        tg._graph = g
+        tg._pk = pk
+        return tg, feats
+
+    def bind_stream(self, Xf: torch.Tensor, ids: torch.Tensor, track: torch.Tensor, y_track: torch.Tensor,
+                    pos_of_det: torch.Tensor, nd: int) -> None:
+        """(Re-)attach a stream's capacity-sized buffers, e.g. after they grew: the native driver's call template caches their
+        addresses and is dropped when one moved."""
+        moved = self._Xd is None or any(a.data_ptr() != b.data_ptr() for a, b in (
+            (Xf, self._Xf), (ids, self._ids_sorted), (track, self.track), (y_track, self.y_track), (pos_of_det, self._pos_of_det)))
+        if moved:
+            self._Xd = self._Xf = Xf
+            self._ids_sorted, self.track, self.y_track, self._pos_of_det = ids, track, y_track, pos_of_det
+            self._fast_tpl = None
+        self._ND = int(nd)
 
     def _sequence(self, yy: np.ndarray, order: np.ndarray) -> None:
         """Per-sequence host state: where each timestep's detections sit in the time-sorted id list; device scratch."""
@@ -346,6 +398,10 @@ class TrackGraph:
                     raise ValueError(f'TrackGraph.update: {nm} differs from what initialize() was given (its contents are '
                                      'cached on the device once per sequence); start a new TrackGraph for new data')
             self._X_src, self._y_src, self._src_versions = X, y, (X._version, y._version)
+        return self._update_rows(score_pos, t, mode, use_hungarian)
+
+    def _update_rows(self, score_pos: Optional[torch.Tensor], t: int, mode: str = 'test', use_hungarian: bool = False) -> torch.Tensor:
+        """update() behind its X / y identity check: everything it does, from the device-resident features and `_t_range`."""
         train = mode == 'train'
         pf, self._prefetch = self._prefetch, None
         N = self.N
@@ -441,7 +497,7 @@ class TrackGraph:
         hung_dev = use_hungarian and self._hungarian_on_device()
         if use_hungarian and not hung_dev:
             self._hungarian(sp)
-        ND = int(self.y_track.numel())
+        ND = int(self.y_track.numel()) if self._ND is None else self._ND
         wsb = int(_lib.load().tmpnn_track_finalize_ws(N))
         if wsb and (self._fin_ws is None or self._fin_ws.numel() * 4 < wsb):
             self._fin_ws = torch.empty((wsb // 4 + 1,), dtype=torch.int32, device=self.device)
@@ -541,6 +597,8 @@ class TrackGraph:
             self._fast_tpl = tpl
         ti = tpl[:30]
         ti[8] = int(ret_win_size)
+        if self._ND is not None:                  # (a stream: the detections so far, not the buffers' capacity)
+            ti[18] = self._ND
         if self._cur:
             ti[13], ti[14] = ti[14], ti[13]
         ti[23] = _stream()
