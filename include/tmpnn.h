@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 11 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 12 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
                                left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
                                5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed);
@@ -48,7 +48,9 @@ extern "C" {
                                   none changed);
                                10: + struct tmpnn_zs_gate_src: tmpnn_gru_bwd_fused_zero_state takes it in place of the gate
                                    planes when gate_plane == 0 (same arguments; calls that pass planes are unchanged);
-                               11: + tmpnn_online_features (entry point added, none changed) */
+                               11: + tmpnn_online_features (entry point added, none changed);
+                               12: + struct tmpnn_mot_store, struct tmpnn_mot_record, tmpnn_mot_events, tmpnn_mot_events_ws,
+                                   tmpnn_mot_dist, tmpnn_mot_max_per_frame (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -953,6 +955,54 @@ int tmpnn_track_retire(const tmpnn_dgraph* g, const tmpnn_track_rows* rows, cons
 int tmpnn_online_features(int D, int nd, int cap, int t_slot, int fr_range, int ncat, int has_temp, int vis_cols,
                           const int32_t* raw, const float* vis, int ld_vis, const float* mean, const float* std_,
                           const float* table, float* X, int ld_x, int32_t* y_track, int32_t* ids, tmpnn_stream stream);
+
+/* ======================================================================================================
+ * MOT evaluation (trackmpnn_amd.moteval.MotEvaluator): the CLEAR-MOT events of S sequences' tracks against their ground truth
+ * in one launch (csrc/moteval.hip) -- what the reference's validation pass does on the host with py-motmetrics, one frame at a
+ * time (utils/metrics.py:7-61, train.py:264-282).  The rule is trackmpnn_amd.moteval.mot_events_host; counts are equal to it,
+ * the distances and dist_sum bit for bit.
+ *
+ * The store holds what does not change between evaluations, packed over the sequences (all device memory, built by
+ * trackmpnn_amd.moteval.MotStore): both sides' rows sorted stably by frame, GT rows with a negative track dropped,
+ *     seq      [S][8] int64    gt_base, n_gt, det_base, n_det, off_base, n_frames, obj_base, n_obj of a sequence
+ *     gt_off   [n_off] int32   per sequence n_frames + 1 offsets over its frame range, relative to gt_base; det_off likewise
+ *     gt_id    [n_gt] int32    object ids renumbered densely per sequence (0 .. n_obj - 1)
+ *     gt_box   [n_gt][4], det_box [n_det][4] float32  x1 y1 x2 y2 (16-byte aligned)
+ *     det_perm [n_det] int32   sorted position -> arrival index of a detection, relative to det_base
+ * tracks [n_det] int32: y_out[:, 1] of every sequence in ARRIVAL order at its det_base; negative = no track.
+ * ====================================================================================================== */
+typedef struct tmpnn_mot_store {
+    int32_t S, reserved;
+    int64_t n_gt, n_det, n_off, n_obj; /* totals over the sequences: the lengths of the arrays below */
+    const int64_t* seq;
+    const int32_t* gt_off;
+    const int32_t* det_off;
+    const int32_t* gt_id;
+    const float* gt_box;
+    const float* det_box;
+    const int32_t* det_perm;
+} tmpnn_mot_store;
+/* One per sequence.  flag: 0, or in its low byte 1 = a frame with more than tmpnn_mot_max_per_frame() GT rows or kept
+ * hypotheses, 2 = a hypothesis id twice in a frame, 4 = the store is inconsistent (an offset, a permutation entry or an object
+ * id out of range: nothing was read outside the arrays), 8 = the solver found no augmenting path; above it (flag >> 8) the
+ * 1-based index of the frame in the sequence's range.  A flagged sequence's counts are those up to that frame. */
+typedef struct tmpnn_mot_record {
+    int64_t objects, predictions, matches /* switches included */, switches, false_positives, misses, frames;
+    int64_t flag;
+    double dist_sum; /* the matched distances, added by frame, then by position among the frame's GT rows */
+} tmpnn_mot_record;
+int tmpnn_mot_max_per_frame(void);
+/* bytes: per sequence a cost matrix of the limit's size (used by frames whose matrix does not fit in LDS), the remembered
+ * hypothesis and last matched frame per object, the tracks in sorted order */
+size_t tmpnn_mot_events_ws(int S, int64_t n_obj, int64_t n_det);
+/* One launch, one workgroup per sequence, out [S].  seq_host: the HOST copy of st->seq, checked against the totals before the
+ * launch (the kernel checks the device copy again, and every offset it indexes by).  ws: 16-byte aligned, tmpnn_mot_events_ws
+ * bytes; its contents need not survive between calls. */
+int tmpnn_mot_events(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, void* ws, size_t ws_bytes,
+                     tmpnn_mot_record* out, tmpnn_stream stream);
+/* out [na][nb] float64 = 1 - IoU of box_a[i], box_b[j] (x1 y1 x2 y2 float32, 16-byte aligned), NaN where it exceeds 0.5 or is
+ * 0 / 0: width and height in float32, the rest in float64, bit-equal to trackmpnn_amd.moteval.mot_dist_host. */
+int tmpnn_mot_dist(const float* box_a, int na, const float* box_b, int nb, double* out, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Wide cells (H = 128 / 256, diff messages; BASELINE.json C5) as LDS-tiled GEMMs on bf16x6 split products

@@ -8,8 +8,9 @@ from .capture import CapturedWindow
 from .chunks import ChunkSampler, DetectionStore, DrawnChunks, draw_chunks_host, make_chunks
 from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
                    train_losses_windows)
-from .loops import train_chunk, train_chunks, train_epoch
+from .loops import train_chunk, train_chunks, train_epoch, validate
 from .monitor import TrainMonitor
+from .moteval import MotEvaluator, MotStore, mot_dist_host, mot_events_host, mot_overall
 from .online import FeatureSpec, OnlineTracker, online_features_host
 from .optim import BucketAdam
 from .track_mpnn import SparseAttention, TrackMPNN
@@ -21,4 +22,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'train_losses_windows', 'train_chunk', 'train_chunks', 'TrainBatch', 'LossWindows', 'build_train_batch',
            'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor', 'BucketAdam',
            'make_chunks', 'DetectionStore', 'ChunkSampler', 'DrawnChunks', 'draw_chunks_host', 'train_epoch', 'AllChunksSkipped',
-           'OnlineTracker', 'FeatureSpec', 'online_features_host']
+           'OnlineTracker', 'FeatureSpec', 'online_features_host', 'MotEvaluator', 'MotStore', 'mot_events_host', 'mot_dist_host',
+           'mot_overall', 'validate']

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -115,12 +115,19 @@ class CChunkDraw(C.Structure):
                                            'count', 'flags', 'offsets', 'X', 'y')])
 
 
+class CMotStore(C.Structure):
+    """struct tmpnn_mot_store (include/tmpnn.h): both sides of S sequences sorted by frame, for the MOT evaluation."""
+    _fields_ = ([('S', C.c_int32), ('reserved', C.c_int32)] + [(f, C.c_int64) for f in ('n_gt', 'n_det', 'n_off', 'n_obj')]
+                + [(f, c_void_p) for f in ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')])
+
+
 _DGP = C.POINTER(CDGraph)
 _MPP = C.POINTER(CMpParams)
 _TRP = C.POINTER(CTrackRows)
 _LWP = C.POINTER(CLossWindows)
 _TBP = C.POINTER(CTrainBuild)
 _CDP = C.POINTER(CChunkDraw)
+_MSP = C.POINTER(CMotStore)
 
 # name -> (restype, argtypes); must mirror include/tmpnn.h (tests/test_abi.py cross-checks the names)
 _SIGNATURES = {
@@ -239,6 +246,10 @@ _SIGNATURES = {
     'tmpnn_chunk_draw_fill': (c_int, [_CDP, c_void_p]),
     'tmpnn_online_features': (c_int, [c_int] * 8 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p]),
+    'tmpnn_mot_max_per_frame': (c_int, []),
+    'tmpnn_mot_events_ws': (c_size_t, [c_int, C.c_int64, C.c_int64]),
+    'tmpnn_mot_events': (c_int, [_MSP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'tmpnn_mot_dist': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

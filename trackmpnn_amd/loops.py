@@ -10,6 +10,8 @@
                     chunks -> device batch build -> train_chunks -> optimizer step
     infer_sequence  reference/infer.py:35-87    one sequence: per timestep update_graph(mode='test', greedy or Hungarian)
                                                 -> model -> decode_tracks (track finalisation + rolling-window deletion)
+    validate        reference/train.py:177-282  the validation pass: infer_sequence over every sequence, then the CLEAR-MOT
+                                                counts of all tracks in one launch (moteval.MotEvaluator) and one host read
 
 Same order of operations, same arguments' meaning and the same results as the reference's drivers (which cannot be imported:
 they parse the command line at import) -- but the graph, the hidden state, the losses' inputs and the tracks stay
@@ -273,6 +275,47 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
         y_out[:, 1] = tg.tracks()[:y_out.shape[0]]
         st.stop('decode')
     return y_out, ncalls, edge_iters
+
+
+def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
+             tp_classifier: bool = True) -> Dict:
+    """The validation pass of train.py:177-282 up to the MOTA that chooses the checkpoint (train.py:300): the model in eval
+    mode for the pass (its mode is restored afterwards), infer_sequence over every sequence, all tracks handed to
+    `evaluator.evaluate` and read once.  sequences: one dict per sequence with 'X' [1, ND, F] and 'y' [1, ND, 2] as
+    infer_sequence takes them; `evaluator`: a MotEvaluator built over the same sequences in the same order (its store holds
+    their frames, boxes and ground truth).  A sequence without detections or without ground truth is skipped as
+    train.py:190-192 skips it, and so is one in which no graph could be initialised (train.py:201-202): it runs no
+    inference and has None in `per_sequence`.
+
+    Returns {'mota', 'motp', 'motas', 'per_sequence'} and the overall counts (objects, predictions, matches, switches,
+    false_positives, misses, frames, dist_sum, recall, precision): the overall figures are the ratios of the summed counts
+    (train.py:282), `motas` the MOTA of every sequence that took part (train.py:281), as fractions -- train.py prints 100 x.
+    Validation-mode F1 and mAP are not computed."""
+    store = evaluator.store
+    if len(sequences) != store.S:
+        raise ValueError(f'validate: {len(sequences)} sequences, the evaluator holds {store.S}')
+    was_training = model.training
+    model.eval()
+    try:
+        tracks = []
+        for s, q in enumerate(sequences):
+            X, y = q['X'], q['y']
+            if int(y.shape[1]) != int(store.seq[s, 3]):
+                raise ValueError(f'validate: sequence {s} has {int(y.shape[1])} detections, the evaluator holds {int(store.seq[s, 3])}')
+            if store.empty[s]:
+                tracks.append(None)
+                continue
+            y_out, ncalls, _ = infer_sequence(model, X, y, cur_win_size, ret_win_size, use_hungarian, evaluator.device,
+                                              tp_classifier)
+            tracks.append(y_out[:, 1] if ncalls > 0 else None)
+        evaluator.evaluate(tracks)
+        per, overall = evaluator.read()
+    finally:
+        model.train(was_training)
+    out = dict(overall)
+    out['motas'] = [p['mota'] for p in per if p is not None]
+    out['per_sequence'] = per
+    return out
 
 
 def _fast_greedy(model, use_hungarian: bool, tp_classifier: bool, stages):

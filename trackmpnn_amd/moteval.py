@@ -1,0 +1,371 @@
+"""CLEAR-MOT counts of a set of tracks against the ground truth (reference utils/metrics.py:7-61, train.py:264-282).
+
+    mot_events_host     the rule, in numpy + scipy: one sequence in, the counts out.  It is the DEFINITION the device kernel
+                        must equal (counts exactly, distances and their sum bit for bit).
+    mot_dist_host       the float64 distance matrix of two box lists (1 - IoU, NaN above 0.5)
+    mot_overall         the figures of several sequences: ratios of the summed counts
+    MotStore            the per-sequence data that do not change between epochs (frames, boxes, GT ids), sorted by frame,
+                        packed over the sequences
+    MotEvaluator        the store on the device + `evaluate(tracks)` (one launch of tmpnn_mot_events, csrc/moteval.hip, one
+                        workgroup per sequence) + `read()` (the one device -> host copy)
+
+The reference scores with py-motmetrics (a pandas accumulator fed one frame at a time).  That package is not a dependency
+of this library and is not pinned by any fixture: the rule below restates MOTAccumulator.update and iou_matrix as they are
+in py-motmetrics >= 1.2 and as metrics.py calls them ("unpinnable").
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_PER_FRAME = 256            # GT rows / kept hypotheses of one frame the device solver takes (csrc/moteval.hip MOT_MAX)
+COUNT_KEYS = ('objects', 'predictions', 'matches', 'switches', 'false_positives', 'misses', 'frames')
+FLAG_LIMIT, FLAG_DUPLICATE, FLAG_STORE, FLAG_SOLVER = 1, 2, 4, 8
+_FLAG_TEXT = {FLAG_LIMIT: f'a frame has more than {MAX_PER_FRAME} GT rows or kept hypotheses',
+              FLAG_DUPLICATE: 'a hypothesis id occurs twice in one frame',
+              FLAG_STORE: 'the store is inconsistent (an offset, a permutation entry or an object id out of range)',
+              FLAG_SOLVER: 'the assignment solver found no augmenting path'}
+
+
+def _boxes(b, what: str) -> np.ndarray:
+    b = np.ascontiguousarray(np.asarray(b, dtype=np.float32)).reshape(-1, 4) if np.size(b) else np.zeros((0, 4), np.float32)
+    return b
+
+
+def _ints(a, what: str, n: Optional[int] = None) -> np.ndarray:
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f'{what}: integer values expected, got {a.dtype}')
+    a = a.astype(np.int64).reshape(-1)
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f'{what}: {a.shape[0]} entries for {n} rows')
+    return a
+
+
+def mot_dist_host(box_o, box_h) -> np.ndarray:
+    """[len(box_o), len(box_h)] float64: 1 - IoU of x1 y1 x2 y2 boxes, NaN where it exceeds 0.5 (and where it is 0 / 0).
+    Width and height are formed in float32, everything after that in float64 -- metrics.py:36-40 hands float32
+    (x, y, w, h) rows to iou_matrix(max_iou=0.5), which works in float64."""
+    bo, bh = _boxes(box_o, 'box_o'), _boxes(box_h, 'box_h')
+    tl_o, tl_h = bo[:, :2].astype(np.float64), bh[:, :2].astype(np.float64)
+    wh_o, wh_h = (bo[:, 2:] - bo[:, :2]).astype(np.float64), (bh[:, 2:] - bh[:, :2]).astype(np.float64)
+    br_o, br_h = tl_o + wh_o, tl_h + wh_h
+    with np.errstate(invalid='ignore', divide='ignore'):
+        iwh = np.maximum(np.minimum(br_o[:, None, :], br_h[None, :, :]) - np.maximum(tl_o[:, None, :], tl_h[None, :, :]), 0)
+        inter = iwh[..., 0] * iwh[..., 1]
+        union = ((wh_o[:, 0] * wh_o[:, 1])[:, None] + (wh_h[:, 0] * wh_h[:, 1])[None, :]) - inter
+        d = 1.0 - inter / union
+        d[d > 0.5] = np.nan
+    return d
+
+
+def _derived(c: Dict) -> Dict:
+    def ratio(a, b):
+        return float(a) / float(b) if b else float('nan')
+    c['mota'] = 1.0 - ratio(c['misses'] + c['false_positives'] + c['switches'], c['objects'])
+    c['motp'] = ratio(c['dist_sum'], c['matches'])
+    c['recall'] = ratio(c['matches'], c['objects'])
+    c['precision'] = ratio(c['matches'], c['predictions'])
+    return c
+
+
+def mot_overall(per_sequence: Sequence[Dict]) -> Dict:
+    """The figures over several sequences: ratios of the SUMMED counts (compute_many(..., generate_overall=True),
+    train.py:281-282), dist_sum added in the order of the list."""
+    c = {k: 0 for k in COUNT_KEYS}
+    c['dist_sum'] = 0.0
+    for r in per_sequence:
+        for k in COUNT_KEYS:
+            c[k] += int(r[k])
+        c['dist_sum'] += float(r['dist_sum'])
+    return _derived(c)
+
+
+def _frame_range(det_frame: np.ndarray, gt_frame: np.ndarray):
+    """(first frame, number of frames) of both sides together, every row counted (metrics.py:19-27); (0, 0) without rows."""
+    both = np.concatenate([det_frame, gt_frame])
+    if both.size == 0:
+        return 0, 0
+    return int(both.min()), int(both.max()) - int(both.min()) + 1
+
+
+def _check_unique(ids: np.ndarray, t: int, what: str):
+    if np.unique(ids).shape[0] != ids.shape[0]:
+        raise ValueError(f'mot_events: {what} id occurs twice in frame {t}')
+
+
+def mot_events_host(det_frame, det_box, tracks, gt_frame, gt_track, gt_box) -> Dict:
+    """The CLEAR-MOT events of one sequence.  det_box / gt_box float32 [n, 4] (x1 y1 x2 y2); tracks = y_out[:, 1] in arrival
+    order; rows with tracks < 0 or gt_track < 0 take no part (metrics.py:28,32).  Per frame of the common range: keep the
+    correspondences of the previous frame (step 1), assign the rest optimally (step 2), count."""
+    from scipy.optimize import linear_sum_assignment
+    det_frame, gt_frame = _ints(det_frame, 'det_frame'), _ints(gt_frame, 'gt_frame')
+    tracks, gt_track = _ints(tracks, 'tracks', det_frame.shape[0]), _ints(gt_track, 'gt_track', gt_frame.shape[0])
+    det_box, gt_box = _boxes(det_box, 'det_box'), _boxes(gt_box, 'gt_box')
+    if det_box.shape[0] != det_frame.shape[0] or gt_box.shape[0] != gt_frame.shape[0]:
+        raise ValueError('mot_events: one box per row expected')
+    t0, nframes = _frame_range(det_frame, gt_frame)
+    c = {k: 0 for k in COUNT_KEYS}
+    c['frames'] = nframes
+    dist_sum = 0.0
+    m: Dict[int, int] = {}
+    last_match: Dict[int, int] = {}
+    for t in range(t0, t0 + nframes):
+        orow = np.where((gt_frame == t) & (gt_track >= 0))[0]
+        hrow = np.where((det_frame == t) & (tracks >= 0))[0]
+        oids, hids = gt_track[orow], tracks[hrow]
+        _check_unique(oids, t, 'a GT')
+        _check_unique(hids, t, 'a hypothesis')
+        nO, nH = oids.shape[0], hids.shape[0]
+        c['objects'] += nO
+        c['predictions'] += nH
+        matched_d = [None] * nO
+        hmask = np.zeros(nH, dtype=bool)
+        if nO and nH:
+            d = mot_dist_host(gt_box[orow], det_box[hrow])
+            omask = np.zeros(nO, dtype=bool)
+            for i in range(nO):                                   # step 1
+                o = int(oids[i])
+                if o not in m or last_match.get(o) != t - 1:
+                    continue
+                js = np.where(~hmask & (hids == m[o]))[0]
+                if js.shape[0] == 0:
+                    continue
+                j = int(js[0])
+                if np.isfinite(d[i, j]):
+                    omask[i] = hmask[j] = True
+                    matched_d[i] = float(d[i, j])
+                    last_match[o] = t
+                    c['matches'] += 1
+            d2 = d.copy()                                         # step 2
+            d2[omask, :] = np.nan
+            d2[:, hmask] = np.nan
+            fin = np.isfinite(d2)
+            if fin.any():
+                L = 2 * min(nO, nH) * (d2[fin].max() + 1) + 1
+                cost = np.where(fin, d2, L)
+                for i, j in zip(*linear_sum_assignment(cost)):
+                    if not fin[i, j]:
+                        continue
+                    o, h = int(oids[i]), int(hids[j])
+                    if o in m and m[o] != h:
+                        c['switches'] += 1
+                    c['matches'] += 1
+                    matched_d[i] = float(d2[i, j])
+                    hmask[j] = True
+                    m[o] = h
+                    last_match[o] = t
+        for i in range(nO):
+            if matched_d[i] is None:
+                c['misses'] += 1
+            else:
+                dist_sum += matched_d[i]
+        c['false_positives'] += int(nH - hmask.sum())
+    c['dist_sum'] = float(dist_sum)
+    return _derived(c)
+
+
+def synth_mot_sequence(seed: int, frames: int, objects: int = 6, p_absent: float = 0.05, p_miss: float = 0.15,
+                       stray_rate: float = 0.18, p_swap: float = 0.06, p_untracked: float = 0.05, t0: int = 0,
+                       shuffle_gt: bool = True) -> Dict:
+    """A synthetic sequence for the tests and tools/mot_eval_bench.py: `objects` boxes drifting over a 1000 x 1000 field,
+    every one absent from the ground truth of a frame with p_absent and undetected with p_miss; detections are jittered
+    boxes that carry the object's hypothesis id (two ids swap or one is renewed with p_swap per frame; -1 with
+    p_untracked); stray detections with fresh ids at `stray_rate` per frame.  GT ids are not dense and the GT rows come
+    in shuffled order.  Returns the dict MotEvaluator takes plus 'tracks'."""
+    rng = np.random.default_rng(seed)
+    pos, vel = rng.uniform(100, 900, (objects, 2)), rng.uniform(-4, 4, (objects, 2))
+    size = rng.uniform(30, 80, (objects, 2))
+    hyp = np.arange(objects) + 100
+    nxt = 100 + objects
+    gt, det = [], []
+    for t in range(frames):
+        if objects >= 2 and rng.random() < p_swap:
+            a, b = rng.choice(objects, 2, replace=False)
+            hyp[a], hyp[b] = hyp[b], hyp[a]
+        if objects and rng.random() < p_swap:
+            hyp[rng.integers(objects)] = nxt
+            nxt += 1
+        for o in range(objects):
+            c = pos[o] + vel[o] * t
+            box = np.concatenate([c - size[o] / 2, c + size[o] / 2])
+            if rng.random() >= p_absent:
+                gt.append((t0 + t, 3 * o + 1, *box))
+            if rng.random() >= p_miss:
+                det.append((t0 + t, hyp[o] if rng.random() >= p_untracked else -1, *(box + rng.normal(0, 2, 4))))
+        for _ in range(rng.poisson(stray_rate)):
+            c, sz = rng.uniform(100, 900, 2), rng.uniform(30, 80, 2)
+            det.append((t0 + t, nxt, *np.concatenate([c - sz / 2, c + sz / 2])))
+            nxt += 1
+    gt = np.asarray(gt, np.float64).reshape(-1, 6)
+    det = np.asarray(det, np.float64).reshape(-1, 6)
+    if shuffle_gt:
+        gt = gt[rng.permutation(gt.shape[0])]
+    return {'det_frame': det[:, 0].astype(np.int64), 'det_box': det[:, 2:].astype(np.float32), 'tracks': det[:, 1].astype(np.int64),
+            'gt_frame': gt[:, 0].astype(np.int64), 'gt_track': gt[:, 1].astype(np.int64), 'gt_box': gt[:, 2:].astype(np.float32)}
+
+
+class MotStore:
+    """What the evaluator keeps of S sequences, packed: rows of both sides sorted STABLY by frame, per-frame offsets over the
+    common frame range (relative to the sequence's first row), GT ids renumbered densely per sequence (ascending original
+    id), the permutation sorted position -> arrival index of the detections, float32 boxes.  GT rows with a negative track
+    are dropped; a GT id twice in a frame raises ValueError.  All host numpy arrays:
+
+        seq      int64 [S, 8]   gt_base, n_gt, det_base, n_det, off_base, n_frames, obj_base, n_obj
+        gt_off   int32 [n_off]  per sequence n_frames + 1 entries; det_off likewise
+        gt_id    int32 [n_gt]   gt_box float32 [n_gt, 4]   det_box float32 [n_det, 4]   det_perm int32 [n_det]
+        t0       first frame of each sequence's range (host only)
+    """
+
+    def __init__(self, sequences: Sequence[Dict]):
+        S = len(sequences)
+        self.seq = np.zeros((S, 8), np.int64)
+        self.t0: List[int] = []
+        self.empty: List[bool] = []
+        self.gt_ids: List[np.ndarray] = []                        # dense id -> original id, per sequence
+        gt_off, det_off, gt_id, gt_box, det_box, det_perm = [], [], [], [], [], []
+        g_base = d_base = o_base = f_base = 0
+        for s, q in enumerate(sequences):
+            det_frame, gt_frame = _ints(q['det_frame'], 'det_frame'), _ints(q['gt_frame'], 'gt_frame')
+            gt_track = _ints(q['gt_track'], 'gt_track', gt_frame.shape[0])
+            db, gb = _boxes(q['det_box'], 'det_box'), _boxes(q['gt_box'], 'gt_box')
+            if db.shape[0] != det_frame.shape[0] or gb.shape[0] != gt_frame.shape[0]:
+                raise ValueError(f'MotStore: sequence {s}: one box per row expected')
+            t0, nf = _frame_range(det_frame, gt_frame)
+            self.empty.append(det_frame.shape[0] == 0 or gt_frame.shape[0] == 0)
+            if nf >= 2 ** 31 - 1 or max(det_frame.shape[0], gt_frame.shape[0]) >= 2 ** 31 - 1:
+                raise ValueError(f'MotStore: sequence {s} is beyond int32')
+            keep = np.where(gt_track >= 0)[0]
+            go = keep[np.argsort(gt_frame[keep], kind='stable')]
+            do = np.argsort(det_frame, kind='stable')
+            uniq, dense = np.unique(gt_track[go], return_inverse=True)
+            if uniq.size and uniq.max() >= 2 ** 31:
+                raise ValueError(f'MotStore: sequence {s}: ids are int32')
+            gf, df = gt_frame[go], det_frame[do]
+            key = gf * (int(uniq.shape[0]) + 1) + dense.reshape(-1)
+            if np.unique(key).shape[0] != key.shape[0]:
+                k, cnt = np.unique(key, return_counts=True)
+                raise ValueError(f'MotStore: sequence {s}: a GT id occurs twice in frame {int(k[cnt > 1][0] // (uniq.shape[0] + 1))}')
+            edges = np.arange(t0, t0 + nf + 1)
+            gt_off.append(np.searchsorted(gf, edges, side='left').astype(np.int32))
+            det_off.append(np.searchsorted(df, edges, side='left').astype(np.int32))
+            gt_id.append(dense.reshape(-1).astype(np.int32))
+            gt_box.append(gb[go])
+            det_box.append(db[do])
+            det_perm.append(do.astype(np.int32))
+            self.seq[s] = (g_base, go.shape[0], d_base, do.shape[0], f_base, nf, o_base, uniq.shape[0])
+            self.t0.append(t0)
+            self.gt_ids.append(uniq)
+            g_base += go.shape[0]
+            d_base += do.shape[0]
+            f_base += nf + 1
+            o_base += uniq.shape[0]
+
+        def cat(parts, dtype, tail=()):
+            return np.ascontiguousarray(np.concatenate(parts).astype(dtype)) if parts else np.zeros((0,) + tail, dtype)
+        self.S = S
+        self.gt_off, self.det_off = cat(gt_off, np.int32), cat(det_off, np.int32)
+        self.gt_id, self.det_perm = cat(gt_id, np.int32), cat(det_perm, np.int32)
+        self.gt_box, self.det_box = cat(gt_box, np.float32, (4,)).reshape(-1, 4), cat(det_box, np.float32, (4,)).reshape(-1, 4)
+        self.n_gt, self.n_det, self.n_off, self.n_obj = g_base, d_base, f_base, o_base
+
+
+RECORD_WORDS = 9               # struct tmpnn_mot_record: seven int64 counts, the flag word, dist_sum (double)
+
+
+class MotEvaluator:
+    """The MOT evaluation of S sequences on the device.  sequences: one dict per sequence with det_frame, det_box, gt_frame,
+    gt_track, gt_box (host arrays or tensors; they are the same in every epoch -- only the tracks change).  The store is
+    built on the host and uploaded once.
+
+        ev.evaluate(tracks)   tracks: per sequence an int tensor / array [n_det] in arrival order, host or device (None:
+                              the sequence takes no part in this evaluation).  One packed upload at the most, one launch, no
+                              host wait.
+        ev.read()             the one device -> host copy: (per_sequence, overall); per_sequence[i] is the dict of
+                              mot_events_host (None for a sequence left out), overall the ratios of the summed counts.
+                              RuntimeError when a sequence's flag word is set (check=False: no error, every dict has
+                              the sequence's 'flag' word instead; a flagged sequence's counts stop at the flagged frame).
+    """
+
+    def __init__(self, sequences: Sequence[Dict], device='cuda:0'):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError(f'MotEvaluator on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a '
+                               'cuda device, or score on the host with mot_events_host')
+        self.device = dev
+        self.store = st = MotStore(sequences)
+        self._seq_host = np.ascontiguousarray(st.seq)
+        up = lambda a: torch.from_numpy(a).to(dev)
+        self._t = {k: up(getattr(st, k)) for k in ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')}
+        self._c = _lib.CMotStore(st.S, 0, st.n_gt, st.n_det, st.n_off, st.n_obj, *[self._t[k].data_ptr() or None for k in
+                            ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')])
+        lib = _lib.load()
+        self._ws_bytes = int(lib.tmpnn_mot_events_ws(st.S, st.n_obj, st.n_det))
+        self._ws = torch.empty(max(self._ws_bytes, 8), dtype=torch.uint8, device=dev)
+        self._tracks = torch.empty(max(st.n_det, 1), dtype=torch.int32, device=dev)
+        self._out = torch.zeros(max(st.S, 1), RECORD_WORDS, dtype=torch.int64, device=dev)
+        self._left_out = [False] * st.S
+        self._pending = False
+
+    def evaluate(self, tracks: Sequence) -> None:
+        st = self.store
+        if len(tracks) != st.S:
+            raise ValueError(f'MotEvaluator.evaluate: {len(tracks)} track arrays for {st.S} sequences')
+        host = np.full(st.n_det, -1, np.int32)
+        on_device = []
+        left_out = []
+        host_used = False
+        for s, tr in enumerate(tracks):
+            base, n = int(st.seq[s, 2]), int(st.seq[s, 3])
+            left_out.append(tr is None)
+            if tr is None:
+                host_used |= n > 0                                  # (its slice is filled with -1)
+                continue
+            if isinstance(tr, torch.Tensor) and tr.is_cuda:
+                if tr.dtype.is_floating_point or tr.numel() != n:
+                    raise ValueError(f'MotEvaluator.evaluate: sequence {s}: an int tensor of {n} tracks expected')
+                on_device.append((base, n, tr))
+            else:
+                a = _ints(tr, f'MotEvaluator.evaluate: sequence {s}: tracks', n)
+                if a.size and (a.max() >= 2 ** 31 or a.min() < -2 ** 31):
+                    raise ValueError(f'MotEvaluator.evaluate: sequence {s}: track ids are int32')
+                host[base:base + n] = a
+                host_used |= n > 0
+        if host_used:
+            self._tracks[:st.n_det].copy_(torch.from_numpy(host), non_blocking=True)       # the one packed upload
+        for base, n, tr in on_device:
+            self._tracks[base:base + n].copy_(tr.reshape(-1))
+        _lib.call('tmpnn_mot_events', C.byref(self._c), self._seq_host.ctypes.data, self._tracks.data_ptr(), self._ws.data_ptr(),
+                  self._ws_bytes, self._out.data_ptr(), _lib.raw_stream(self.device))
+        self._left_out = left_out
+        self._pending = True
+
+    def read(self, check: bool = True):
+        if not self._pending:
+            raise RuntimeError('MotEvaluator.read: no evaluation has been enqueued')
+        rec = self._out.cpu().numpy()                               # (the one device -> host copy; it waits for the launch)
+        dsum = rec.view(np.float64)[:, 8]
+        bad = [(s, int(rec[s, 7])) for s in range(self.store.S) if rec[s, 7] != 0 and not self._left_out[s]]
+        if bad and check:
+            msg = '; '.join(f'sequence {s}, frame {self.store.t0[s] + (f >> 8) - 1}: '
+                            + ', '.join(txt for bit, txt in _FLAG_TEXT.items() if f & bit) for s, f in bad)
+            raise RuntimeError(f'MotEvaluator.read: {msg}')
+        per = []
+        for s in range(self.store.S):
+            if self._left_out[s]:
+                per.append(None)
+                continue
+            c = {k: int(rec[s, i]) for i, k in enumerate(COUNT_KEYS)}
+            c['dist_sum'] = float(dsum[s])
+            c = _derived(c)
+            if not check:
+                c['flag'] = int(rec[s, 7])
+            per.append(c)
+        return per, mot_overall([p for p in per if p is not None])
