@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define TMPNN_ABI_VERSION 12 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
+#define TMPNN_ABI_VERSION 13 /* 2: struct tmpnn_graph gained seg_plan (round 4); 3: win_plan (round 5); 4 (round 6, frozen): the
                                exported set is what a default run can reach (80 entry points: 15 superseded or internal ones
                                left it), tmpnn_input_tf_* take x_rows, + tmpnn_segsum_fwd_live, tmpnn_bce_logits_*;
                                5: + struct tmpnn_loss_windows, tmpnn_train_losses_win_* (entry points added, none changed);
@@ -50,7 +50,9 @@ extern "C" {
                                    planes when gate_plane == 0 (same arguments; calls that pass planes are unchanged);
                                11: + tmpnn_online_features (entry point added, none changed);
                                12: + struct tmpnn_mot_store, struct tmpnn_mot_record, tmpnn_mot_events, tmpnn_mot_events_ws,
-                                   tmpnn_mot_dist, tmpnn_mot_max_per_frame (entry points added, none changed) */
+                                   tmpnn_mot_dist, tmpnn_mot_max_per_frame (entry points added, none changed);
+                               13: + struct tmpnn_map_store, struct tmpnn_map_record, tmpnn_map_best, tmpnn_map_eval,
+                                   tmpnn_map_eval_ws, tmpnn_map_tile (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1003,6 +1005,63 @@ int tmpnn_mot_events(const tmpnn_mot_store* st, const int64_t* seq_host, const i
 /* out [na][nb] float64 = 1 - IoU of box_a[i], box_b[j] (x1 y1 x2 y2 float32, 16-byte aligned), NaN where it exceeds 0.5 or is
  * 0 / 0: width and height in float32, the rest in float64, bit-equal to trackmpnn_amd.moteval.mot_dist_host. */
 int tmpnn_mot_dist(const float* box_a, int na, const float* box_b, int nb, double* out, tmpnn_stream stream);
+
+/* ======================================================================================================
+ * Validation mAP (trackmpnn_amd.mapeval.MapEvaluator): the mean average precision of the detections that were given a track,
+ * over S sequences, in two launches (csrc/mapeval.hip) -- what the reference's validation pass computes on the host
+ * (utils/metrics.py:93-229, train.py:272-273,286).  The rule is trackmpnn_amd.mapeval.map_host; counts are equal to it, ap bit
+ * for bit.
+ *
+ * The store holds what does not change between evaluations (all device memory, built by trackmpnn_amd.mapeval.MapStore).  GT rows
+ * are sorted stably by (class, sequence, frame); a GROUP is the GT rows of one (sequence, frame, class), a range of that order;
+ * detections stay in arrival order, packed over the sequences.
+ *     gt_box     [n_gt][4] float32  x1 y1 x2 y2 (16-byte aligned)     gt_seq [n_gt] int32  the row's sequence
+ *     cls_gt_off [C + 1] int32      the GT rows of a class
+ *     grp_off    [n_grp + 1] int32  the GT rows of a group
+ *     det_box    [n_det][4] float32 (16-byte aligned)
+ *     det_grp    [n_det] int32      the group of the detection's (sequence, frame, class), -1: there is none
+ *     det_best   [n_det] int32      what tmpnn_map_best wrote
+ *     cls_off    [C + 1] int32, order [n_live] int32   per class its detections in frames that have GT rows, by descending
+ *                                   score, ties by (sequence, arrival index)
+ *     claim_off  [n_gt + 1] int32, claim_det [n_claim] int32   per GT row the detections with det_best == row, arrival order
+ * tracks [n_det] int32: y_out[:, 1] of every sequence in arrival order, negative = no track (a sequence that takes no part: all
+ * negative); part [S] int32: 1 where the sequence takes part (its GT rows count), else 0.
+ * ====================================================================================================== */
+typedef struct tmpnn_map_store {
+    int32_t S, C;
+    int64_t n_gt, n_det, n_grp, n_live, n_claim; /* the lengths of the arrays below; all < 2^31 */
+    const float* gt_box;
+    const int32_t* gt_seq;
+    const int32_t* cls_gt_off;
+    const int32_t* grp_off;
+    const float* det_box;
+    const int32_t* det_grp;
+    const int32_t* det_best;
+    const int32_t* cls_off;
+    const int32_t* order;
+    const int32_t* claim_off;
+    const int32_t* claim_det;
+} tmpnn_map_store;
+/* One per class.  annotations: the class's GT rows over the sequences that take part (0: the class is not one of this
+ * evaluation); kept: its kept detections in frames with GT rows; flag: 0, or 1 = the store is inconsistent (an offset or an
+ * index out of range: nothing was read outside the arrays; ap is 0 then). */
+typedef struct tmpnn_map_record {
+    double ap;
+    int64_t annotations, kept, true_positives, flag;
+} tmpnn_map_record;
+/* entries of a class's sorted list that one step of the sweeps takes (the carries cross at its multiples) */
+int tmpnn_map_tile(void);
+/* best [n_det]: per detection the index (in the store's GT order) of the GT row of its group with the largest IoU in the
+ * "+1" form of utils/misc.py:4-22, float64 from the float32 boxes, the FIRST maximum (a NaN counts as the maximum, as in
+ * np.argmax); -1 where det_grp is -1, where the maximum is below 0.5 or NaN; -2 where det_grp or the group's offsets are out of
+ * range.  Equal to trackmpnn_amd.mapeval.map_best_host per group.  Reads gt_box, grp_off, det_box, det_grp only. */
+int tmpnn_map_best(const tmpnn_map_store* st, int32_t* best, tmpnn_stream stream);
+/* bytes: the true-positive marks, the status of the claim lists, tp_k and the precision / envelope of every list entry */
+size_t tmpnn_map_eval_ws(int64_t n_gt, int64_t n_det, int64_t n_live);
+/* Two launches (one thread per GT row: the first kept claimant; one workgroup per class: three tiled sweeps of its sorted
+ * list), out [C].  ws: 16-byte aligned, tmpnn_map_eval_ws bytes; its contents need not survive between calls. */
+int tmpnn_map_eval(const tmpnn_map_store* st, const int32_t* tracks, const int32_t* part, void* ws, size_t ws_bytes,
+                   tmpnn_map_record* out, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Wide cells (H = 128 / 256, diff messages; BASELINE.json C5) as LDS-tiled GEMMs on bf16x6 split products

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMPNN_LIB_PATH') or os.path.join(_HERE, 'lib', 'libtmpnn.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tmpnn.h')
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 c_int = C.c_int
 c_void_p = C.c_void_p
@@ -121,6 +121,13 @@ class CMotStore(C.Structure):
                 + [(f, c_void_p) for f in ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')])
 
 
+class CMapStore(C.Structure):
+    """struct tmpnn_map_store (include/tmpnn.h): GT rows by (class, sequence, frame), claim lists and per-class order, for mAP."""
+    _fields_ = ([('S', C.c_int32), ('C', C.c_int32)] + [(f, C.c_int64) for f in ('n_gt', 'n_det', 'n_grp', 'n_live', 'n_claim')]
+                + [(f, c_void_p) for f in ('gt_box', 'gt_seq', 'cls_gt_off', 'grp_off', 'det_box', 'det_grp', 'det_best', 'cls_off',
+                                           'order', 'claim_off', 'claim_det')])
+
+
 _DGP = C.POINTER(CDGraph)
 _MPP = C.POINTER(CMpParams)
 _TRP = C.POINTER(CTrackRows)
@@ -128,6 +135,7 @@ _LWP = C.POINTER(CLossWindows)
 _TBP = C.POINTER(CTrainBuild)
 _CDP = C.POINTER(CChunkDraw)
 _MSP = C.POINTER(CMotStore)
+_MAP = C.POINTER(CMapStore)
 
 # name -> (restype, argtypes); must mirror include/tmpnn.h (tests/test_abi.py cross-checks the names)
 _SIGNATURES = {
@@ -250,6 +258,10 @@ _SIGNATURES = {
     'tmpnn_mot_events_ws': (c_size_t, [c_int, C.c_int64, C.c_int64]),
     'tmpnn_mot_events': (c_int, [_MSP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     'tmpnn_mot_dist': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'tmpnn_map_tile': (c_int, []),
+    'tmpnn_map_best': (c_int, [_MAP, c_void_p, c_void_p]),
+    'tmpnn_map_eval_ws': (c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    'tmpnn_map_eval': (c_int, [_MAP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

@@ -1,0 +1,317 @@
+// Mean average precision of the kept tracks' detections against the ground truth, on the device (tmpnn_map_best, tmpnn_map_eval;
+// include/tmpnn.h; host definition: trackmpnn_amd.mapeval.map_host).  The reference collects the kept detections of every
+// validation sequence on the host and scores them per class (utils/metrics.py:93-229, train.py:272-273,286).
+//
+// What changes between two evaluations is only which detections are KEPT (tracks >= 0, sequence taking part); boxes, scores and
+// classes stay.  So the store fixes, once:
+//   best      per detection the GT row of largest "+1" IoU among the GT rows of its image and class (first maximum; -1 below 0.5,
+//             for NaN and where there is no such row) -- k_map_best, float64 from the float32 boxes, every operation a single
+//             correctly rounded IEEE operation in numpy's order (contraction is OFF for this file), so `best` equals the host's;
+//   claims    per GT row the detections whose best row it is, in arrival order;
+//   order     per class its detections in images with ground truth, by descending score, ties in natural order.
+// A kept detection is a true positive iff it is the FIRST KEPT entry of its best row's claim list.
+//
+// An evaluation is two launches, whatever the size:
+//   k_map_mark    one thread per GT row walks the row's claim list and marks its first kept claimant;
+//   k_map_class   one workgroup per class sweeps the class's sorted list in tiles of MAP_TILE entries, three times:
+//                   ascending   the running counts k (kept) and tp_k (true positives), precision tp_k / k;
+//                   descending  the precision envelope (suffix maximum), carried from tile to tile;
+//                   ascending   the terms (tp_k / N - (tp_k - 1) / N) * env_k of the true positives, added by ONE lane in
+//                               ascending k (bit-equal to the host's running sum),
+//                 and counts the class's GT rows over the sequences that take part (N).
+// Workgroups never wait on each other (no look-back, no spinning, no cooperative launch) and nothing is atomic.
+//
+// Every index read from the store is checked against the store's totals before it is used; an entry out of range sets the flag
+// of the class's record (for a claim list: of the class of its GT row) and nothing is read or written outside the arrays.
+#pragma clang fp contract(off)
+#include "common.h"
+
+using namespace tmpnn;
+
+namespace {
+
+constexpr int MAP_TILE = 256;                // entries of the sorted list per sweep step = threads of k_map_class
+constexpr int MAP_WAVES = MAP_TILE / 64;
+constexpr int MAP_FLAG_STORE = 1;
+
+// "+1" IoU of two x1 y1 x2 y2 boxes (utils/misc.py:4-22; host: mapeval.map_iou_host, the same operations in the same order)
+__device__ __forceinline__ double map_iou(float4 d, float4 g) {
+    const double x11 = d.x, y11 = d.y, x12 = d.z, y12 = d.w, x21 = g.x, y21 = g.y, x22 = g.z, y22 = g.w;
+    const double xA = x11 > x21 ? x11 : x21, yA = y11 > y21 ? y11 : y21;
+    const double xB = x12 < x22 ? x12 : x22, yB = y12 < y22 ? y12 : y22;
+    const double w = (xB - xA) + 1.0, h = (yB - yA) + 1.0;
+    const double inter = (w > 0.0 ? w : 0.0) * (h > 0.0 ? h : 0.0);
+    const double area_d = ((x12 - x11) + 1.0) * ((y12 - y11) + 1.0);
+    const double area_g = ((x22 - x21) + 1.0) * ((y22 - y21) + 1.0);
+    return inter / ((area_d + area_g) - inter);
+}
+
+constexpr int MB_THREADS = 256;
+__global__ __launch_bounds__(MB_THREADS) void k_map_best(tmpnn_map_store st, int32_t* __restrict__ best) {
+    const float4* det_box = reinterpret_cast<const float4*>(st.det_box);
+    const float4* gt_box = reinterpret_cast<const float4*>(st.gt_box);
+    const int64_t stride = (int64_t)gridDim.x * MB_THREADS;
+    for (int64_t d = (int64_t)blockIdx.x * MB_THREADS + threadIdx.x; d < st.n_det; d += stride) {
+        const int g = st.det_grp[d];
+        int r = -1;
+        if (g >= 0) {
+            r = -2;                                               // (until the group's range has been checked)
+            if (g < st.n_grp) {
+                const int a = st.grp_off[g], b = st.grp_off[g + 1];
+                if (a >= 0 && a <= b && b <= st.n_gt) {
+                    const float4 box = det_box[d];
+                    double bv = 0.0;
+                    int bi = -1;
+                    bool bnan = false;
+                    for (int j = a; j < b; ++j) {                 // np.argmax: the first maximum, a NaN counts as one
+                        const double v = map_iou(box, gt_box[j]);
+                        if (bi < 0) { bv = v; bi = j; bnan = v != v; }
+                        else if (!bnan) {
+                            if (v != v) { bnan = true; bi = j; }
+                            else if (v > bv) { bv = v; bi = j; }
+                        }
+                    }
+                    r = (bi >= 0 && !bnan && bv >= 0.5) ? bi : -1;
+                }
+            }
+        }
+        best[d] = r;
+    }
+}
+
+constexpr int MM_THREADS = 256;
+__global__ __launch_bounds__(MM_THREADS) void k_map_mark(tmpnn_map_store st, const int32_t* __restrict__ tracks,
+                                                        uint8_t* __restrict__ mark, uint8_t* __restrict__ gstat) {
+    const int64_t g = (int64_t)blockIdx.x * MM_THREADS + threadIdx.x;
+    if (g >= st.n_gt) return;
+    const int64_t a = st.claim_off[g], b = st.claim_off[g + 1];
+    bool bad = a < 0 || b < a || b > st.n_claim;
+    if (!bad) {
+        bool found = false;
+        for (int64_t i = a; i < b; ++i) {
+            const int d = st.claim_det[i];
+            if (d < 0 || d >= st.n_det) { bad = true; break; }
+            const bool kept = tracks[d] >= 0;
+            mark[d] = (kept && !found) ? 1 : 0;
+            found |= kept;
+        }
+    }
+    gstat[g] = bad ? 1 : 0;
+}
+
+struct MapShared {
+    double d[MAP_TILE];                      // suffix maxima / AP terms of a tile
+    double wave_d[MAP_WAVES];
+    int wave_a[MAP_WAVES + 1], wave_b[MAP_WAVES + 1];
+};
+
+// inclusive prefix sums of two ints over the workgroup, and their totals (every thread calls; three barriers)
+__device__ __forceinline__ void map_scan2(MapShared& S, int& a, int& b, int& tot_a, int& tot_b) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int ta = __shfl_up(a, off), tb = __shfl_up(b, off);
+        if (lane >= off) { a += ta; b += tb; }
+    }
+    if (lane == 63) { S.wave_a[wave] = a; S.wave_b[wave] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int ra = 0, rb = 0;
+        for (int w = 0; w < MAP_WAVES; ++w) {
+            const int ta = S.wave_a[w], tb = S.wave_b[w];
+            S.wave_a[w] = ra; S.wave_b[w] = rb;
+            ra += ta; rb += tb;
+        }
+        S.wave_a[MAP_WAVES] = ra; S.wave_b[MAP_WAVES] = rb;
+    }
+    __syncthreads();
+    a += S.wave_a[wave]; b += S.wave_b[wave];
+    tot_a = S.wave_a[MAP_WAVES]; tot_b = S.wave_b[MAP_WAVES];
+    __syncthreads();
+}
+
+__device__ __forceinline__ double map_shfl_down_f64(double x, int off) {
+    const long long b = __double_as_longlong(x);
+    const int hi = __shfl_down((int)(b >> 32), off), lo = __shfl_down((int)b, off);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+
+// inclusive SUFFIX maxima over the workgroup (x >= 0, no NaNs: a maximum is exact in any order), and the tile's maximum
+__device__ __forceinline__ double map_suffix_max(MapShared& S, double x, double& tile_max) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double t = map_shfl_down_f64(x, off);
+        if (lane + off < 64) x = t > x ? t : x;
+    }
+    if (lane == 0) S.wave_d[wave] = x;
+    __syncthreads();
+    double later = 0.0, all = 0.0;
+#pragma unroll
+    for (int w = 0; w < MAP_WAVES; ++w) {
+        const double t = S.wave_d[w];
+        all = t > all ? t : all;
+        if (w > wave) later = t > later ? t : later;
+    }
+    __syncthreads();
+    tile_max = all;
+    return later > x ? later : x;
+}
+
+__global__ __launch_bounds__(MAP_TILE) void k_map_class(tmpnn_map_store st, const int32_t* __restrict__ tracks,
+                                                        const int32_t* __restrict__ part, const uint8_t* __restrict__ mark,
+                                                        const uint8_t* __restrict__ gstat, int32_t* __restrict__ ws_tp,
+                                                        double* __restrict__ ws_prec, tmpnn_map_record* __restrict__ out) {
+    __shared__ MapShared S;
+    const int c = blockIdx.x, tid = threadIdx.x;
+    int flag = 0;
+    // ---- N: the class's GT rows over the sequences that take part; the status of their claim lists
+    int64_t g0 = st.cls_gt_off[c], g1 = st.cls_gt_off[c + 1];
+    if (g0 < 0 || g1 < g0 || g1 > st.n_gt) { flag = MAP_FLAG_STORE; g0 = g1 = 0; }
+    int cnt = 0, badrow = 0;
+    for (int64_t g = g0 + tid; g < g1; g += MAP_TILE) {
+        const int s = st.gt_seq[g];
+        if (s < 0 || s >= st.S) badrow = 1;
+        else if (part[s] != 0) ++cnt;
+        badrow |= gstat[g];
+    }
+    int N, nbad;
+    map_scan2(S, cnt, badrow, N, nbad);                           // (the totals: every thread holds them afterwards)
+    if (nbad) flag = MAP_FLAG_STORE;
+    // ---- the class's sorted list
+    int64_t p0 = st.cls_off[c], p1 = st.cls_off[c + 1];
+    if (p0 < 0 || p1 < p0 || p1 > st.n_live) { flag = MAP_FLAG_STORE; p0 = p1 = 0; }
+    const int64_t n = p1 - p0;
+    const int64_t ntiles = (n + MAP_TILE - 1) / MAP_TILE;
+    // sweep 1, ascending: k, tp_k, precision
+    int kept_run = 0, tp_run = 0, bad = 0;
+    for (int64_t t = 0; t < ntiles; ++t) {
+        const int64_t p = p0 + t * MAP_TILE + tid;
+        int kept = 0, tp = 0;
+        if (p < p1) {
+            const int d = st.order[p];
+            if (d < 0 || d >= st.n_det) bad = 1;
+            else {
+                kept = tracks[d] >= 0;
+                const int b = st.det_best[d];
+                if (b >= st.n_gt || b < -1) bad = 1;
+                else tp = kept && b >= 0 && mark[d] != 0;
+            }
+        }
+        int k = kept, tk = tp, tot_k, tot_t;
+        map_scan2(S, k, tk, tot_k, tot_t);
+        k += kept_run; tk += tp_run;
+        if (p < p1) {
+            ws_tp[p] = tp ? tk : 0;                               // (tp_k of a true positive is >= 1)
+            ws_prec[p] = kept ? (double)tk / (double)k : 0.0;
+        }
+        kept_run += tot_k; tp_run += tot_t;
+    }
+    // sweep 2, descending: the envelope (this thread reads back only what it wrote itself: the same p in every sweep)
+    double carry = 0.0;
+    for (int64_t t = ntiles - 1; t >= 0; --t) {
+        const int64_t p = p0 + t * MAP_TILE + tid;
+        const double x = p < p1 ? ws_prec[p] : 0.0;
+        double tile_max;
+        double e = map_suffix_max(S, x, tile_max);
+        e = carry > e ? carry : e;
+        if (p < p1) ws_prec[p] = e;
+        carry = tile_max > carry ? tile_max : carry;
+    }
+    // sweep 3, ascending: the AP terms of the true positives, added by one lane in ascending k
+    double ap = 0.0;
+    for (int64_t t = 0; t < ntiles; ++t) {
+        const int64_t p = p0 + t * MAP_TILE + tid;
+        double term = 0.0;
+        if (p < p1) {
+            const int tk = ws_tp[p];
+            if (tk > 0) term = ((double)tk / (double)N - (double)(tk - 1) / (double)N) * ws_prec[p];
+        }
+        S.d[tid] = term;
+        __syncthreads();
+        if (tid == 0) {
+            const int m = (int)((n - t * MAP_TILE) < MAP_TILE ? (n - t * MAP_TILE) : MAP_TILE);
+            for (int i = 0; i < m; ++i) ap += S.d[i];             // (a term of 0 leaves the sum as it is: ap >= 0)
+        }
+        __syncthreads();
+    }
+    int zero = 0, tot_zero;
+    map_scan2(S, bad, zero, nbad, tot_zero);
+    if (nbad) flag = MAP_FLAG_STORE;
+    if (tid == 0) {
+        tmpnn_map_record r;
+        r.ap = (N > 0 && !flag) ? ap : 0.0;
+        r.annotations = N; r.kept = kept_run; r.true_positives = tp_run; r.flag = flag;
+        out[c] = r;
+    }
+}
+
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+int check_store(const tmpnn_map_store* st, const char* who, bool eval) {
+    TM_REQUIRE(st != nullptr, "%s: store is null", who);
+    TM_REQUIRE(st->S >= 0 && st->C >= 0 && st->n_gt >= 0 && st->n_det >= 0 && st->n_grp >= 0 && st->n_live >= 0 && st->n_claim >= 0,
+               "%s: S=%d C=%d n_gt=%lld n_det=%lld n_grp=%lld n_live=%lld n_claim=%lld", who, st->S, st->C, (long long)st->n_gt,
+               (long long)st->n_det, (long long)st->n_grp, (long long)st->n_live, (long long)st->n_claim);
+    TM_REQUIRE(st->n_gt < 0x7fffffff && st->n_det < 0x7fffffff && st->n_grp < 0x7fffffff && st->n_live <= st->n_det &&
+               st->n_claim <= st->n_det, "%s: the store is indexed by int32 (and n_live, n_claim <= n_det)", who);
+    TM_REQUIRE(st->n_det == 0 || (st->det_box && st->det_grp), "%s: null detection arrays", who);
+    TM_REQUIRE(st->n_gt == 0 || st->gt_box, "%s: null GT boxes", who);
+    TM_REQUIRE(st->grp_off, "%s: null group offsets", who);
+    TM_REQUIRE(aligned16(st->gt_box) && aligned16(st->det_box), "%s: boxes must be 16-byte aligned", who);
+    if (eval) {
+        TM_REQUIRE(st->cls_gt_off && st->cls_off && st->claim_off, "%s: null offsets", who);
+        TM_REQUIRE(st->n_gt == 0 || st->gt_seq, "%s: null gt_seq", who);
+        TM_REQUIRE(st->n_det == 0 || st->det_best, "%s: null det_best", who);
+        TM_REQUIRE(st->n_live == 0 || st->order, "%s: null order", who);
+        TM_REQUIRE(st->n_claim == 0 || st->claim_det, "%s: null claim_det", who);
+    }
+    return TMPNN_OK;
+}
+
+}  // namespace
+
+extern "C" int tmpnn_map_tile(void) { return MAP_TILE; }
+
+extern "C" size_t tmpnn_map_eval_ws(int64_t n_gt, int64_t n_det, int64_t n_live) {
+    if (n_gt < 0 || n_det < 0 || n_live < 0) return 0;
+    return align16((size_t)n_det) + align16((size_t)n_gt) + align16((size_t)n_live * 4) + align16((size_t)n_live * 8);
+}
+
+extern "C" int tmpnn_map_best(const tmpnn_map_store* st, int32_t* best, tmpnn_stream stream) {
+    if (int rc = check_store(st, "map_best", false)) return rc;
+    if (st->n_det == 0) return TMPNN_OK;
+    TM_REQUIRE(best != nullptr, "map_best: best is null");
+    int blocks = ceil_div(st->n_det, MB_THREADS);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_map_best, dim3(blocks), dim3(MB_THREADS), 0, as_stream(stream), *st, best);
+    return check_launch("map_best");
+}
+
+extern "C" int tmpnn_map_eval(const tmpnn_map_store* st, const int32_t* tracks, const int32_t* part, void* ws, size_t ws_bytes,
+                              tmpnn_map_record* out, tmpnn_stream stream) {
+    if (int rc = check_store(st, "map_eval", true)) return rc;
+    if (st->C == 0) return TMPNN_OK;
+    TM_REQUIRE(out != nullptr, "map_eval: out is null");
+    TM_REQUIRE(st->n_det == 0 || tracks, "map_eval: tracks is null");
+    TM_REQUIRE(st->S == 0 || part, "map_eval: part is null");
+    const size_t need = tmpnn_map_eval_ws(st->n_gt, st->n_det, st->n_live);
+    if (need && (ws == nullptr || ws_bytes < need)) return set_error(TMPNN_EWORKSPACE, "map_eval: workspace %zu < %zu bytes", ws_bytes, need);
+    TM_REQUIRE(aligned16(ws), "map_eval: workspace must be 16-byte aligned");
+    char* p = static_cast<char*>(ws);
+    uint8_t* mark = reinterpret_cast<uint8_t*>(p);
+    p += align16((size_t)st->n_det);
+    uint8_t* gstat = reinterpret_cast<uint8_t*>(p);
+    p += align16((size_t)st->n_gt);
+    int32_t* ws_tp = reinterpret_cast<int32_t*>(p);
+    p += align16((size_t)st->n_live * 4);
+    double* ws_prec = reinterpret_cast<double*>(p);
+    if (st->n_gt > 0) {
+        hipLaunchKernelGGL(k_map_mark, dim3(ceil_div(st->n_gt, MM_THREADS)), dim3(MM_THREADS), 0, as_stream(stream), *st, tracks, mark,
+                           gstat);
+        if (int rc = check_launch("map_eval (marks)")) return rc;
+    }
+    hipLaunchKernelGGL(k_map_class, dim3(st->C), dim3(MAP_TILE), 0, as_stream(stream), *st, tracks, part, mark, gstat, ws_tp, ws_prec,
+                       out);
+    return check_launch("map_eval");
+}

@@ -278,7 +278,7 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
 
 
 def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
-             tp_classifier: bool = True) -> Dict:
+             tp_classifier: bool = True, map_evaluator=None) -> Dict:
     """The validation pass of train.py:177-282 up to the MOTA that chooses the checkpoint (train.py:300): the model in eval
     mode for the pass (its mode is restored afterwards), infer_sequence over every sequence, all tracks handed to
     `evaluator.evaluate` and read once.  sequences: one dict per sequence with 'X' [1, ND, F] and 'y' [1, ND, 2] as
@@ -290,10 +290,15 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     Returns {'mota', 'motp', 'motas', 'per_sequence'} and the overall counts (objects, predictions, matches, switches,
     false_positives, misses, frames, dist_sum, recall, precision): the overall figures are the ratios of the summed counts
     (train.py:282), `motas` the MOTA of every sequence that took part (train.py:281), as fractions -- train.py prints 100 x.
-    Validation-mode F1 and mAP are not computed."""
+    map_evaluator: a mapeval.MapEvaluator built over the same sequences in the same order (or None: nothing more is done
+    and nothing more returned).  It is handed the same track list -- the sequences left out of the MOTA are left out of the
+    mAP (train.py:272-273) -- and the result gains 'map' (train.py:286, as a fraction) and 'aps' (class -> AP).
+    Validation-mode F1 is not computed."""
     store = evaluator.store
     if len(sequences) != store.S:
         raise ValueError(f'validate: {len(sequences)} sequences, the evaluator holds {store.S}')
+    if map_evaluator is not None and [int(n) for n in np.diff(map_evaluator.store.det_base)] != [int(n) for n in store.seq[:, 3]]:
+        raise ValueError('validate: map_evaluator was not built over the sequences of evaluator')
     was_training = model.training
     model.eval()
     try:
@@ -309,12 +314,18 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
                                               tp_classifier)
             tracks.append(y_out[:, 1] if ncalls > 0 else None)
         evaluator.evaluate(tracks)
+        if map_evaluator is not None:
+            map_evaluator.evaluate(tracks)
         per, overall = evaluator.read()
+        mres = map_evaluator.read() if map_evaluator is not None else None
     finally:
         model.train(was_training)
     out = dict(overall)
     out['motas'] = [p['mota'] for p in per if p is not None]
     out['per_sequence'] = per
+    if mres is not None:
+        out['map'] = mres['map']
+        out['aps'] = dict(zip(mres['classes'], mres['ap']))
     return out
 
 
