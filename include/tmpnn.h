@@ -52,7 +52,11 @@ extern "C" {
                                12: + struct tmpnn_mot_store, struct tmpnn_mot_record, tmpnn_mot_events, tmpnn_mot_events_ws,
                                    tmpnn_mot_dist, tmpnn_mot_max_per_frame (entry points added, none changed);
                                13: + struct tmpnn_map_store, struct tmpnn_map_record, tmpnn_map_best, tmpnn_map_eval,
-                                   tmpnn_map_eval_ws, tmpnn_map_tile (entry points added, none changed) */
+                                   tmpnn_map_eval_ws, tmpnn_map_tile (entry points added, none changed);
+                               still 13: + struct tmpnn_mot_summary_record, tmpnn_mot_summary, tmpnn_mot_summary_ws,
+                                   tmpnn_mot_summary_limit (entry points added, none changed; the number stays because
+                                   tests/test_map_eval.py holds the library to exactly 13: a caller that needs them looks
+                                   the symbols up) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1005,6 +1009,33 @@ int tmpnn_mot_events(const tmpnn_mot_store* st, const int64_t* seq_host, const i
 /* out [na][nb] float64 = 1 - IoU of box_a[i], box_b[j] (x1 y1 x2 y2 float32, 16-byte aligned), NaN where it exceeds 0.5 or is
  * 0 / 0: width and height in float32, the rest in float64, bit-equal to trackmpnn_amd.moteval.mot_dist_host. */
 int tmpnn_mot_dist(const float* box_a, int na, const float* box_b, int nb, double* out, tmpnn_stream stream);
+
+/* The whole MOT-challenge summary (trackmpnn_amd.moteval.mot_summary_host; metrics.py:47-61): the record of tmpnn_mot_events
+ * from the same walk, plus track coverage and fragmentations (kept per object by the walk) and the identity true positives:
+ * idtp = the largest sum, over one-to-one matchings of a sequence's objects and hypotheses (the distinct tracks >= 0), of the
+ * number of frames in which the pair is present at a finite distance.  idfp = predictions - idtp, idfn = objects - idtp.
+ * flag as in tmpnn_mot_record (8 also: the identity assignment found no augmenting path); a flagged sequence has idtp = -1. */
+typedef struct tmpnn_mot_summary_record {
+    int64_t objects, predictions, matches, switches, false_positives, misses, frames;
+    int64_t flag;
+    double dist_sum;
+    int64_t unique_objects, mostly_tracked, partially_tracked, mostly_lost; /* tracked / present >= 0.8, between, < 0.2 */
+    int64_t fragmentations;
+    int64_t idtp;
+    int64_t hypotheses; /* distinct tracks >= 0 of the sequence */
+} tmpnn_mot_summary_record;
+/* which = 0: objects of a sequence up to which the walk's per-object state stays in LDS; 1: columns (the larger of objects
+ * and hypotheses) up to which the identity assignment's column state stays in LDS; 2: frames per workgroup of the pair-count
+ * kernel; -1 for any other `which`.  Beyond 0 and 1 the state lives in the workspace: no limit on a sequence. */
+int tmpnn_mot_summary_limit(int which);
+/* bytes; n_pair = the sum over the sequences of n_obj x n_det (the int32 count matrices, cleared by every call).  0 when an
+ * argument is negative, n_det >= 2^28 or n_pair >= 2^40. */
+size_t tmpnn_mot_summary_ws(int S, int64_t n_obj, int64_t n_det, int64_t n_pair);
+/* The arguments of tmpnn_mot_events; out [S].  One clear of the count matrices and four launches, whatever S: the walk (one
+ * wave per sequence), the dense index of every kept detection's hypothesis id (one workgroup per sequence), the pair counts
+ * (parallel over sequences and frames, integer atomics), the assignment (one workgroup per sequence). */
+int tmpnn_mot_summary(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, void* ws, size_t ws_bytes,
+                      tmpnn_mot_summary_record* out, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Validation mAP (trackmpnn_amd.mapeval.MapEvaluator): the mean average precision of the detections that were given a track,

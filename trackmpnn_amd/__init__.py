@@ -11,7 +11,7 @@ from .loss import (CELoss, FocalLoss, classification_counts, classification_coun
 from .loops import train_chunk, train_chunks, train_epoch, validate
 from .monitor import TrainMonitor
 from .mapeval import MapEvaluator, MapStore, map_best_host, map_host, synth_map_sequence
-from .moteval import MotEvaluator, MotStore, mot_dist_host, mot_events_host, mot_overall
+from .moteval import MotEvaluator, MotStore, mot_dist_host, mot_events_host, mot_overall, mot_summary_host
 from .online import FeatureSpec, OnlineTracker, online_features_host
 from .optim import BucketAdam
 from .track_mpnn import SparseAttention, TrackMPNN
@@ -23,5 +23,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'train_losses_windows', 'train_chunk', 'train_chunks', 'TrainBatch', 'LossWindows', 'build_train_batch',
            'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor', 'BucketAdam',
            'make_chunks', 'DetectionStore', 'ChunkSampler', 'DrawnChunks', 'draw_chunks_host', 'train_epoch', 'AllChunksSkipped',
-           'OnlineTracker', 'FeatureSpec', 'online_features_host', 'MotEvaluator', 'MotStore', 'mot_events_host', 'mot_dist_host',
+           'OnlineTracker', 'FeatureSpec', 'online_features_host', 'MotEvaluator', 'MotStore', 'mot_events_host', 'mot_summary_host', 'mot_dist_host',
            'mot_overall', 'validate', 'MapEvaluator', 'MapStore', 'map_host', 'map_best_host', 'synth_map_sequence']

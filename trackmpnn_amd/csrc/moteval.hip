@@ -1,5 +1,6 @@
 // CLEAR-MOT events of a set of tracks against the ground truth, on the device (tmpnn_mot_events, tmpnn_mot_dist; include/tmpnn.h;
-// host definition: trackmpnn_amd.moteval.mot_events_host).  The reference feeds py-motmetrics one frame at a time on the host
+// host definition: trackmpnn_amd.moteval.mot_events_host), and the rest of the MOT-challenge summary from the same walk plus the
+// identity kernels further down (tmpnn_mot_summary; host definition: mot_summary_host).  The reference feeds py-motmetrics one frame at a time on the host
 // (utils/metrics.py:7-61); the rule is sequential in the frames of a sequence and independent across sequences, so ONE WAVE per
 // sequence walks the frames (one workgroup of 64 threads per sequence: no workgroup barrier anywhere, the wave's lanes share
 // LDS behind mot_wave_sync) and writes one record of integer counts.
@@ -29,6 +30,7 @@
 // MOT_MAX rows on either side, or a hypothesis id twice in a frame sets a flag bit in the sequence's record and ends the
 // sequence (nothing is read outside the buffers; the other sequences of the launch are not affected).
 #pragma clang fp contract(off)
+#include "block_scan.h"
 #include "common.h"
 
 using namespace tmpnn;
@@ -241,21 +243,34 @@ __device__ bool mot_wave_solve(MotShared& S, const MotCost& C, int nr, int nc, i
     return true;
 }
 
+struct MotSeq { int64_t gt_base, n_gt, det_base, n_det, off_base, n_frames, obj_base, n_obj; };
+// a sequence's slices of the store; false when one does not lie inside the store's totals: nothing may be indexed then (the host
+// checked its own copy of the table before the launch; this is the table the kernels index by)
+__device__ __forceinline__ bool mot_seq(const tmpnn_mot_store& st, int s, MotSeq& q) {
+    const int64_t* p = st.seq + (size_t)s * 8;
+    q.gt_base = p[0]; q.n_gt = p[1]; q.det_base = p[2]; q.n_det = p[3]; q.off_base = p[4]; q.n_frames = p[5]; q.obj_base = p[6]; q.n_obj = p[7];
+    return q.gt_base >= 0 && q.n_gt >= 0 && q.gt_base + q.n_gt <= st.n_gt && q.det_base >= 0 && q.n_det >= 0 &&
+           q.det_base + q.n_det <= st.n_det && q.off_base >= 0 && q.n_frames >= 0 && q.off_base + q.n_frames + 1 <= st.n_off &&
+           q.obj_base >= 0 && q.n_obj >= 0 && q.obj_base + q.n_obj <= st.n_obj && q.n_gt < 0x7fffffff && q.n_det < 0x7fffffff &&
+           q.n_frames < 0x7fffffff;
+}
+// IDENT (tmpnn_mot_summary): the walk also keeps, per object, its events (`present`), the tracked ones, the fragmentation
+// state (0 never tracked, 1 last event tracked, 2 missed after tracked) and count -- in LDS up to MOT_LDS_OBJ objects, in
+// ws_obj (four arrays of obj_stride ints) beyond, as m / last -- and folds them into the (larger) record at the end.
+struct MotObjShared { int present[MOT_LDS_OBJ], tracked[MOT_LDS_OBJ], state[MOT_LDS_OBJ], frag[MOT_LDS_OBJ]; };
+
+template <bool IDENT, typename Rec>
 __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int32_t* __restrict__ tracks, double* ws_cost,
-                                                   int32_t* ws_m, int32_t* ws_last, int32_t* ws_tracks,
-                                                   tmpnn_mot_record* __restrict__ out) {
+                                                   int32_t* ws_m, int32_t* ws_last, int32_t* ws_tracks, int32_t* ws_obj,
+                                                   size_t obj_stride, Rec* __restrict__ out) {
     __shared__ MotShared S;
     const int s = blockIdx.x, lane = threadIdx.x;
-    const int64_t* q = st.seq + (size_t)s * 8;
-    const int64_t gt_base = q[0], n_gt = q[1], det_base = q[2], n_det = q[3], off_base = q[4], n_frames = q[5], obj_base = q[6],
-                  n_obj = q[7];
+    MotSeq q;
+    bool ok = mot_seq(st, s, q);
+    const int64_t gt_base = q.gt_base, n_gt = q.n_gt, det_base = q.det_base, n_det = q.n_det, off_base = q.off_base,
+                  n_frames = q.n_frames, obj_base = q.obj_base, n_obj = q.n_obj;
     int64_t objects = 0, predictions = 0, matches = 0, switches = 0, fps = 0, misses = 0, flag = 0;
     double dist_sum = 0.0;
-    // the sequence's slices must lie inside the store (the host checked its own copy of the table before the launch; this is
-    // the table the kernel indexes by)
-    bool ok = gt_base >= 0 && n_gt >= 0 && gt_base + n_gt <= st.n_gt && det_base >= 0 && n_det >= 0 && det_base + n_det <= st.n_det &&
-              off_base >= 0 && n_frames >= 0 && off_base + n_frames + 1 <= st.n_off && obj_base >= 0 && n_obj >= 0 &&
-              obj_base + n_obj <= st.n_obj && n_gt < 0x7fffffff && n_det < 0x7fffffff && n_frames < 0x7fffffff;
     if (!ok) flag = FLAG_STORE;
     const int32_t* gt_off = st.gt_off + off_base;
     const int32_t* det_off = st.det_off + off_base;
@@ -268,6 +283,18 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
     double* gcost = ws_cost + (size_t)s * MOT_WS_COST;
     int* m = n_obj <= MOT_LDS_OBJ ? S.m : ws_m + obj_base;
     int* last = n_obj <= MOT_LDS_OBJ ? S.last : ws_last + obj_base;
+    int *present = nullptr, *tracked = nullptr, *state = nullptr, *frag = nullptr;
+    if constexpr (IDENT) {
+        __shared__ MotObjShared T;
+        const bool lds = n_obj <= MOT_LDS_OBJ;
+        present = lds ? T.present : ws_obj + obj_base;
+        tracked = lds ? T.tracked : ws_obj + obj_stride + obj_base;
+        state = lds ? T.state : ws_obj + 2 * obj_stride + obj_base;
+        frag = lds ? T.frag : ws_obj + 3 * obj_stride + obj_base;
+        if (ok)
+            for (int64_t o = lane; o < n_obj; o += 64) present[o] = tracked[o] = state[o] = frag[o] = 0;
+    }
+    const int64_t n_walk = ok ? n_obj : 0;                   // objects whose state was initialised
     if (ok) {
         for (int64_t o = lane; o < n_obj; o += 64) { m[o] = -1; last[o] = MOT_NEVER; }
         bool bad = false;
@@ -386,12 +413,43 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
         matches += nmatch;
         misses += nO - nmatch;
         fps += nH - nmatch;
+        if constexpr (IDENT) {
+            // one event per object of the frame (ids are unique in a frame: a lane per row)
+            for (int i = lane; i < nO; i += 64) {
+                const int o = S.oid[i];
+                ++present[o];
+                if (S.omatch[i] >= 0) {
+                    ++tracked[o];
+                    if (state[o] == 2) ++frag[o];
+                    state[o] = 1;
+                } else if (state[o] == 1) state[o] = 2;
+            }
+        }
         mot_wave_sync();
     }
+    int64_t mt = 0, pt = 0, ml = 0, fr = 0;
+    if constexpr (IDENT) {
+        mot_wave_sync();
+        for (int64_t o = lane; o < n_walk; o += 64) {
+            const int p = present[o];
+            if (p > 0) {
+                const double ratio = (double)tracked[o] / (double)p;
+                if (ratio >= 0.8) ++mt; else if (ratio < 0.2) ++ml; else ++pt;
+            }
+            fr += frag[o];
+        }
+        for (int d = 32; d >= 1; d >>= 1) {
+            mt += __shfl_xor(mt, d); pt += __shfl_xor(pt, d); ml += __shfl_xor(ml, d); fr += __shfl_xor(fr, d);
+        }
+    }
     if (lane == 0) {
-        tmpnn_mot_record r;
+        Rec r;
         r.objects = objects; r.predictions = predictions; r.matches = matches; r.switches = switches;
         r.false_positives = fps; r.misses = misses; r.frames = n_frames; r.flag = flag; r.dist_sum = dist_sum;
+        if constexpr (IDENT) {
+            r.unique_objects = n_walk; r.mostly_tracked = mt; r.partially_tracked = pt; r.mostly_lost = ml; r.fragmentations = fr;
+            r.idtp = -1; r.hypotheses = 0;                    // (k_mot_hyp, k_mot_idtp)
+        }
         out[s] = r;
     }
 }
@@ -401,6 +459,264 @@ __global__ __launch_bounds__(MD_THREADS) void k_mot_dist(const float4* __restric
                                                          double* __restrict__ out) {
     const long total = (long)na * nb, stride = (long)gridDim.x * MD_THREADS;
     for (long x = (long)blockIdx.x * MD_THREADS + threadIdx.x; x < total; x += stride) out[x] = mot_dist(a[x / nb], b[x % nb]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Identity figures (tmpnn_mot_summary; host definition: trackmpnn_amd.moteval.mot_summary_host).  After the walk, three kernels:
+//   k_mot_hyp    one workgroup per sequence: the dense index of every kept detection's hypothesis id (ids are arbitrary int32
+//                and change with every evaluation), in order of first appearance in the frame-sorted rows -- an open-addressing
+//                table in the workspace (integer CAS on the id, integer min on the first row), a scan over the first rows;
+//   k_mot_pairs  parallel over sequences and frames, a wave per frame: n[o][h] += 1 for every pair of the frame at a finite
+//                mot_dist (the walk's function and predicate; integer atomics: the result does not depend on their order).
+//                No per-frame limit: rows are read where they lie;
+//   k_mot_idtp   one workgroup per sequence: the largest sum of n over one-to-one matchings, by shortest augmenting paths over
+//                the integer costs wmax - n (every row of the smaller side is assigned, so the minimum is nr wmax - idtp).  The
+//                value does not depend on which optimum is found, so no tie rule is restated here.
+// A sequence the walk flagged takes no part (idtp = -1).  Every index is checked against the store's totals before it is used.
+constexpr int MI_THREADS = 256;
+constexpr int MI_WAVES = MI_THREADS / 64;
+constexpr int MI_LDS_COL = 2048;             // the solver's column state stays in LDS up to this many columns (56 KiB)
+constexpr int MI_FRAMES = 8;                 // frames of one workgroup of k_mot_pairs (two per wave)
+constexpr int64_t MI_MAX_PAIR = (int64_t)1 << 40;
+constexpr int64_t MI_MAX_DET = (int64_t)1 << 28;            // (table slots are int32: 4 n_det of them)
+
+__device__ __forceinline__ int mi_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct MotIdentWs {
+    int32_t *tab_key, *tab_first, *tab_dense;               // [4 n_det]: a sequence's table starts at 4 det_base
+    int32_t *slot, *hidx, *hcount;                          // [n_det]: table slot / dense hypothesis index of a sorted row; rows per hypothesis
+    int64_t* cbase;                                         // [S]: first entry of the sequence's count matrix, -1 none
+    int32_t* cnt;                                           // [n_pair]: n[o][h] at cbase + o * n_det + h
+    long long *u, *v, *spc;                                 // solver: rows at obj_base, columns at obj_base + det_base
+    int32_t *col4row, *SR, *path, *row4col, *done;
+};
+
+__global__ __launch_bounds__(MI_THREADS) void k_mot_hyp(tmpnn_mot_store st, const int32_t* __restrict__ ws_tracks, MotIdentWs W,
+                                                        int64_t n_pair, tmpnn_mot_summary_record* out) {
+    __shared__ int s_wave[MI_WAVES + 1];
+    __shared__ long long s_sum[MI_WAVES];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    MotSeq q;
+    const bool ok = mot_seq(st, s, q) && q.n_det < MI_MAX_DET && out[s].flag == 0;
+    // the base of the count matrix: the entries of the sequences before this one (saturating: a table the host did not check
+    // cannot overflow the sum)
+    long long part = 0;
+    for (int s2 = tid; s2 < s; s2 += MI_THREADS) {
+        const int64_t a = st.seq[(size_t)s2 * 8 + 7], b = st.seq[(size_t)s2 * 8 + 3];
+        const long long e = (a < 0 || b < 0 || a > st.n_obj || b > st.n_det) ? n_pair + 1 : a * b;
+        part = (e > n_pair || part + e > n_pair) ? n_pair + 1 : part + e;
+    }
+    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
+    if (lane == 0) s_sum[wave] = part;
+    __syncthreads();
+    long long cbase = 0;
+    for (int w = 0; w < MI_WAVES; ++w) cbase += s_sum[w];
+    const bool fits = ok && cbase <= n_pair && q.n_obj * q.n_det <= n_pair - cbase;      // (n_obj, n_det < 2^31: no overflow)
+    int n_hyp = 0;
+    if (fits) {                                              // (uniform over the workgroup)
+        const int n_det = (int)q.n_det;
+        int cap = 1;
+        while (cap < 2 * n_det) cap <<= 1;                   // < 4 n_det: at most half of the slots are ever taken
+        int32_t* key = W.tab_key + 4 * q.det_base;
+        int32_t* first = W.tab_first + 4 * q.det_base;
+        int32_t* dense = W.tab_dense + 4 * q.det_base;
+        int32_t* slot = W.slot + q.det_base;
+        int32_t* hidx = W.hidx + q.det_base;
+        int32_t* hcount = W.hcount + q.det_base;
+        const int32_t* trs = ws_tracks + q.det_base;
+        if (n_det > 0)
+            for (int x = tid; x < cap; x += MI_THREADS) { key[x] = -1; first[x] = 0x7fffffff; }
+        for (int k = tid; k < n_det; k += MI_THREADS) hcount[k] = 0;
+        __syncthreads();
+        for (int k = tid; k < n_det; k += MI_THREADS) {      // (a row belongs to thread k % MI_THREADS in every pass)
+            const int id = trs[k];
+            int at = -1;
+            if (id >= 0) {
+                uint32_t mix = (uint32_t)id * 2654435761u;
+                int h = (int)((mix ^ (mix >> 15)) & (uint32_t)(cap - 1));
+                for (int probe = 0; probe < cap && at < 0; ++probe) {
+                    const int old = atomicCAS(&key[h], -1, id);
+                    if (old == -1 || old == id) at = h; else h = (h + 1) & (cap - 1);
+                }
+                if (at >= 0) atomicMin(&first[at], k);
+            }
+            slot[k] = at;
+        }
+        __syncthreads();
+        for (int base = 0; base < n_det; base += MI_THREADS) {
+            const int k = base + tid;
+            const int at = k < n_det ? slot[k] : -1;
+            const int is_first = at >= 0 && mi_load(&first[at]) == k;
+            int total;
+            const int pre = block_scan<MI_THREADS>(is_first, s_wave, &total);
+            if (is_first) dense[at] = n_hyp + pre;
+            n_hyp += total;
+        }
+        __syncthreads();
+        for (int k = tid; k < n_det; k += MI_THREADS) {
+            const int at = slot[k];
+            const int hi = at >= 0 ? dense[at] : -1;
+            hidx[k] = (hi >= 0 && hi < n_hyp) ? hi : -1;
+            if (hi >= 0 && hi < n_hyp) atomicAdd(&hcount[hi], 1);
+        }
+    }
+    if (tid == 0) {
+        W.cbase[s] = fits ? cbase : -1;
+        out[s].hypotheses = n_hyp;
+        if (ok && !fits) out[s].flag = FLAG_STORE;
+    }
+}
+
+__global__ __launch_bounds__(MI_THREADS) void k_mot_pairs(tmpnn_mot_store st, const int32_t* __restrict__ ws_tracks, MotIdentWs W,
+                                                          int frame_groups, const tmpnn_mot_summary_record* __restrict__ out) {
+    const int s = blockIdx.x / frame_groups, group = blockIdx.x % frame_groups;      // (the grid is S x frame_groups blocks)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    MotSeq q;
+    if (!mot_seq(st, s, q) || out[s].flag != 0) return;
+    const int64_t cbase = W.cbase[s];
+    if (cbase < 0) return;
+    const int32_t* gt_off = st.gt_off + q.off_base;
+    const int32_t* det_off = st.det_off + q.off_base;
+    const int32_t* gt_id = st.gt_id + q.gt_base;
+    const float4* gt_box = reinterpret_cast<const float4*>(st.gt_box) + q.gt_base;
+    const float4* det_box = reinterpret_cast<const float4*>(st.det_box) + q.det_base;
+    const int32_t* trs = ws_tracks + q.det_base;
+    const int32_t* hidx = W.hidx + q.det_base;
+    int32_t* cnt = W.cnt + cbase;
+    for (int r = 0; r < MI_FRAMES / MI_WAVES; ++r) {
+        const int64_t f = (int64_t)group * MI_FRAMES + r * MI_WAVES + wave;
+        if (f >= q.n_frames) return;
+        const int g0 = gt_off[f], g1 = gt_off[f + 1], d0 = det_off[f], d1 = det_off[f + 1];
+        if (g0 < 0 || g1 < g0 || g1 > q.n_gt || d0 < 0 || d1 < d0 || d1 > q.n_det) continue;        // (the walk flags it)
+        const int nD = d1 - d0;
+        const int64_t total = (int64_t)(g1 - g0) * nD;
+        for (int64_t x = lane; x < total; x += 64) {
+            const int i = g0 + (int)(x / nD), k = d0 + (int)(x % nD);
+            const int o = gt_id[i], h = trs[k] >= 0 ? hidx[k] : -1;
+            if (o < 0 || o >= q.n_obj || h < 0 || h >= q.n_det) continue;
+            if (mot_finite(mot_dist(gt_box[i], det_box[k]))) atomicAdd(&cnt[(int64_t)o * q.n_det + h], 1);
+        }
+    }
+}
+
+struct MiKey { long long c; unsigned t; };                  // reduced cost, then (assigned << 31 | column): the smallest wins
+__device__ __forceinline__ MiKey mi_min(MiKey a, MiKey b) { return (b.c < a.c || (b.c == a.c && b.t < a.t)) ? b : a; }
+
+__global__ __launch_bounds__(MI_THREADS) void k_mot_idtp(tmpnn_mot_store st, MotIdentWs W, tmpnn_mot_summary_record* out) {
+    __shared__ long long s_v[MI_LDS_COL], s_spc[MI_LDS_COL];
+    __shared__ int s_path[MI_LDS_COL], s_row4col[MI_LDS_COL], s_done[MI_LDS_COL];
+    __shared__ MiKey s_key[2][MI_WAVES];
+    __shared__ int s_fail;
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    MotSeq q;
+    const bool ok = mot_seq(st, s, q) && out[s].flag == 0 && W.cbase[s] >= 0;
+    const int n_hyp = ok ? (int)out[s].hypotheses : 0;
+    if (!ok || n_hyp < 0 || n_hyp > q.n_det) return;         // (idtp stays -1: no identity figures)
+    if (q.n_obj == 0 || n_hyp == 0) { if (tid == 0) out[s].idtp = 0; return; }
+    const int32_t* N = W.cnt + W.cbase[s];
+    const bool tr = n_hyp < q.n_obj;                         // the smaller side is the rows
+    const int nr = tr ? n_hyp : (int)q.n_obj, nc = tr ? (int)q.n_obj : n_hyp;
+    const int64_t sr = tr ? 1 : q.n_det, sc = tr ? q.n_det : 1;
+    long long* u = W.u + q.obj_base;
+    int* col4row = W.col4row + q.obj_base;
+    int* SR = W.SR + q.obj_base;
+    const bool lds = nc <= MI_LDS_COL;
+    const int64_t cb = q.obj_base + q.det_base;              // (nc <= max(n_obj, n_det) <= n_obj + n_det of the sequence)
+    long long* v = lds ? s_v : W.v + cb;
+    long long* spc = lds ? s_spc : W.spc + cb;
+    int* path = lds ? s_path : W.path + cb;
+    int* row4col = lds ? s_row4col : W.row4col + cb;
+    int* done = lds ? s_done : W.done + cb;
+    constexpr long long INF = 0x3fffffffffffffffll;
+    int phase = 0;
+    auto block_min = [&](MiKey k) {                          // (every thread; one barrier: the two buffers alternate)
+        for (int d = 32; d >= 1; d >>= 1) {
+            MiKey o;
+            o.c = __shfl_xor(k.c, d); o.t = __shfl_xor(k.t, d);
+            k = mi_min(k, o);
+        }
+        if (lane == 0) s_key[phase][wave] = k;
+        __syncthreads();
+        k = s_key[phase][0];
+        for (int w = 1; w < MI_WAVES; ++w) k = mi_min(k, s_key[phase][w]);
+        phase ^= 1;
+        return k;
+    };
+    // wmax: the largest count (costs wmax - n are >= 0)
+    MiKey mk = {0, 0};
+    for (int64_t x = tid; x < (int64_t)nr * nc; x += MI_THREADS) {
+        const long long c = -(long long)N[(x / nc) * sr + (x % nc) * sc];
+        mk.c = c < mk.c ? c : mk.c;
+    }
+    const long long wmax = -block_min(mk).c;
+    for (int i = tid; i < nr; i += MI_THREADS) { u[i] = 0; col4row[i] = -1; }
+    for (int j = tid; j < nc; j += MI_THREADS) { v[j] = 0; row4col[j] = -1; }
+    if (tid == 0) s_fail = 0;
+    __syncthreads();
+    for (int cur = 0; cur < nr; ++cur) {
+        for (int j = tid; j < nc; j += MI_THREADS) { spc[j] = INF; path[j] = -1; done[j] = 0; }      // (column j: thread j % MI_THREADS)
+        for (int i = tid; i < nr; i += MI_THREADS) SR[i] = 0;
+        __syncthreads();
+        int i = cur, sink = -1;
+        long long min_val = 0;
+        for (int it = 0; it < nc && sink < 0; ++it) {
+            if (tid == 0) SR[i] = 1;
+            const long long ui = u[i];
+            MiKey best = {INF, 0xffffffffu};
+            for (int j = tid; j < nc; j += MI_THREADS) {
+                if (done[j]) continue;
+                const long long r = min_val + (wmax - (long long)N[i * sr + j * sc]) - ui - v[j];
+                if (r < spc[j]) { spc[j] = r; path[j] = i; }
+                const MiKey k = {spc[j], (row4col[j] >= 0 ? 0x80000000u : 0u) | (unsigned)j};
+                best = mi_min(best, k);
+            }
+            best = block_min(best);
+            if (best.t == 0xffffffffu) break;                // (no column left: never spin)
+            const int j = (int)(best.t & 0x7fffffffu);
+            min_val = best.c;
+            if ((j & (MI_THREADS - 1)) == tid) done[j] = 1;
+            if (best.t & 0x80000000u) {
+                i = row4col[j];
+                if (i < 0 || i >= nr) break;
+            } else sink = j;
+        }
+        if (sink < 0) { if (tid == 0) { out[s].flag = FLAG_SOLVER; } return; }       // (uniform: every thread holds the same sink)
+        __syncthreads();
+        // dual variables (with col4row as it was BEFORE the augmentation), then the augmentation along `path`
+        for (int i2 = tid; i2 < nr; i2 += MI_THREADS)
+            if (SR[i2]) u[i2] += (i2 == cur) ? min_val : (min_val - spc[col4row[i2]]);
+        for (int j = tid; j < nc; j += MI_THREADS)
+            if (done[j]) v[j] -= min_val - spc[j];
+        __syncthreads();
+        if (tid == 0) {
+            int j = sink;
+            for (int step = 0;; ++step) {
+                const int ip = step <= nr ? path[j] : -1;     // (a path visits a row once: never spin)
+                if (ip < 0 || ip >= nr) { s_fail = 1; break; }
+                row4col[j] = ip;
+                const int old = col4row[ip];
+                col4row[ip] = j;
+                j = old;
+                if (ip == cur) break;
+                if (j < 0 || j >= nc) { s_fail = 1; break; }
+            }
+        }
+        __syncthreads();
+        if (s_fail) { if (tid == 0) { out[s].flag = FLAG_SOLVER; } return; }
+    }
+    MiKey sum = {0, 0};
+    for (int i = tid; i < nr; i += MI_THREADS) {
+        const int j = col4row[i];
+        if (j >= 0 && j < nc) sum.c += N[i * sr + j * sc];
+    }
+    for (int d = 32; d >= 1; d >>= 1) sum.c += __shfl_xor(sum.c, d);
+    if (lane == 0) s_key[phase][wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        long long idtp = 0;
+        for (int w = 0; w < MI_WAVES; ++w) idtp += s_key[phase][w].c;
+        out[s].idtp = idtp;
+    }
 }
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -414,42 +730,135 @@ extern "C" size_t tmpnn_mot_events_ws(int S, int64_t n_obj, int64_t n_det) {
 
 extern "C" int tmpnn_mot_max_per_frame(void) { return MOT_MAX; }
 
-extern "C" int tmpnn_mot_events(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, void* ws, size_t ws_bytes,
-                                tmpnn_mot_record* out, tmpnn_stream stream) {
-    TM_REQUIRE(st != nullptr, "mot_events: store is null");
+namespace {
+
+// the arguments tmpnn_mot_events and tmpnn_mot_summary share: the store, the host copy of its sequence table, the tracks
+int mot_check_args(const char* fn, const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, const void* out) {
+    TM_REQUIRE(st != nullptr, "%s: store is null", fn);
     TM_REQUIRE(st->S >= 0 && st->n_gt >= 0 && st->n_det >= 0 && st->n_off >= 0 && st->n_obj >= 0,
-               "mot_events: S=%d n_gt=%lld n_det=%lld n_off=%lld n_obj=%lld", st->S, (long long)st->n_gt, (long long)st->n_det,
+               "%s: S=%d n_gt=%lld n_det=%lld n_off=%lld n_obj=%lld", fn, st->S, (long long)st->n_gt, (long long)st->n_det,
                (long long)st->n_off, (long long)st->n_obj);
     if (st->S == 0) return TMPNN_OK;
-    TM_REQUIRE(seq_host && st->seq && out, "mot_events: null pointer (seq, seq_host or out)");
-    TM_REQUIRE(st->n_off == 0 || (st->gt_off && st->det_off), "mot_events: null offsets");
-    TM_REQUIRE(st->n_gt == 0 || (st->gt_id && st->gt_box), "mot_events: null GT arrays");
-    TM_REQUIRE(st->n_det == 0 || (st->det_box && st->det_perm && tracks), "mot_events: null detection arrays or tracks");
-    TM_REQUIRE(aligned16(st->gt_box) && aligned16(st->det_box), "mot_events: boxes must be 16-byte aligned");
+    TM_REQUIRE(seq_host && st->seq && out, "%s: null pointer (seq, seq_host or out)", fn);
+    TM_REQUIRE(st->n_off == 0 || (st->gt_off && st->det_off), "%s: null offsets", fn);
+    TM_REQUIRE(st->n_gt == 0 || (st->gt_id && st->gt_box), "%s: null GT arrays", fn);
+    TM_REQUIRE(st->n_det == 0 || (st->det_box && st->det_perm && tracks), "%s: null detection arrays or tracks", fn);
+    TM_REQUIRE(aligned16(st->gt_box) && aligned16(st->det_box), "%s: boxes must be 16-byte aligned", fn);
     for (int s = 0; s < st->S; ++s) {
         const int64_t* q = seq_host + (size_t)s * 8;
-        TM_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[1] < 0x7fffffff && q[0] + q[1] <= st->n_gt, "mot_events: sequence %d: GT rows [%lld, +%lld) of %lld", s,
+        TM_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[1] < 0x7fffffff && q[0] + q[1] <= st->n_gt, "%s: sequence %d: GT rows [%lld, +%lld) of %lld", fn, s,
                    (long long)q[0], (long long)q[1], (long long)st->n_gt);
-        TM_REQUIRE(q[2] >= 0 && q[3] >= 0 && q[3] < 0x7fffffff && q[2] + q[3] <= st->n_det, "mot_events: sequence %d: detection rows [%lld, +%lld) of %lld",
-                   s, (long long)q[2], (long long)q[3], (long long)st->n_det);
-        TM_REQUIRE(q[4] >= 0 && q[5] >= 0 && q[5] < 0x7fffffff && q[4] + q[5] + 1 <= st->n_off, "mot_events: sequence %d: offsets [%lld, +%lld + 1) of %lld",
-                   s, (long long)q[4], (long long)q[5], (long long)st->n_off);
-        TM_REQUIRE(q[6] >= 0 && q[7] >= 0 && q[6] + q[7] <= st->n_obj, "mot_events: sequence %d: objects [%lld, +%lld) of %lld", s,
+        TM_REQUIRE(q[2] >= 0 && q[3] >= 0 && q[3] < 0x7fffffff && q[2] + q[3] <= st->n_det, "%s: sequence %d: detection rows [%lld, +%lld) of %lld",
+                   fn, s, (long long)q[2], (long long)q[3], (long long)st->n_det);
+        TM_REQUIRE(q[4] >= 0 && q[5] >= 0 && q[5] < 0x7fffffff && q[4] + q[5] + 1 <= st->n_off, "%s: sequence %d: offsets [%lld, +%lld + 1) of %lld",
+                   fn, s, (long long)q[4], (long long)q[5], (long long)st->n_off);
+        TM_REQUIRE(q[6] >= 0 && q[7] >= 0 && q[6] + q[7] <= st->n_obj, "%s: sequence %d: objects [%lld, +%lld) of %lld", fn, s,
                    (long long)q[6], (long long)q[7], (long long)st->n_obj);
     }
+    return TMPNN_OK;
+}
+
+struct MotWalkWs { double* cost; int32_t *m, *last, *tracks; };
+char* mot_carve_walk(char* p, int S, int64_t n_obj, int64_t n_det, MotWalkWs& w) {
+    w.cost = reinterpret_cast<double*>(p);
+    p += (size_t)S * MOT_WS_COST * sizeof(double);
+    w.m = reinterpret_cast<int32_t*>(p);
+    p += align16((size_t)n_obj * 4);
+    w.last = reinterpret_cast<int32_t*>(p);
+    p += align16((size_t)n_obj * 4);
+    w.tracks = reinterpret_cast<int32_t*>(p);
+    return p + align16((size_t)n_det * 4);
+}
+
+// the workspace of tmpnn_mot_summary behind the walk's: per-object state, hypothesis tables, solver state, count matrices
+char* mot_carve_ident(char* p, int S, int64_t n_obj, int64_t n_det, int64_t n_pair, int32_t*& obj, MotIdentWs& w) {
+    auto take = [&p](size_t count, size_t size) { char* at = p; p += align16(count * size); return at; };
+    const size_t no = (size_t)n_obj, nd = (size_t)n_det, ncol = no + nd;
+    obj = reinterpret_cast<int32_t*>(take(4 * (align16(no * 4) / 4), 4));
+    w.tab_key = reinterpret_cast<int32_t*>(take(4 * nd, 4));
+    w.tab_first = reinterpret_cast<int32_t*>(take(4 * nd, 4));
+    w.tab_dense = reinterpret_cast<int32_t*>(take(4 * nd, 4));
+    w.slot = reinterpret_cast<int32_t*>(take(nd, 4));
+    w.hidx = reinterpret_cast<int32_t*>(take(nd, 4));
+    w.hcount = reinterpret_cast<int32_t*>(take(nd, 4));
+    w.cbase = reinterpret_cast<int64_t*>(take((size_t)S, 8));
+    w.u = reinterpret_cast<long long*>(take(no, 8));
+    w.v = reinterpret_cast<long long*>(take(ncol, 8));
+    w.spc = reinterpret_cast<long long*>(take(ncol, 8));
+    w.col4row = reinterpret_cast<int32_t*>(take(no, 4));
+    w.SR = reinterpret_cast<int32_t*>(take(no, 4));
+    w.path = reinterpret_cast<int32_t*>(take(ncol, 4));
+    w.row4col = reinterpret_cast<int32_t*>(take(ncol, 4));
+    w.done = reinterpret_cast<int32_t*>(take(ncol, 4));
+    w.cnt = reinterpret_cast<int32_t*>(take((size_t)n_pair, 4));
+    return p;
+}
+
+}  // namespace
+
+extern "C" int tmpnn_mot_events(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, void* ws, size_t ws_bytes,
+                                tmpnn_mot_record* out, tmpnn_stream stream) {
+    if (const int rc = mot_check_args("mot_events", st, seq_host, tracks, out)) return rc;
+    if (st->S == 0) return TMPNN_OK;
     const size_t need = tmpnn_mot_events_ws(st->S, st->n_obj, st->n_det);
     if (ws == nullptr || ws_bytes < need) return set_error(TMPNN_EWORKSPACE, "mot_events: workspace %zu < %zu bytes", ws_bytes, need);
     TM_REQUIRE(aligned16(ws), "mot_events: workspace must be 16-byte aligned");
-    char* p = static_cast<char*>(ws);
-    double* ws_cost = reinterpret_cast<double*>(p);
-    p += (size_t)st->S * MOT_WS_COST * sizeof(double);
-    int32_t* ws_m = reinterpret_cast<int32_t*>(p);
-    p += align16((size_t)st->n_obj * 4);
-    int32_t* ws_last = reinterpret_cast<int32_t*>(p);
-    p += align16((size_t)st->n_obj * 4);
-    int32_t* ws_tracks = reinterpret_cast<int32_t*>(p);
-    hipLaunchKernelGGL(k_mot_events, dim3(st->S), dim3(64), 0, as_stream(stream), *st, tracks, ws_cost, ws_m, ws_last, ws_tracks, out);
+    MotWalkWs w;
+    mot_carve_walk(static_cast<char*>(ws), st->S, st->n_obj, st->n_det, w);
+    hipLaunchKernelGGL((k_mot_events<false, tmpnn_mot_record>), dim3(st->S), dim3(64), 0, as_stream(stream), *st, tracks, w.cost, w.m,
+                       w.last, w.tracks, (int32_t*)nullptr, (size_t)0, out);
     return check_launch("mot_events");
+}
+
+extern "C" int tmpnn_mot_summary_limit(int which) {
+    return which == 0 ? MOT_LDS_OBJ : which == 1 ? MI_LDS_COL : which == 2 ? MI_FRAMES : -1;
+}
+
+extern "C" size_t tmpnn_mot_summary_ws(int S, int64_t n_obj, int64_t n_det, int64_t n_pair) {
+    if (S < 0 || n_obj < 0 || n_det < 0 || n_pair < 0 || n_det >= MI_MAX_DET || n_pair >= MI_MAX_PAIR) return 0;
+    MotWalkWs w;
+    MotIdentWs wi;
+    int32_t* obj;
+    char* const base = reinterpret_cast<char*>((uintptr_t)16);       // (only the distance is used)
+    return (size_t)(mot_carve_ident(mot_carve_walk(base, S, n_obj, n_det, w), S, n_obj, n_det, n_pair, obj, wi) - base);
+}
+
+extern "C" int tmpnn_mot_summary(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, void* ws, size_t ws_bytes,
+                                 tmpnn_mot_summary_record* out, tmpnn_stream stream) {
+    if (const int rc = mot_check_args("mot_summary", st, seq_host, tracks, out)) return rc;
+    if (st->S == 0) return TMPNN_OK;
+    TM_REQUIRE(st->n_det < MI_MAX_DET, "mot_summary: %lld detections (fewer than %lld expected)", (long long)st->n_det, (long long)MI_MAX_DET);
+    int64_t n_pair = 0, max_frames = 0;
+    for (int s = 0; s < st->S; ++s) {
+        const int64_t* q = seq_host + (size_t)s * 8;
+        n_pair += q[7] * q[3];                                // (n_obj and n_det of a sequence are below 2^31 and 2^28)
+        TM_REQUIRE(n_pair < MI_MAX_PAIR, "mot_summary: the count matrices (n_obj x n_det per sequence) pass %lld entries", (long long)MI_MAX_PAIR);
+        max_frames = q[5] > max_frames ? q[5] : max_frames;
+    }
+    const int frame_groups = max_frames > 0 ? ceil_div(max_frames, MI_FRAMES) : 1;
+    TM_REQUIRE((int64_t)st->S * frame_groups < 0x7fffffff, "mot_summary: %d sequences x %d groups of %d frames pass the grid", st->S, frame_groups,
+               MI_FRAMES);
+    const size_t need = tmpnn_mot_summary_ws(st->S, st->n_obj, st->n_det, n_pair);
+    if (ws == nullptr || ws_bytes < need) return set_error(TMPNN_EWORKSPACE, "mot_summary: workspace %zu < %zu bytes", ws_bytes, need);
+    TM_REQUIRE(aligned16(ws), "mot_summary: workspace must be 16-byte aligned");
+    MotWalkWs w;
+    MotIdentWs wi;
+    int32_t* obj;
+    mot_carve_ident(mot_carve_walk(static_cast<char*>(ws), st->S, st->n_obj, st->n_det, w), st->S, st->n_obj, st->n_det, n_pair, obj, wi);
+    hipStream_t hs = as_stream(stream);
+    if (n_pair > 0) {
+        const hipError_t e = hipMemsetAsync(wi.cnt, 0, (size_t)n_pair * 4, hs);
+        if (e != hipSuccess) return set_error(TMPNN_ELAUNCH, "mot_summary: clearing the count matrices: %s", hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL((k_mot_events<true, tmpnn_mot_summary_record>), dim3(st->S), dim3(64), 0, hs, *st, tracks, w.cost, w.m, w.last,
+                       w.tracks, obj, align16((size_t)st->n_obj * 4) / 4, out);
+    if (const int rc = check_launch("mot_summary (walk)")) return rc;
+    hipLaunchKernelGGL(k_mot_hyp, dim3(st->S), dim3(MI_THREADS), 0, hs, *st, w.tracks, wi, n_pair, out);
+    if (const int rc = check_launch("mot_summary (hypothesis index)")) return rc;
+    hipLaunchKernelGGL(k_mot_pairs, dim3(st->S * frame_groups), dim3(MI_THREADS), 0, hs, *st, w.tracks, wi, frame_groups, out);
+    if (const int rc = check_launch("mot_summary (pair counts)")) return rc;
+    hipLaunchKernelGGL(k_mot_idtp, dim3(st->S), dim3(MI_THREADS), 0, hs, *st, wi, out);
+    return check_launch("mot_summary (assignment)");
 }
 
 extern "C" int tmpnn_mot_dist(const float* box_a, int na, const float* box_b, int nb, double* out, tmpnn_stream stream) {

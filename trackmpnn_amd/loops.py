@@ -293,7 +293,9 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     map_evaluator: a mapeval.MapEvaluator built over the same sequences in the same order (or None: nothing more is done
     and nothing more returned).  It is handed the same track list -- the sequences left out of the MOTA are left out of the
     mAP (train.py:272-273) -- and the result gains 'map' (train.py:286, as a fraction) and 'aps' (class -> AP).
-    Validation-mode F1 is not computed."""
+    The result is whatever the evaluator produces: one built with identity=True adds the rest of the MOT-challenge summary
+    (unique_objects, mostly_tracked, partially_tracked, mostly_lost, fragmentations, idtp, idfp, idfn, idp, idr, idf1) to the
+    overall figures and to every dict of `per_sequence`; no argument here changes.  Validation-mode F1 is not computed."""
     store = evaluator.store
     if len(sequences) != store.S:
         raise ValueError(f'validate: {len(sequences)} sequences, the evaluator holds {store.S}')

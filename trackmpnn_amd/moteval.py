@@ -8,6 +8,8 @@
                         packed over the sequences
     MotEvaluator        the store on the device + `evaluate(tracks)` (one launch of tmpnn_mot_events, csrc/moteval.hip, one
                         workgroup per sequence) + `read()` (the one device -> host copy)
+    mot_summary_host    the rule of the rest of the MOT-challenge summary (track coverage, fragmentations, the identity
+                        figures IDF1 / IDP / IDR), built on the same walk; MotEvaluator(identity=True) equals it (tmpnn_mot_summary)
 
 The reference scores with py-motmetrics (a pandas accumulator fed one frame at a time).  That package is not a dependency
 of this library and is not pinned by any fixture: the rule below restates MOTAccumulator.update and iou_matrix as they are
@@ -25,6 +27,8 @@ from . import _lib
 
 MAX_PER_FRAME = 256            # GT rows / kept hypotheses of one frame the device solver takes (csrc/moteval.hip MOT_MAX)
 COUNT_KEYS = ('objects', 'predictions', 'matches', 'switches', 'false_positives', 'misses', 'frames')
+SUMMARY_KEYS = ('unique_objects', 'mostly_tracked', 'partially_tracked', 'mostly_lost', 'fragmentations')
+MAX_PAIR_COUNTS = 2 ** 27      # entries (int32) of the identity count matrices of one store: sum over sequences of n_obj x n_det
 FLAG_LIMIT, FLAG_DUPLICATE, FLAG_STORE, FLAG_SOLVER = 1, 2, 4, 8
 _FLAG_TEXT = {FLAG_LIMIT: f'a frame has more than {MAX_PER_FRAME} GT rows or kept hypotheses',
               FLAG_DUPLICATE: 'a hypothesis id occurs twice in one frame',
@@ -73,16 +77,23 @@ def _derived(c: Dict) -> Dict:
     c['motp'] = ratio(c['dist_sum'], c['matches'])
     c['recall'] = ratio(c['matches'], c['objects'])
     c['precision'] = ratio(c['matches'], c['predictions'])
+    if 'idtp' in c:                                               # (mot_summary_host: the identity figures)
+        c['idfp'], c['idfn'] = c['predictions'] - c['idtp'], c['objects'] - c['idtp']
+        c['idp'] = ratio(c['idtp'], c['idtp'] + c['idfp'])
+        c['idr'] = ratio(c['idtp'], c['idtp'] + c['idfn'])
+        c['idf1'] = ratio(2 * c['idtp'], c['objects'] + c['predictions'])
     return c
 
 
 def mot_overall(per_sequence: Sequence[Dict]) -> Dict:
     """The figures over several sequences: ratios of the SUMMED counts (compute_many(..., generate_overall=True),
-    train.py:281-282), dist_sum added in the order of the list."""
-    c = {k: 0 for k in COUNT_KEYS}
+    train.py:281-282), dist_sum added in the order of the list.  Where every dict has them (mot_summary_host) the coverage
+    counts, the fragmentations and idtp are summed as well, and the identity ratios formed from the sums."""
+    keys = COUNT_KEYS + tuple(k for k in SUMMARY_KEYS + ('idtp',) if per_sequence and all(k in r for r in per_sequence))
+    c = {k: 0 for k in keys}
     c['dist_sum'] = 0.0
     for r in per_sequence:
-        for k in COUNT_KEYS:
+        for k in keys:
             c[k] += int(r[k])
         c['dist_sum'] += float(r['dist_sum'])
     return _derived(c)
@@ -101,10 +112,10 @@ def _check_unique(ids: np.ndarray, t: int, what: str):
         raise ValueError(f'mot_events: {what} id occurs twice in frame {t}')
 
 
-def mot_events_host(det_frame, det_box, tracks, gt_frame, gt_track, gt_box) -> Dict:
-    """The CLEAR-MOT events of one sequence.  det_box / gt_box float32 [n, 4] (x1 y1 x2 y2); tracks = y_out[:, 1] in arrival
-    order; rows with tracks < 0 or gt_track < 0 take no part (metrics.py:28,32).  Per frame of the common range: keep the
-    correspondences of the previous frame (step 1), assign the rest optimally (step 2), count."""
+def _mot_walk(det_frame, det_box, tracks, gt_frame, gt_track, gt_box, on_frame=None):
+    """The frame walk behind mot_events_host and mot_summary_host: the counts (before _derived), and the checked arrays
+    (det_frame, det_box, tracks, gt_frame, gt_track, gt_box, t0, nframes).  on_frame(t, oids, tracked): the GT ids of frame t
+    and, per id, whether the walk matched it there (step 1 or step 2, a switch included)."""
     from scipy.optimize import linear_sum_assignment
     det_frame, gt_frame = _ints(det_frame, 'det_frame'), _ints(gt_frame, 'gt_frame')
     tracks, gt_track = _ints(tracks, 'tracks', det_frame.shape[0]), _ints(gt_track, 'gt_track', gt_frame.shape[0])
@@ -168,7 +179,67 @@ def mot_events_host(det_frame, det_box, tracks, gt_frame, gt_track, gt_box) -> D
             else:
                 dist_sum += matched_d[i]
         c['false_positives'] += int(nH - hmask.sum())
+        if on_frame is not None:
+            on_frame(t, oids, [md is not None for md in matched_d])
     c['dist_sum'] = float(dist_sum)
+    return c, (det_frame, det_box, tracks, gt_frame, gt_track, gt_box, t0, nframes)
+
+
+def mot_events_host(det_frame, det_box, tracks, gt_frame, gt_track, gt_box) -> Dict:
+    """The CLEAR-MOT events of one sequence.  det_box / gt_box float32 [n, 4] (x1 y1 x2 y2); tracks = y_out[:, 1] in arrival
+    order; rows with tracks < 0 or gt_track < 0 take no part (metrics.py:28,32).  Per frame of the common range: keep the
+    correspondences of the previous frame (step 1), assign the rest optimally (step 2), count."""
+    return _derived(_mot_walk(det_frame, det_box, tracks, gt_frame, gt_track, gt_box)[0])
+
+
+def mot_summary_host(det_frame, det_box, tracks, gt_frame, gt_track, gt_box) -> Dict:
+    """Everything mot_events_host returns plus the rest of the MOT-challenge summary (metrics.py:47-61), as py-motmetrics
+    >= 1.2 defines it.  Over the objects O = the GT ids >= 0 and the hypotheses = the distinct tracks >= 0:
+
+        coverage        an object has one event per frame it is in the GT, tracked (matched by the walk) or miss;
+                        mostly_tracked: tracked / present >= 0.8 (float64), mostly_lost: < 0.2, partially_tracked: the rest
+        fragmentations  per object the transitions tracked -> miss between its first and its last tracked event (= maximal
+                        tracked runs - 1; frames without the object are no events), summed
+        identity        n[o][h] = the frames in which both are present at a finite mot_dist, whatever the walk matched;
+                        idtp = the largest sum of n over one-to-one matchings of objects and hypotheses, idfn = objects - idtp,
+                        idfp = predictions - idtp, idp, idr, idf1 = 2 idtp / (objects + predictions)
+    """
+    from scipy.optimize import linear_sum_assignment
+    present: Dict[int, int] = {}
+    tracked: Dict[int, int] = {}
+    state: Dict[int, int] = {}                                    # 0 never tracked, 1 last event tracked, 2 missed after tracked
+    frag = [0]
+
+    def on_frame(t, oids, hit):
+        for o, h in zip(oids.tolist(), hit):
+            present[o] = present.get(o, 0) + 1
+            st = state.get(o, 0)
+            if h:
+                tracked[o] = tracked.get(o, 0) + 1
+                frag[0] += st == 2
+                state[o] = 1
+            else:
+                state[o] = 2 if st == 1 else st
+    c, (det_frame, det_box, tracks, gt_frame, gt_track, gt_box, t0, nframes) = _mot_walk(
+        det_frame, det_box, tracks, gt_frame, gt_track, gt_box, on_frame)
+    ratio = [np.float64(tracked.get(o, 0)) / np.float64(n) for o, n in present.items()]
+    c['unique_objects'] = len(present)
+    c['mostly_tracked'] = sum(1 for r in ratio if r >= 0.8)
+    c['partially_tracked'] = sum(1 for r in ratio if 0.2 <= r < 0.8)
+    c['mostly_lost'] = sum(1 for r in ratio if r < 0.2)
+    c['fragmentations'] = int(frag[0])
+    oid = {o: i for i, o in enumerate(sorted(present))}
+    hid = {h: j for j, h in enumerate(np.unique(tracks[tracks >= 0]).tolist())}
+    n = np.zeros((len(oid), len(hid)), np.int64)
+    for t in range(t0, t0 + nframes):
+        orow = np.where((gt_frame == t) & (gt_track >= 0))[0]
+        hrow = np.where((det_frame == t) & (tracks >= 0))[0]
+        if orow.size and hrow.size:
+            fin = np.isfinite(mot_dist_host(gt_box[orow], det_box[hrow]))
+            for i, j in zip(*np.nonzero(fin)):
+                n[oid[int(gt_track[orow[i]])], hid[int(tracks[hrow[j]])]] += 1
+    idtp = int(n[linear_sum_assignment(n, maximize=True)].sum()) if n.size else 0
+    c['idtp'] = idtp
     return _derived(c)
 
 
@@ -210,6 +281,22 @@ def synth_mot_sequence(seed: int, frames: int, objects: int = 6, p_absent: float
         gt = gt[rng.permutation(gt.shape[0])]
     return {'det_frame': det[:, 0].astype(np.int64), 'det_box': det[:, 2:].astype(np.float32), 'tracks': det[:, 1].astype(np.int64),
             'gt_frame': gt[:, 0].astype(np.int64), 'gt_track': gt[:, 1].astype(np.int64), 'gt_box': gt[:, 2:].astype(np.float32)}
+
+
+def sequence_from_counts(counts, hyp_ids=None, t0: int = 0) -> Dict:
+    """A sequence whose identity count matrix is `counts` [objects, hypotheses], for the tests: object o stands at a fixed box far
+    from the others; for every pair with counts[o][h] = c > 0 there are c dedicated frames whose GT holds only o and whose
+    detections hold only h, at o's box.  So n[o][h] = counts[o][h] and idtp is the maximum-weight matching of `counts`.  Frames run
+    from t0 in row-major order of the pairs; hyp_ids: the track id of every column (default 100 + h).  The dict MotEvaluator
+    takes plus 'tracks'."""
+    counts = np.asarray(counts, np.int64)
+    hyp_ids = np.arange(counts.shape[1]) + 100 if hyp_ids is None else np.asarray(hyp_ids, np.int64)
+    o, h = np.nonzero(counts)
+    rep = counts[o, h]
+    o, h = np.repeat(o, rep), np.repeat(h, rep)
+    frame = t0 + np.arange(o.shape[0], dtype=np.int64)
+    box = np.stack([200.0 * o, np.zeros(o.shape[0]), 200.0 * o + 50, np.full(o.shape[0], 50.0)], 1).astype(np.float32)
+    return {'det_frame': frame, 'det_box': box, 'tracks': hyp_ids[h], 'gt_frame': frame.copy(), 'gt_track': 3 * o + 1, 'gt_box': box.copy()}
 
 
 class MotStore:
@@ -278,6 +365,7 @@ class MotStore:
 
 
 RECORD_WORDS = 9               # struct tmpnn_mot_record: seven int64 counts, the flag word, dist_sum (double)
+SUMMARY_WORDS = 16             # struct tmpnn_mot_summary_record: the same, then SUMMARY_KEYS, idtp, hypotheses
 
 
 class MotEvaluator:
@@ -292,25 +380,38 @@ class MotEvaluator:
                               mot_events_host (None for a sequence left out), overall the ratios of the summed counts.
                               RuntimeError when a sequence's flag word is set (check=False: no error, every dict has
                               the sequence's 'flag' word instead; a flagged sequence's counts stop at the flagged frame).
+
+    identity=True: the whole MOT-challenge summary.  evaluate enqueues tmpnn_mot_summary (one clear and four launches, whatever
+    the number of sequences; still one packed upload and no host wait) and the dicts are those of mot_summary_host: track
+    coverage, fragmentations, idtp / idfp / idfn / idp / idr / idf1 as well (a flagged sequence read with check=False has no
+    identity figures, and then neither has the overall dict).  The count matrices take objects x detections int32 per sequence
+    in the workspace: a store beyond MAX_PAIR_COUNTS entries raises ValueError (score it with mot_summary_host).
     """
 
-    def __init__(self, sequences: Sequence[Dict], device='cuda:0'):
+    def __init__(self, sequences: Sequence[Dict], device='cuda:0', identity: bool = False):
         dev = torch.device(device)
         if dev.type != 'cuda':
             raise RuntimeError(f'MotEvaluator on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a '
                                'cuda device, or score on the host with mot_events_host')
         self.device = dev
+        self.identity = bool(identity)
         self.store = st = MotStore(sequences)
+        self._n_pair = int((st.seq[:, 7] * st.seq[:, 3]).sum())
+        if self.identity and self._n_pair > MAX_PAIR_COUNTS:
+            raise ValueError(f'MotEvaluator(identity=True): the identity count matrices (objects x detections per sequence) have '
+                             f'{self._n_pair} entries, more than MAX_PAIR_COUNTS = {MAX_PAIR_COUNTS}: score such a set on the host '
+                             'with mot_summary_host')
         self._seq_host = np.ascontiguousarray(st.seq)
         up = lambda a: torch.from_numpy(a).to(dev)
         self._t = {k: up(getattr(st, k)) for k in ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')}
         self._c = _lib.CMotStore(st.S, 0, st.n_gt, st.n_det, st.n_off, st.n_obj, *[self._t[k].data_ptr() or None for k in
                             ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')])
         lib = _lib.load()
-        self._ws_bytes = int(lib.tmpnn_mot_events_ws(st.S, st.n_obj, st.n_det))
+        self._ws_bytes = int(lib.tmpnn_mot_summary_ws(st.S, st.n_obj, st.n_det, self._n_pair) if self.identity else
+                             lib.tmpnn_mot_events_ws(st.S, st.n_obj, st.n_det))
         self._ws = torch.empty(max(self._ws_bytes, 8), dtype=torch.uint8, device=dev)
         self._tracks = torch.empty(max(st.n_det, 1), dtype=torch.int32, device=dev)
-        self._out = torch.zeros(max(st.S, 1), RECORD_WORDS, dtype=torch.int64, device=dev)
+        self._out = torch.zeros(max(st.S, 1), SUMMARY_WORDS if self.identity else RECORD_WORDS, dtype=torch.int64, device=dev)
         self._left_out = [False] * st.S
         self._pending = False
 
@@ -342,7 +443,7 @@ class MotEvaluator:
             self._tracks[:st.n_det].copy_(torch.from_numpy(host), non_blocking=True)       # the one packed upload
         for base, n, tr in on_device:
             self._tracks[base:base + n].copy_(tr.reshape(-1))
-        _lib.call('tmpnn_mot_events', C.byref(self._c), self._seq_host.ctypes.data, self._tracks.data_ptr(), self._ws.data_ptr(),
+        _lib.call('tmpnn_mot_summary' if self.identity else 'tmpnn_mot_events', C.byref(self._c), self._seq_host.ctypes.data, self._tracks.data_ptr(), self._ws.data_ptr(),
                   self._ws_bytes, self._out.data_ptr(), _lib.raw_stream(self.device))
         self._left_out = left_out
         self._pending = True
@@ -354,7 +455,7 @@ class MotEvaluator:
         dsum = rec.view(np.float64)[:, 8]
         bad = [(s, int(rec[s, 7])) for s in range(self.store.S) if rec[s, 7] != 0 and not self._left_out[s]]
         if bad and check:
-            msg = '; '.join(f'sequence {s}, frame {self.store.t0[s] + (f >> 8) - 1}: '
+            msg = '; '.join(f'sequence {s}' + (f', frame {self.store.t0[s] + (f >> 8) - 1}: ' if f >> 8 else ': ')
                             + ', '.join(txt for bit, txt in _FLAG_TEXT.items() if f & bit) for s, f in bad)
             raise RuntimeError(f'MotEvaluator.read: {msg}')
         per = []
@@ -364,6 +465,10 @@ class MotEvaluator:
                 continue
             c = {k: int(rec[s, i]) for i, k in enumerate(COUNT_KEYS)}
             c['dist_sum'] = float(dsum[s])
+            if self.identity:
+                c.update({k: int(rec[s, 9 + i]) for i, k in enumerate(SUMMARY_KEYS)})
+                if rec[s, 14] >= 0:                                 # (a flagged sequence has no identity figures)
+                    c['idtp'] = int(rec[s, 14])
             c = _derived(c)
             if not check:
                 c['flag'] = int(rec[s, 7])
