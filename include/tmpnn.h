@@ -56,7 +56,9 @@ extern "C" {
                                still 13: + struct tmpnn_mot_summary_record, tmpnn_mot_summary, tmpnn_mot_summary_ws,
                                    tmpnn_mot_summary_limit (entry points added, none changed; the number stays because
                                    tests/test_map_eval.py holds the library to exactly 13: a caller that needs them looks
-                                   the symbols up) */
+                                   the symbols up);
+                               still 13, for the same reason: + struct tmpnn_val_record, tmpnn_val_f1_count (entry point
+                                   added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -942,6 +944,31 @@ int tmpnn_track_retire(const tmpnn_dgraph* g, const tmpnn_track_rows* rows, cons
                        int32_t* keep, int32_t* small, const tmpnn_track_rows* rows_out, const float* h, int ld_h, int W,
                        float* h_new, int ld_hn, float* s_new, int next_t, int32_t* active, int32_t* notify,
                        tmpnn_stream stream);
+
+/* The validation monitor (train.py:207-219, :241-253, :278; csrc/valmon.hip): the F1 of every forward call of the validation
+ * pass in ONE launch per forward, enqueued between the model call and tmpnn_track_retire.  g: the graph the model call ran on;
+ * labels [N]: the tracker's row labels (tmpnn_track_rows.labels of the CURRENT row set: retire compacts them into the other
+ * one); scores [N]: P(positive) per row as the model call wrote it.
+ *   targets: create_targets (models/loss.py:8-44) as tmpnn_targets states it -- per det, over its CSR run in ascending edge
+ *     row, the last label-positive past edge and the first label-positive future edge get 1, every other edge 0, a det its
+ *     label.  An edge chosen by both endpoints counts once.  The chosen edges are a bitmap in the LDS; no targets array exists.
+ *   counts: pred = score > 0.5f (strict, as tmpnn_cls_counts); tp, fp, fn over the edge rows and, tp_classifier != 0, the det
+ *     rows (without the TP classifier a det's score is never read); rows = E + Dn in either mode.
+ *   fold, by one thread: rows > 0 makes the call a forward -- one with an empty selection included (no TP classifier, E = 0:
+ *     the reference appends f1_score([], [], zero_division=0) = 0.0).  F1 = 2 tp / (2 tp + fp + fn) in fp64, 0 where the
+ *     denominator is 0; rec->sum_f1 += F1, rec->forwards += 1, the four totals += the forward's.  log (or NULL): int32
+ *     [log_cap][4]; the forward's (tp, fp, fn, rows) is written at log[4 * min(forwards before, log_cap - 1)].
+ * E, Dn and the status are read from g->meta on the device: a graph with status != 0 is no forward, and nothing here waits for
+ * the host.  N <= TMPNN_TRACK_MAX_ROWS (checked on the host; N = 0 launches nothing).  Integer counts (ballot + popcount, the
+ * waves combined in wave order, integer LDS atomics for the bitmap), one fp64 addition per launch: exact and repeatable.  The
+ * record is device memory the caller zeroes and reads. */
+typedef struct tmpnn_val_record {
+    double sum_f1;             /* over the forwards */
+    int64_t forwards;
+    int64_t tp, fp, fn, rows;  /* summed over the forwards */
+} tmpnn_val_record;
+int tmpnn_val_f1_count(const tmpnn_dgraph* g, const uint8_t* labels, const float* scores, int tp_classifier,
+                       tmpnn_val_record* rec, int32_t* log, int log_cap, tmpnn_stream stream);
 
 
 /* ======================================================================================================

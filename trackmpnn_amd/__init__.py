@@ -9,7 +9,7 @@ from .chunks import ChunkSampler, DetectionStore, DrawnChunks, draw_chunks_host,
 from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
                    train_losses_windows)
 from .loops import train_chunk, train_chunks, train_epoch, validate
-from .monitor import TrainMonitor
+from .monitor import TrainMonitor, ValMonitor, val_counts_host, val_f1_host
 from .mapeval import MapEvaluator, MapStore, map_best_host, map_host, synth_map_sequence
 from .moteval import MotEvaluator, MotStore, mot_dist_host, mot_events_host, mot_overall, mot_summary_host
 from .online import FeatureSpec, OnlineTracker, online_features_host
@@ -24,4 +24,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'build_train_batch_device', 'classification_counts', 'classification_counts_windows', 'TrainMonitor', 'BucketAdam',
            'make_chunks', 'DetectionStore', 'ChunkSampler', 'DrawnChunks', 'draw_chunks_host', 'train_epoch', 'AllChunksSkipped',
            'OnlineTracker', 'FeatureSpec', 'online_features_host', 'MotEvaluator', 'MotStore', 'mot_events_host', 'mot_summary_host', 'mot_dist_host',
-           'mot_overall', 'validate', 'MapEvaluator', 'MapStore', 'map_host', 'map_best_host', 'synth_map_sequence']
+           'mot_overall', 'validate', 'MapEvaluator', 'MapStore', 'map_host', 'map_best_host', 'synth_map_sequence',
+           'ValMonitor', 'val_counts_host', 'val_f1_host']

@@ -232,7 +232,8 @@ std::vector<torch::Tensor> small_iter(torch::Tensor x, c10::optional<torch::Tens
 // ------------------------------------------------------------------------------------------------------------------------
 // One inference timestep of infer.py:70-87 (greedy or, since round 5, --hungarian association) without the interpreter between its launches: update_graph's block append
 // (tmpnn_track_extend; the active set of this timestep was derived by the previous step's tmpnn_track_retire), the model call
-// in eval mode (tmpnn_mp_iter_fwd) and decode_tracks (tmpnn_track_retire, with the NEXT timestep's active set), then the one
+// in eval mode (tmpnn_mp_iter_fwd), with a validation monitor the forward's F1 counts (tmpnn_val_f1_count), and decode_tracks
+// (tmpnn_track_retire, with the NEXT timestep's active set), then the one
 // host read of the timestep.  trackmpnn_amd/loops.py drives it for models on the fused path and graphs of LDS size; every other
 // case (Hungarian matching on the host, attention heads, wide cells, re-initialisation, empty timesteps) takes TrackGraph.update / .decode.
 // Same kernels, same arguments: the results are those of the Python path bit for bit.
@@ -247,6 +248,7 @@ using extend_tf_fn = int (*)(int, int, int, const int32_t*, const int32_t*, int,
                              const int32_t*, tmpnn_stream);
 using fwd_parts_fn = int (*)(const tmpnn_mp_params*, const float*, const tmpnn_dgraph*, int, const float*, int, float*, int, float*,
                              float*, float*, float*, size_t, int, tmpnn_stream);
+using val_fn = int (*)(const tmpnn_dgraph*, const uint8_t*, const float*, int, tmpnn_val_record*, int32_t*, int, tmpnn_stream);
 
 // The driver's state and the two halves of a timestep.  FRONT: the block append + index form + input transform
 // (tmpnn_track_extend_tf; or tmpnn_track_extend when the one-launch form is switched off).  BACK: the iteration
@@ -258,6 +260,7 @@ struct Driver {
     int32_t* active; const int32_t* track; const float* X; int F; int32_t* y_track; int ND; int32_t* pos_of_det; int32_t* keep_rows;
     int32_t* small; tmpnn_stream stream; int associate; void* hung_ws; size_t hung_ws_bytes; int32_t* notify; int score_rule;
     int ret_win; bool one_launch;
+    val_fn f_val; tmpnn_val_record* val_rec; int32_t* val_log; int val_log_cap; int val_tp;      // the validation monitor, or f_val = NULL
     const tmpnn_mp_params* P; const float* prep; int64_t G, H, GH;
     at::TensorOptions opts, iopts;
 };
@@ -269,7 +272,7 @@ struct Front {                // what the first launch of a timestep produced / 
 }  // namespace
 
 static Driver make_driver(const std::vector<int64_t>& ti, const std::vector<int64_t>& info, const torch::Tensor& h) {
-    TORCH_CHECK(ti.size() == 31 && info.size() == 18, "greedy_run: bad descriptors");
+    TORCH_CHECK((ti.size() == 31 || ti.size() == 36) && info.size() == 18, "greedy_run: bad descriptors");
     Driver d;
     d.f_extend = reinterpret_cast<extend_fn>(ti[0]);
     d.f_retire = reinterpret_cast<retire_fn>(ti[1]);
@@ -301,6 +304,17 @@ static Driver make_driver(const std::vector<int64_t>& ti, const std::vector<int6
     d.score_rule = (int)ti[30];
     TORCH_CHECK((d.score_rule & ~8) == 0 && (d.score_rule == 0 || d.f_fwd_parts != nullptr), "greedy_run: score rule ", d.score_rule);
     TORCH_CHECK(d.associate == 1 || (d.associate == 2 && d.hung_ws && d.hung_ws_bytes > 0), "greedy_run: association rule ", d.associate);
+    // the validation monitor (tmpnn_val_f1_count: one launch per timestep between the iteration and the decode; its record, its
+    // log or 0 with the log's capacity, whether det rows are counted); a descriptor of the old length has none
+    d.f_val = nullptr; d.val_rec = nullptr; d.val_log = nullptr; d.val_log_cap = 0; d.val_tp = 1;
+    if (ti.size() == 36) {
+        d.f_val = reinterpret_cast<val_fn>(ti[31]);
+        d.val_rec = reinterpret_cast<tmpnn_val_record*>(ti[32]);
+        d.val_log = reinterpret_cast<int32_t*>(ti[33]);
+        d.val_log_cap = (int)ti[34];
+        d.val_tp = ti[35] != 0 ? 1 : 0;
+        TORCH_CHECK(d.f_val == nullptr || d.val_rec != nullptr, "greedy_run: a validation monitor without a record");
+    }
     d.f_fwd = reinterpret_cast<fwd_fn>(info[0]);
     d.f_err = reinterpret_cast<err_fn>(info[2]);
     d.f_bind = reinterpret_cast<bind_fn>(info[6]);
@@ -380,6 +394,11 @@ static Back launch_back(const Driver& d, Front& f, int64_t N, int64_t A, int64_t
         rc = d.f_fwd(d.P, d.prep, &dg, (int)n_new, f.feats.data_ptr<float>(), d.F, h_cat.data_ptr<float>(), 0, b.h_out.data_ptr<float>(),
                      b.logits.data_ptr<float>(), b.scores.data_ptr<float>(), f.save.data_ptr<float>(), (size_t)f.save.numel(), d.stream);
     TORCH_CHECK(rc == 0, "tmpnn_mp_iter_fwd failed (code ", rc, "): ", d.f_err());
+    if (d.f_val != nullptr) {
+        // the forward's F1 (train.py:241-253) BEFORE the decode: it reads the labels of the row set the decode compacts away
+        rc = d.f_val(&dg, rows_cur->labels, b.scores.data_ptr<float>(), d.val_tp, d.val_rec, d.val_log, d.val_log_cap, d.stream);
+        TORCH_CHECK(rc == 0, "tmpnn_val_f1_count failed (code ", rc, "): ", d.f_err());
+    }
     b.hbuf = at::empty({(Nt + spare) * d.GH}, d.opts);
     b.h_new = at::empty({0}, d.opts).set_(b.hbuf.storage(), 0, {Nt, d.GH}, {d.GH, 1});
     b.s_new = at::empty({Nt, 1}, d.opts);

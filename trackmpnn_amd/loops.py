@@ -11,7 +11,8 @@
     infer_sequence  reference/infer.py:35-87    one sequence: per timestep update_graph(mode='test', greedy or Hungarian)
                                                 -> model -> decode_tracks (track finalisation + rolling-window deletion)
     validate        reference/train.py:177-282  the validation pass: infer_sequence over every sequence, then the CLEAR-MOT
-                                                counts of all tracks in one launch (moteval.MotEvaluator) and one host read
+                                                counts of all tracks in one launch (moteval.MotEvaluator) and one host read;
+                                                with a monitor.ValMonitor the F1 of every forward call (train.py:278)
 
 Same order of operations, same arguments' meaning and the same results as the reference's drivers (which cannot be imported:
 they parse the command line at import) -- but the graph, the hidden state, the losses' inputs and the tracks stay
@@ -202,9 +203,13 @@ def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier:
 
 def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 5, ret_win_size: int = 0,
                    use_hungarian: bool = False, device='cuda:0', tp_classifier: bool = True,
-                   stages: Optional[Dict[str, float]] = None):
+                   stages: Optional[Dict[str, float]] = None, monitor=None):
     """One sequence of infer.py:35-87 (model in eval mode).  Returns (y_out [ND, 2] int64 as the reference keeps it, number
-    of forward calls, sum of E over them)."""
+    of forward calls, sum of E over them).
+    monitor: a ValMonitor (monitor.py) that counts every forward call as the validation pass does (train.py:207-219, :241-253):
+    one more launch behind each model call -- the first call, the calls after a re-initialisation and every update call, a
+    timestep without new detections included -- before the decode, on the native driver's timesteps as on the composed ones;
+    no host read, and tracks, call count and edge count are the ones without it."""
     st = _Stages(stages)
     yy = y[0].detach().cpu().numpy().astype('int64')
     y_out = yy.copy()
@@ -218,6 +223,8 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
         tg, feats, t_st, t_end = init
         st.stop('graph')
         scores, logits, h, _ = model.forward_dgraph(feats, None, tg.graph)
+        if monitor is not None:
+            monitor.count(tg, scores, tp_classifier)
         sc = _pos_score(tg, scores, tp_classifier)
         st.stop('model_fwd')
         ncalls, edge_iters = 1, tg.E
@@ -251,7 +258,8 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
                     # one it does not take (no detections, a graph beyond the one-launch kernels, ...)
                     steps = [(t, t_end if t == t_end - 1 else t - cur_win_size + 2, t + 1 if t + 1 < t_end else -1)
                              for t in range(t_cur, t_end)]
-                    r = tg.greedy_run_fast(fast, step_info, h, h_cap, steps, ret_win_size, use_hungarian, tp_classifier)
+                    r = tg.greedy_run_fast(fast, step_info, h, h_cap, steps, ret_win_size, use_hungarian, tp_classifier,
+                                           monitor=monitor)
                     if r is not None:
                         h, sc, h_cap, n_done, edges = r
                         n_added = 1                            # (a native step only runs with D_t > 0 new detections)
@@ -264,6 +272,8 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
             st.stop('graph')
             scores, logits, h, _ = model.forward_dgraph(feats, h, tg.graph)
             h_cap = 0
+            if monitor is not None:
+                monitor.count(tg, scores, tp_classifier)         # (before the decode deletes rows and flips the row sets)
             sc = _pos_score(tg, scores, tp_classifier)
             st.stop('model_fwd')
             ncalls += 1
@@ -278,7 +288,7 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
 
 
 def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
-             tp_classifier: bool = True, map_evaluator=None) -> Dict:
+             tp_classifier: bool = True, map_evaluator=None, monitor=None) -> Dict:
     """The validation pass of train.py:177-282 up to the MOTA that chooses the checkpoint (train.py:300): the model in eval
     mode for the pass (its mode is restored afterwards), infer_sequence over every sequence, all tracks handed to
     `evaluator.evaluate` and read once.  sequences: one dict per sequence with 'X' [1, ND, F] and 'y' [1, ND, 2] as
@@ -295,7 +305,11 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     mAP (train.py:272-273) -- and the result gains 'map' (train.py:286, as a fraction) and 'aps' (class -> AP).
     The result is whatever the evaluator produces: one built with identity=True adds the rest of the MOT-challenge summary
     (unique_objects, mostly_tracked, partially_tracked, mostly_lost, fragmentations, idtp, idfp, idfn, idp, idr, idf1) to the
-    overall figures and to every dict of `per_sequence`; no argument here changes.  Validation-mode F1 is not computed."""
+    overall figures and to every dict of `per_sequence`; no argument here changes.
+    monitor: a monitor.ValMonitor (or None: nothing more is done and nothing more returned).  It is reset, counts every forward
+    call of every sequence that runs (one launch each, on either inference path; a skipped sequence contributes none) and is
+    read once, after the evaluator: the result gains 'f1' (train.py:278, the mean over the forwards, as a fraction) and
+    'f1_forwards'."""
     store = evaluator.store
     if len(sequences) != store.S:
         raise ValueError(f'validate: {len(sequences)} sequences, the evaluator holds {store.S}')
@@ -303,6 +317,8 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
         raise ValueError('validate: map_evaluator was not built over the sequences of evaluator')
     was_training = model.training
     model.eval()
+    if monitor is not None:
+        monitor.reset()
     try:
         tracks = []
         for s, q in enumerate(sequences):
@@ -313,13 +329,14 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
                 tracks.append(None)
                 continue
             y_out, ncalls, _ = infer_sequence(model, X, y, cur_win_size, ret_win_size, use_hungarian, evaluator.device,
-                                              tp_classifier)
+                                              tp_classifier, monitor=monitor)
             tracks.append(y_out[:, 1] if ncalls > 0 else None)
         evaluator.evaluate(tracks)
         if map_evaluator is not None:
             map_evaluator.evaluate(tracks)
         per, overall = evaluator.read()
         mres = map_evaluator.read() if map_evaluator is not None else None
+        vres = monitor.read() if monitor is not None else None
     finally:
         model.train(was_training)
     out = dict(overall)
@@ -328,6 +345,9 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     if mres is not None:
         out['map'] = mres['map']
         out['aps'] = dict(zip(mres['classes'], mres['ap']))
+    if vres is not None:
+        out['f1'] = vres['f1']
+        out['f1_forwards'] = vres['forwards']
     return out
 
 

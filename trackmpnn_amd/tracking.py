@@ -542,13 +542,15 @@ class TrackGraph:
         return None if r is None else r[:3]
 
     def greedy_run_fast(self, fast, model_info, h: torch.Tensor, cap_rows: int, steps, ret_win_size: int,
-                        use_hungarian: bool = False, tp_classifier: bool = True):
+                        use_hungarian: bool = False, tp_classifier: bool = True, monitor=None):
         """Steady-state inference timesteps (update -> eval model call -> decode; greedy or device-Hungarian association) through
         the native driver (csrc_host/fast_iter.cpp greedy_run / greedy_step): per timestep the same three tracker calls and the
         same model call as update() / TrackMPNN.forward_dgraph / decode(), issued without the interpreter between them or between
         the timesteps, and the timestep's one host read.  steps: [(t, t_upto, next_t or -1), ...] in loop order; as many of them
         as the native step takes are run (it stops in front of a timestep without detections, a grown graph beyond the
         one-launch kernels' 4096 rows, a problem the device solver may not take).
+        monitor: a monitor.ValMonitor -- the driver then enqueues its counting launch (tmpnn_val_f1_count) between every
+        timestep's model call and decode; everything else is what it is without one.
         Preconditions for the first step (else None and the caller takes the Python path): the previous decode / step prefetched
         its active set (`_prefetch`), D_t > 0, the grown graph fits.
         Returns (h', score', capacity of h' in rows, steps done, sum of E over their model calls) or None."""
@@ -603,6 +605,8 @@ class TrackGraph:
             ti[13], ti[14] = ti[14], ti[13]
         ti[23] = _stream()
         ti.append(0 if tp_classifier else 8)     # (no TP classifier: every detection's score is 1, infer.py:77-80)
+        if monitor is not None:                  # (the longer descriptor: entry point, record, log, log capacity, det rows counted)
+            ti += [*monitor.native_args(), 1 if tp_classifier else 0]
         ids0 = tpl[11]
         flat = []
         tr = self._t_range
