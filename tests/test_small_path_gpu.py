@@ -349,7 +349,7 @@ def test_gradient_sink_keeps_the_autograd_contract():
     for p in params:
         p.grad = torch.full_like(p, 3.0)
     grads = torch.autograd.grad(window_loss(), params)
-    assert model._sink is not None                                   # the native sink path was taken
+    assert (model._route.node, model._route.grads) == ('native', 'sink') and model._sink is not None
     assert all(bool((p.grad == 3.0).all()) for p in params)
     gscale = max(float(g.abs().max()) for g in grads)
     fired = []
@@ -379,7 +379,7 @@ def test_gradient_sink_keeps_the_autograd_contract():
     fp = list(frozen.parameters())
     fp[2].requires_grad_(False)
     window_loss(frozen).backward()
-    assert frozen._sink is None and fp[2].grad is None
+    assert (frozen._route.node, frozen._route.grads) == ('python', 'autograd') and frozen._sink is None and fp[2].grad is None
     for i, (p, g) in enumerate(zip(fp, grads)):
         if i != 2:
             assert float((p.grad - g).abs().max()) <= 1e-5 * gscale, i

@@ -41,8 +41,7 @@ class CapturedWindow:
             raise RuntimeError(f'CapturedWindow: at most {DG_BIG_ROWS} rows per call (this window: {nmax})')
         # models outside the fused batch-1 path (attention heads, nhidden 128 / 256, padded widths) are recorded through the
         # STAGED kernels on prebuilt plans: launch sizes are host values fixed at capture time, nothing reads back
-        padded = bool(getattr(model, '_padded', False))
-        self.staged = not small_eligible(model, nmax) or (padded and model._small.att)
+        self.staged = not small_eligible(model, nmax)
         self.static_x: List[torch.Tensor] = [x.detach().clone() for x, _, _ in calls]
         self.graphs: List[DeviceGraph] = [device_graph_from_adjacency(na, ea, dev) for _, na, ea in calls]
         for g in self.graphs:

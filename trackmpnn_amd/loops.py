@@ -357,25 +357,22 @@ def _fast_greedy(model, use_hungarian: bool, tp_classifier: bool, stages):
     the sequence's problems: the driver checks per timestep) Hungarian association, with or without the TP
     classifier (without: the iteration writes 1 as every detection's score, infer.py:77-80), no per-stage instrumentation;
     (None, None, 0) otherwise."""
-    from .small import fast_module, small_eligible
-    if stages is not None or model.training or getattr(model, '_padded', False):
-        return None, None, 0
+    from .small import fast_module, plan_small_route
     sp = getattr(model, '_small', None)
-    if sp is None or not sp.eligible or sp.att or not small_eligible(model, 1):
+    if stages is not None or model.training or sp is None:
         return None, None, 0
     fast = fast_module()
-    if fast is None or not hasattr(fast, 'greedy_run'):
+    # the route of a one-row call with nothing to differentiate: the driver issues the calls forward_dgraph would
+    r = plan_small_route(sp.eligible, sp.att, getattr(model, '_padded', False), 1, 1, False, False, False, False, False, False,
+                         fast is not None)
+    if (r.path, r.node, r.grads, r.padded) != ('fused', 'native', 'none', False) or not hasattr(fast, 'greedy_run'):
         return None, None, 0
-    if model._plist is None:
-        named = dict(model.named_parameters())
-        model._plist = [named[nm] for nm in model.spec.param_names()]
-        model._bufs = dict(model.named_buffers())
 
     class _G:                     # fast_info() only reads .N of the graph it is given (overwritten per step by the driver)
         N = 0
 
     def finfo():
-        params = model._plist
+        params = model._param_list()
         return sp.fast_info(params, _G, sp.params(params), False, False, False, 0)
 
     return fast, finfo, 0

@@ -9,6 +9,8 @@ anything else takes the staged path of functional.py.  There is no fallback to t
 """
 from __future__ import annotations
 
+import dataclasses
+import functools
 import os
 
 import ctypes as C
@@ -465,6 +467,49 @@ def bwd_ws_bytes(N: int, n: int, G: int, H: int, IN_e: int) -> int:
     return 4 * (N * G * IN_e + nb * G * slab + G * 2 * n * H + 16)
 
 
+@dataclasses.dataclass(frozen=True)
+class SmallRoute:
+    """What one batch-1 call runs, decided once from host values (plan_small_route)."""
+    path: str               # 'fused' (this module) | 'staged' (functional.py; node and grads are '' there)
+    padded: bool            # fused on the zero-padded parameter copies of a width the kernels are not instantiated for
+    node: str               # 'native' (csrc_host/fast_iter.cpp) | 'python' (_SmallIter)
+    grads: str              # parameter gradients: 'inplace' (into p.grad) | 'sink' (_ParamSink) | 'autograd' | 'none'
+    need_grad: bool         # anything saved for a backward
+
+
+def plan_small_route(eligible: bool, att: bool, padded: bool, N: int, cap: int, grad_on: bool, x_grad: bool, h_grad: bool,
+                     any_param_grad: bool, all_param_grad: bool, inplace: bool, native: bool) -> SmallRoute:
+    """The route of one call of N rows (graph capacity `cap`) on a model with the facts `eligible` (SmallPath.eligible), `att`
+    (attention heads) and `padded`.  grad_on: torch's grad mode; x_grad / h_grad / any_ / all_param_grad: requires_grad of the
+    inputs and of the parameters the node is handed (the padded copies of a padded width); inplace: in-place accumulation is
+    asked for (the module flag or functional.INPLACE_GRADS) AND every parameter owns a usable .grad buffer; native: the C++
+    node is loaded.  Host values only: no tensor, no library call."""
+    return _route(bool(eligible), bool(att), bool(padded), 0 < N <= DG_BIG_ROWS, cap == N, bool(grad_on), bool(x_grad),
+                  bool(h_grad), bool(any_param_grad), bool(all_param_grad), bool(inplace), bool(native))
+
+
+@functools.lru_cache(maxsize=None)      # (twelve booleans: the calls of a loop repeat a handful of them)
+def _route(eligible, att, padded, n_ok, cap_is_n, grad_on, x_grad, h_grad, any_pg, all_pg, inplace, native) -> SmallRoute:
+    pgrad = grad_on and any_pg
+    need_grad = grad_on and (any_pg or x_grad or h_grad)
+    if not eligible or not n_ok or (padded and att):
+        # models the fused iteration does not cover (nhidden >= 128; padded widths with attention heads; empty or huge graphs)
+        return SmallRoute('staged', padded, '', '', need_grad)
+    native_ok = native and cap_is_n and not att         # (attention heads: the Python node sequences the attention stage)
+    if not padded and pgrad and inplace:                # GradBucket: the parameters are not autograd inputs
+        return SmallRoute('fused', padded, 'native' if native_ok else 'python', 'inplace', need_grad)
+    if native_ok and pgrad and all_pg:                  # default gradient semantics on the native node: one gradient sink
+        return SmallRoute('fused', padded, 'native', 'sink', need_grad)
+    if native_ok and not need_grad:
+        # inference: the native node saves nothing and records nothing.  The body runs it under no_grad: with grad mode on
+        # and a frozen model it would otherwise hand back outputs that require grad over a backward with nothing saved
+        return SmallRoute('fused', padded, 'native', 'none', False)
+    return SmallRoute('fused', padded, 'python', 'autograd' if need_grad else 'none', need_grad)
+
+
 def small_eligible(model, N: int) -> bool:
+    """Does a call of N rows on this model take the fused iteration: the one answer forward(), forward_dgraph(), CapturedWindow
+    and the loops ask (the route's `path`, which no gradient flag enters)."""
     sp = model._small
-    return sp.eligible and 0 < N <= DG_BIG_ROWS
+    return _route(sp.eligible, sp.att, bool(getattr(model, '_padded', False)), 0 < N <= DG_BIG_ROWS, True, False, False, False,
+                  False, False, False, False).path == 'fused'

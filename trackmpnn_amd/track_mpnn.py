@@ -9,7 +9,7 @@ block-diagonally), which is what the benchmark and any loop that owns its graphs
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -22,7 +22,7 @@ from .functional import MPIteration, ModelSpec
 from .graph import (DG_BIG_ROWS, CallPlan, DeviceGraph, FrameGraph, device_graph_from_adjacency, graph_from_adjacency,
                     plan_single)
 from .layers import FactorGraphGRU
-from .small import SmallPath, _ParamSink, _SmallIter, fast_module, small_eligible
+from .small import SmallPath, _ParamSink, _SmallIter, fast_module, plan_small_route, small_eligible
 
 # hidden widths the kernels run natively; above 256 (multiples of 128, csrc/common.h supported_H_big) models without
 # attention heads are served: the wide edge cell and the H-generic f32 kernels, row movers in 256-column slices
@@ -135,26 +135,26 @@ class TrackMPNN(nn.Module):
         self.output_transform_edge.bias.data.uniform_(-4.595, -4.595)
         self.output_activation = nn.Sigmoid()
         self.spec = ModelSpec(tuple(groups), self.hpad, max(int(nattheads), 0), msg_type)
-        self._graph_cache = None
         # set by trackmpnn_amd.dist.GradBucket: parameter gradients are added straight into p.grad (functional.py)
         self.inplace_param_grads = False
         self._small = SmallPath(self)          # batch-1 path state (pointer structs, operand images)
-        self._small_pad = None                 # ... of a zero-padded width (its parameters are the padded copies)
-        self._plist = None
-        self._bufs = None
-        self._anchor = None
-        self._sink = None                      # gradient sink of the native node (default gradient mode)
-        self._sink_key = None
-        self._anch_key = None
-        self._anch_calls = 0
-        self._gst = None
-        self._pending_graphs = []              # DeviceGraphs whose validation status has not been read back yet
-        self._pad_cache = None                 # (key, padded parameter copies) of the zero-padded widths
+        self._drop(TrackMPNN._CACHED)
 
-    # per-call bookkeeping of the batch-1 path (plain Python values, reassigned on every forward call): kept out of
-    # nn.Module.__setattr__'s parameter / buffer / sub-module checks (~2.5 us per assignment, twice per call)
-    _PLAIN = frozenset(('_graph_cache', '_anchor', '_anch_key', '_anch_calls', '_gst', '_sink', '_sink_key', '_plist',
-                        '_bufs', '_pending_graphs', '_pad_cache', '_small_pad'))
+    # cached state and per-call bookkeeping of the batch-1 path, each field named once with what it holds; every field drops
+    # to None (the call counter to 0, the pending list to []).  Plain Python values, reassigned on every forward call: kept
+    # out of nn.Module.__setattr__'s parameter / buffer / sub-module checks (~2.5 us per assignment, twice per call)
+    _CACHED = ('_pad_cache',            # (key, padded parameter copies, token) of the zero-padded widths
+               '_small_pad',            # SmallPath of a zero-padded width (its parameters are the padded copies)
+               '_plist', '_bufs',       # parameters in spec.param_names() order / buffers by name (_param_list)
+               '_anchor',               # the dummy autograd input of the in-place gradient mode
+               '_anch_key', '_anch_calls', '_gst',      # usable .grad buffers: sentinel pointers, call count, pointer struct
+               '_sink', '_sink_key',    # gradient sink of the native node (default gradient mode) and what it was built over
+               '_graph_cache',          # the last adjacency pair forward() converted
+               '_pending_graphs',       # DeviceGraphs whose validation status has not been read back yet
+               '_route')                # SmallRoute of the last forward_dgraph call (a record, not a cache)
+    _PLAIN = frozenset(_CACHED)
+    _ON_LOAD = ('_pad_cache', '_plist', '_bufs', '_sink', '_sink_key')          # what load_state_dict drops (new values)
+    _ON_MOVE = _ON_LOAD + ('_anchor', '_anch_key', '_graph_cache')              # what _apply drops (new storage)
 
     def __setattr__(self, name, value):
         if name in TrackMPNN._PLAIN:
@@ -162,30 +162,28 @@ class TrackMPNN(nn.Module):
         else:
             super().__setattr__(name, value)
 
+    def _drop(self, fields, state=None):
+        """Drop the named cached fields: on the module (the pointer structs of `_small` are then re-read as well), or on
+        `state`, a copy of its __dict__."""
+        d = self.__dict__ if state is None else state
+        for k in fields:
+            d[k] = [] if k == '_pending_graphs' else (0 if k == '_anch_calls' else None)
+        if state is None:
+            self._small.invalidate()
+
     def _drop_caches(self):
         # adjacencies converted by earlier eager calls and not yet checked are validated NOW (one host round trip) instead of
         # being forgotten: the caller is promised a ValueError for an invalid graph, not just NaN outputs
         if self._pending_graphs and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
             self.check_graphs()
-        self._pad_cache = None
-        self._small.invalidate()
-        self._small_pad = None
-        self._plist = self._bufs = self._anchor = None
-        self._sink = self._sink_key = None
-        self._anch_key = None
-        self._anch_calls = 0
-        self._gst = None
-        self._graph_cache = None
-        self._pending_graphs = []
+        self._drop(TrackMPNN._CACHED)
 
     def __getstate__(self):
         # copy.deepcopy(model), pickle, torch.save(model): the batch-1 path's caches hold ctypes pointer structs, function
         # pointers and a non-leaf sink tensor -- none of them copyable, all of them rebuilt on the next forward call
         state = self.__dict__.copy()
-        for k in TrackMPNN._PLAIN:
-            state[k] = [] if k == '_pending_graphs' else (0 if k == '_anch_calls' else None)
+        self._drop(TrackMPNN._CACHED, state)
         state['_small'] = None
-        state['_small_pad'] = None
         return state
 
     def __setstate__(self, state):
@@ -201,20 +199,12 @@ class TrackMPNN(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         # .cuda() / .to() / .float(): parameter storage moves -> drop every cached device pointer
         out = super()._apply(fn, *args, **kwargs)
-        self._pad_cache = None
-        self._small.invalidate()
-        self._plist = self._bufs = self._anchor = None
-        self._sink = self._sink_key = None
-        self._anch_key = None
-        self._graph_cache = None
+        self._drop(TrackMPNN._ON_MOVE)
         return out
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
-        self._pad_cache = None
-        self._small.invalidate()
-        self._plist = self._bufs = None
-        self._sink = self._sink_key = None
+        self._drop(TrackMPNN._ON_LOAD)
         return out
 
     def get_input_transform(self, n_in, n_out):
@@ -287,7 +277,6 @@ class TrackMPNN(nn.Module):
         if torch.is_grad_enabled():
             live = [t for t in out if t.requires_grad]
             if live:
-                import weakref
                 me = weakref.ref(self)                 # (no reference cycle tensor -> hook -> copies -> tensor)
 
                 def spent(_g, me=me, token=token):
@@ -365,127 +354,32 @@ class TrackMPNN(nn.Module):
         for g in pending:
             g.check()
 
-    def forward_dgraph(self, x: torch.Tensor, h_in: Optional[torch.Tensor], graph: DeviceGraph,
-                       dropout_keep: Optional[Sequence[torch.Tensor]] = None):
-        """One message-passing call on a DeviceGraph: the fused iteration (H in {32, 64}; with attention heads the attention
-        stage runs between its two launches), the staged kernels for every other model.  dropout_keep: as forward_graph."""
-        if not x.is_cuda:
-            raise RuntimeError(f'x is on {x.device}: trackmpnn_amd runs on the MI355X HIP kernels only '
-                               '(no CPU or torch fallback exists)')
-        if self._padded and small_eligible(self, graph.N) and not self._small.att:
-            return self._forward_dgraph_padded(x, h_in, graph)
-        if self._padded or not small_eligible(self, graph.N):
-            # models the fused iteration does not cover (nhidden >= 128; padded widths with attention heads): the staged kernels
-            # on the same device-resident graph (frame_graph() reads E and Dn back: their launch sizes are host values)
-            return self.forward_graph(x, h_in, plan_single(graph.frame_graph(), int(x.shape[0])), dropout_keep=dropout_keep)
+    def _param_list(self):
+        """The parameters in spec.param_names() order (the buffers by name land in `_bufs`), read once per set of storages."""
         if self._plist is None:
             named = dict(self.named_parameters())
             self._plist = [named[nm] for nm in self.spec.param_names()]
             self._bufs = dict(self.named_buffers())
-        params = self._plist
-        grad_on = torch.is_grad_enabled()
-        pgrad = grad_on and any(p.requires_grad for p in params)
-        need_grad = grad_on and (pgrad or x.requires_grad or (h_in is not None and h_in.requires_grad))
-        # in-place accumulation (GradBucket): the parameters are not autograd inputs -- one dummy tensor stands in
-        anchored = False
-        if pgrad and (self.inplace_param_grads or _functional.INPLACE_GRADS):
-            # every parameter must own a usable .grad buffer; checked in full when the first / last buffer moves and
-            # every 64th call, by two sentinel pointers otherwise
-            g0, g1 = params[0].grad, params[-1].grad
-            key = (g0.data_ptr(), g1.data_ptr()) if (g0 is not None and g1 is not None) else None
-            self._anch_calls += 1
-            if key is not None and key == self._anch_key and (self._anch_calls & 63):
-                anchored = True
-            else:
-                dev = x.device
-                anchored = all(p.requires_grad and p.grad is not None and p.grad.dtype == torch.float32
-                               and p.grad.is_contiguous() and p.grad.device == dev for p in params)
-                self._anch_key = key if anchored else None
-                self._gst = self._small.grad_struct([p.grad for p in params]) if anchored else None
-        spare = max(256, graph.N)
-        # the carried state is extended IN PLACE when it came out of this path (it has spare rows behind it) and has
-        # not been continued from before; a second continuation from the same tensor copies instead
-        n = int(x.shape[0])
-        append = (h_in is not None and n > 0 and getattr(h_in, '_tmpnn_spare_rows', 0) >= n
-                  and not getattr(h_in, '_tmpnn_consumed', False))
-        if append:
-            h_in._tmpnn_consumed = True
-        call = dict(small=self._small, graph=graph, training=self.training, need_grad=need_grad, spare=spare, append=append,
-                    param_objs=params, anchored=anchored, check_pending=self.check_graphs, keep=dropout_keep)
-        att = self._small.att                  # attention heads: the Python node (it sequences the attention stage)
-        if anchored:
-            if self._anchor is None or self._anchor.device != x.device:
-                self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-            fast = fast_module() if not att else None
-            if fast is not None and graph.cap == graph.N:
-                # C++ autograd node (csrc_host/fast_iter.cpp): same kernels, no interpreter between the allocations
-                sp = self._small
-                info = sp.fast_info(params, graph, self._gst, self.training, need_grad, append, spare)
-                scores, logits, h_out = fast.small_iter(x, h_in, self._anchor, graph.arena, info, sp.keep(self._gst))
-            else:
-                scores, logits, h_out = _SmallIter.apply(call, x, h_in, self._anchor)
-        elif not att and pgrad and fast_module() is not None and graph.cap == graph.N and all(p.requires_grad for p in params):
-            # default gradient semantics on the native node: one gradient SINK per set of parameter values (a fresh one
-            # whenever a parameter's version counter moved, i.e. after every optimizer step)
-            sp = self._small
-            tmpl, total, offs, shapes = sp.grad_template(params)
-            key = tuple(p._version for p in params)
-            if self._sink is None or self._sink_key != key or self._sink.device != x.device:
-                self._sink = _ParamSink.apply(total, offs, shapes, *params)
-                self._sink_key = key
-            info = sp.fast_info(params, graph, tmpl, self.training, need_grad, append, spare, sink_total=total)
-            scores, logits, h_out = fast_module().small_iter(x, h_in, self._sink, graph.arena, info, sp.keep())
-        else:
-            fast = fast_module() if not (need_grad or att) else None
-            if fast is not None and graph.cap == graph.N:
-                # inference (nothing needs a gradient): the native node as well -- it saves nothing and records nothing
-                # (under no_grad: with grad mode on and a frozen model the node would otherwise hand back outputs that
-                #  require grad over a backward with nothing saved -- the Python node returns plain tensors there too)
-                if self._anchor is None or self._anchor.device != x.device:
-                    self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-                sp = self._small
-                info = sp.fast_info(params, graph, sp.params(params), self.training, False, append, spare)
-                with torch.no_grad():
-                    scores, logits, h_out = fast.small_iter(x, h_in, self._anchor, graph.arena, info, sp.keep())
-            else:
-                scores, logits, h_out = _SmallIter.apply(call, x, h_in, *params)
-        h_out._tmpnn_spare_rows = spare
-        if need_grad and self._pending_graphs:
-            # deferred validation must have happened before ANY backward node of this call runs (the native node does
-            # not check): the first gradient that reaches one of the outputs triggers the one host round trip
-            for t in (scores, logits, h_out):
-                if t.requires_grad:
-                    t.register_hook(self._check_graphs_hook)
-        if att:
-            fg = graph.frame_graph()
-            return scores, logits, h_out, tuple([SparseAttention(fg, ak) for ak in a] for a in call['alphas'])
-        return scores, logits, h_out, (None,) * self.spec.G
+        return self._plist
 
-    def _forward_dgraph_padded(self, x, h_in, graph: DeviceGraph):
-        """The fused iteration for a width the kernels are not instantiated for (nhidden padded to 32 / 64, no attention
-        heads): the same two launches per direction on the ZERO-PADDED parameter copies (built once per set of parameter
-        values; autograd hands the true parameters their gradients through the pads, summed over the calls of a window
-        first), padded BatchNorm buffers kept next to the true ones, and the carried state kept in its padded form behind
-        the [N, G * nhidden] tensor the caller sees (a view of it where there is one feature group)."""
-        if self._plist is None:
-            named = dict(self.named_parameters())
-            self._plist = [named[nm] for nm in self.spec.param_names()]
-            self._bufs = dict(self.named_buffers())
-        H, Hp, G = self.nhidden, self.hpad, self.spec.G
-        params = self._padded_params(self._plist)
+    def _padded_set(self, dev):
+        """(padded parameter copies, their SmallPath) of a width the kernels are not instantiated for: the copies are built
+        once per set of parameter values, the padded BatchNorm buffers are kept next to the true ones."""
+        H, Hp = self.nhidden, self.hpad
+        params = self._padded_params(self._param_list())
         sp = self._small_pad
-        if sp is None or sp.pad_buffers is None or next(iter(sp.pad_buffers.values())).device != x.device:
+        if sp is None or sp.pad_buffers is None or next(iter(sp.pad_buffers.values())).device != dev:
             sp = SmallPath(self, padded=True)
             sp.set_grad_layout(params)
             pb = {}
             for k, b in self._bufs.items():
                 if k.endswith('running_mean') or k.endswith('running_var'):
-                    pb[k] = torch.nn.functional.pad(b.detach().to(x.device), (0, Hp - H), value=1.0 if k.endswith('var') else 0.0).contiguous()
+                    pb[k] = torch.nn.functional.pad(b.detach().to(dev), (0, Hp - H), value=1.0 if k.endswith('var') else 0.0).contiguous()
                 else:
-                    pb[k] = b.detach().to(x.device).clone()
+                    pb[k] = b.detach().to(dev).clone()
             sp.pad_buffers = pb
             sp._buf_ver = {k: b._version for k, b in self._bufs.items()}
-            object.__setattr__(self, '_small_pad', sp)
+            self._small_pad = sp
         else:
             # the true buffers are the source of truth between calls (load_state_dict, manual edits): a padded copy is
             # refreshed when its original's version counter has moved since this path last wrote it
@@ -497,63 +391,125 @@ class TrackMPNN(nn.Module):
                         else:
                             sp.pad_buffers[k].copy_(b)
                     sp._buf_ver[k] = b._version
+        return params, sp
+
+    def _grad_buffers_usable(self, params, dev) -> bool:
+        """In-place accumulation (GradBucket): every parameter must own a usable .grad buffer; checked in full when the
+        first / last buffer moves and every 64th call, by two sentinel pointers otherwise."""
+        g0, g1 = params[0].grad, params[-1].grad
+        key = (g0.data_ptr(), g1.data_ptr()) if (g0 is not None and g1 is not None) else None
+        self._anch_calls += 1
+        if key is not None and key == self._anch_key and (self._anch_calls & 63):
+            return True
+        ok = all(p.requires_grad and p.grad is not None and p.grad.dtype == torch.float32
+                 and p.grad.is_contiguous() and p.grad.device == dev for p in params)
+        self._anch_key = key if ok else None
+        self._gst = self._small.grad_struct([p.grad for p in params]) if ok else None
+        return ok
+
+    def forward_dgraph(self, x: torch.Tensor, h_in: Optional[torch.Tensor], graph: DeviceGraph,
+                       dropout_keep: Optional[Sequence[torch.Tensor]] = None):
+        """One message-passing call on a DeviceGraph: the fused iteration (H in {32, 64}, other widths up to 64 zero-padded
+        when they have no attention heads; with heads the attention stage runs between its two launches), the staged kernels
+        for every other model.  What runs is decided once (small.plan_small_route) and kept in `_route`.  A padded width runs
+        the same two launches per direction on the ZERO-PADDED parameter copies (autograd hands the true parameters their
+        gradients through the pads, summed over the calls of a window first), with the carried state kept in its padded form
+        behind the [N, G * nhidden] tensor the caller sees (a view of it where there is one feature group).
+        dropout_keep: as forward_graph."""
+        if not x.is_cuda:
+            raise RuntimeError(f'x is on {x.device}: trackmpnn_amd runs on the MI355X HIP kernels only '
+                               '(no CPU or torch fallback exists)')
+        # ---- the route
+        sp, padded, dev = self._small, self._padded, x.device
+        fused = small_eligible(self, graph.N)
+        params = self._param_list()
+        if fused and padded:
+            params, sp = self._padded_set(dev)           # (the node is handed the copies: the route reads THEIR flags)
+        fast = fast_module()
         grad_on = torch.is_grad_enabled()
-        need_grad = grad_on and (any(p.requires_grad for p in params) or x.requires_grad
-                                 or (h_in is not None and h_in.requires_grad))
-        n = int(x.shape[0])
-        hp_in = None
-        if h_in is not None:
-            hp_in = getattr(h_in, '_tmpnn_padded_state', None)
+        pgrad = grad_on and any(p.requires_grad for p in params)
+        inplace = (fused and pgrad and not padded and (self.inplace_param_grads or _functional.INPLACE_GRADS)
+                   and self._grad_buffers_usable(params, dev))
+        route = self._route = plan_small_route(
+            fused, sp.att, padded, graph.N, graph.cap, grad_on, grad_on and x.requires_grad,
+            grad_on and h_in is not None and h_in.requires_grad, pgrad,
+            inplace or (pgrad and all(p.requires_grad for p in params)), inplace, fast is not None)
+        if route.path == 'staged':
+            # the staged kernels on the same device-resident graph (frame_graph() reads E and Dn back: their launch sizes
+            # are host values)
+            return self.forward_graph(x, h_in, plan_single(graph.frame_graph(), int(x.shape[0])), dropout_keep=dropout_keep)
+        need_grad = route.need_grad
+        # ---- carried state: extended IN PLACE when it came out of this path (it has spare rows behind it) and has not been
+        # continued from before; a second continuation from the same tensor copies instead
+        h_c = h_in
+        if padded and h_in is not None:
+            h_c = getattr(h_in, '_tmpnn_padded_state', None)
             # the padded tensor behind h_in is reused only while h_in is what this path returned: for several feature groups
             # h_in is a COPY of it, so an in-place edit by the caller (masking / resetting rows) moves h_in's version counter
             # and the state is padded afresh from h_in (one group: h_in is a view of the padded tensor, edits reach it)
-            if (hp_in is None or hp_in.shape[0] != h_in.shape[0]
-                    or (G > 1 and getattr(h_in, '_tmpnn_padded_ver', None) != (h_in.data_ptr(), h_in._version))):
-                hp_in = self._pad_state(h_in)
+            if (h_c is None or h_c.shape[0] != h_in.shape[0]
+                    or (self.spec.G > 1 and getattr(h_in, '_tmpnn_padded_ver', None) != (h_in.data_ptr(), h_in._version))):
+                h_c = self._pad_state(h_in)
         spare = max(256, graph.N)
-        append = (hp_in is not None and n > 0 and getattr(hp_in, '_tmpnn_spare_rows', 0) >= n
-                  and not getattr(hp_in, '_tmpnn_consumed', False))
+        n = int(x.shape[0])
+        append = (h_c is not None and n > 0 and getattr(h_c, '_tmpnn_spare_rows', 0) >= n
+                  and not getattr(h_c, '_tmpnn_consumed', False))
         if append:
-            hp_in._tmpnn_consumed = True
-        pgrad = grad_on and any(p.requires_grad for p in params)
-        fast = fast_module() if graph.cap == graph.N else None
-        if fast is not None and pgrad and all(p.requires_grad for p in params):
-            # the native node with a gradient SINK over the padded copies: each call returns one flat gradient buffer, autograd
-            # sums those per window and hands the slices to the copies once -- whose pad ops then reach the true parameters
-            tmpl, total, offs, shapes = sp.grad_template(params)
-            token = self._pad_cache[2] if self._pad_cache is not None else None
-            if self._sink is None or self._sink_key is not token or self._sink.device != x.device:
-                self._sink = _ParamSink.apply(total, offs, shapes, *params)
-                self._sink_key = token
-            info = sp.fast_info(params, graph, tmpl, self.training, need_grad, append, spare, sink_total=total)
-            scores, logits, h_pad = fast.small_iter(x, hp_in, self._sink, graph.arena, info, sp.keep())
-        elif fast is not None and not need_grad:
-            if self._anchor is None or self._anchor.device != x.device:
-                self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-            info = sp.fast_info(params, graph, sp.params(params), self.training, False, append, spare)
-            with torch.no_grad():
-                scores, logits, h_pad = fast.small_iter(x, hp_in, self._anchor, graph.arena, info, sp.keep())
+            h_c._tmpnn_consumed = True
+        # ---- node call
+        if (inplace or (route.node, route.grads) == ('native', 'none')) and (self._anchor is None or self._anchor.device != dev):
+            self._anchor = torch.zeros(1, device=dev, requires_grad=True)     # one dummy tensor stands in for the parameters
+        if route.node == 'native':
+            # C++ autograd node (csrc_host/fast_iter.cpp): same kernels, no interpreter between the allocations
+            if route.grads == 'sink':
+                # one gradient SINK per set of parameter values (a fresh one whenever a parameter's version counter moved, i.e.
+                # after every optimizer step; a padded width: whenever the copies were rebuilt).  Each call returns one flat
+                # gradient buffer, autograd sums those per window and hands the slices to the parameters (the copies) once
+                gst, total, offs, shapes = sp.grad_template(params)
+                key = (self._pad_cache or (None,) * 3)[2] if padded else tuple(p._version for p in params)
+                if self._sink is None or self._sink_key != key or self._sink.device != dev:
+                    self._sink = _ParamSink.apply(total, offs, shapes, *params)
+                    self._sink_key = key
+                carrier = self._sink
+            else:
+                gst, total, carrier = (self._gst if inplace else sp.params(params)), 0, self._anchor
+            info = sp.fast_info(params, graph, gst, self.training, need_grad, append, spare, sink_total=total)
+            args = (x, h_c, carrier, graph.arena, info, sp.keep(gst if inplace else None))
+            if route.grads == 'none':
+                with torch.no_grad():
+                    scores, logits, h_out = fast.small_iter(*args)
+            else:
+                scores, logits, h_out = fast.small_iter(*args)
         else:
             call = dict(small=sp, graph=graph, training=self.training, need_grad=need_grad, spare=spare, append=append,
-                        param_objs=params, anchored=False, check_pending=self.check_graphs, keep=None)
-            scores, logits, h_pad = _SmallIter.apply(call, x, hp_in, *params)
-        h_pad._tmpnn_spare_rows = spare
-        if self.training and n > 0:
-            with torch.no_grad():                                  # running statistics of the true units (one fused copy + the counters)
-                fl = [k for k in self._bufs if k.endswith('running_mean') or k.endswith('running_var')]
-                torch._foreach_copy_([self._bufs[k] for k in fl], [sp.pad_buffers[k][:H] for k in fl])
-                for k, b in self._bufs.items():
-                    if k not in fl:
-                        b.copy_(sp.pad_buffers[k])
-                    sp._buf_ver[k] = b._version
-        h_out = h_pad[:, :H] if G == 1 else self._unpad_state(h_pad)
-        h_out._tmpnn_padded_state = h_pad
-        h_out._tmpnn_padded_ver = (h_out.data_ptr(), h_out._version)
+                        param_objs=params, anchored=inplace, check_pending=self.check_graphs, keep=dropout_keep)
+            scores, logits, h_out = _SmallIter.apply(call, x, h_c, *([self._anchor] if inplace else params))
+        # ---- epilogue
+        h_out._tmpnn_spare_rows = spare
         if need_grad and self._pending_graphs:
-            for t in (scores, logits, h_pad):
+            # deferred validation must have happened before ANY backward node of this call runs (the native node does
+            # not check): the first gradient that reaches one of the outputs triggers the one host round trip
+            for t in (scores, logits, h_out):
                 if t.requires_grad:
                     t.register_hook(self._check_graphs_hook)
-        return scores, logits, h_out, (None,) * G
+        if padded:
+            H = self.nhidden
+            if self.training and n > 0:
+                with torch.no_grad():                                  # running statistics of the true units (one fused copy + the counters)
+                    fl = [k for k in self._bufs if k.endswith('running_mean') or k.endswith('running_var')]
+                    torch._foreach_copy_([self._bufs[k] for k in fl], [sp.pad_buffers[k][:H] for k in fl])
+                    for k, b in self._bufs.items():
+                        if k not in fl:
+                            b.copy_(sp.pad_buffers[k])
+                        sp._buf_ver[k] = b._version
+            h_pad = h_out
+            h_out = h_pad[:, :H] if self.spec.G == 1 else self._unpad_state(h_pad)
+            h_out._tmpnn_padded_state = h_pad
+            h_out._tmpnn_padded_ver = (h_out.data_ptr(), h_out._version)
+        if sp.att:
+            fg = graph.frame_graph()
+            return scores, logits, h_out, tuple([SparseAttention(fg, ak) for ak in a] for a in call['alphas'])
+        return scores, logits, h_out, (None,) * self.spec.G
 
     def _check_graphs_hook(self, grad):
         self.check_graphs()
@@ -572,7 +528,7 @@ class TrackMPNN(nn.Module):
             raise RuntimeError(f'x is on {x.device}: trackmpnn_amd runs on the MI355X HIP kernels only '
                                '(no CPU or torch fallback exists)')
         N = int(node_adj.shape[0])
-        small = SMALL_PATH and small_eligible(self, N) and not (self._padded and self._small.att)
+        small = SMALL_PATH and small_eligible(self, N)
         # the last call's graph is reused when the SAME adjacency objects come again unmodified (the static-window pattern:
         # several MP iterations on one graph).  Weak references: the cache pins neither a dense N x N adjacency nor its
         # device copy, and a recycled id() cannot alias (a dead reference never matches).
