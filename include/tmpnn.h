@@ -58,7 +58,10 @@ extern "C" {
                                    tests/test_map_eval.py holds the library to exactly 13: a caller that needs them looks
                                    the symbols up);
                                still 13, for the same reason: + struct tmpnn_val_record, tmpnn_val_f1_count (entry point
-                                   added, none changed) */
+                                   added, none changed);
+                               still 13, for the same reason: + struct tmpnn_label_store, struct tmpnn_label_record, struct
+                                   tmpnn_label_out, tmpnn_label_dets, tmpnn_label_compact, tmpnn_label_max_per_frame,
+                                   tmpnn_label_wave_frame (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1120,6 +1123,88 @@ size_t tmpnn_map_eval_ws(int64_t n_gt, int64_t n_det, int64_t n_live);
  * list), out [C].  ws: 16-byte aligned, tmpnn_map_eval_ws bytes; its contents need not survive between calls. */
 int tmpnn_map_eval(const tmpnn_map_store* st, const int32_t* tracks, const int32_t* part, void* ws, size_t ws_bytes,
                    tmpnn_map_record* out, tmpnn_stream stream);
+
+/* ======================================================================================================
+ * GT track ids for detections (trackmpnn_amd.labeling.DetectionLabeler; csrc/labeldet.hip) -- the reference's get_track_ids
+ * (dataset/kitti_mot.py:422-486, dataset/bdd100k_mot.py:407-470) over all frames of S sequences at once: the greedy matching
+ * of a frame's detections to its GT boxes in descending float32 "+1" IoU (equal categories, IoU >= iou_thresh; equal IoUs by
+ * ascending flat index p * G' + g over the matchable rows), then the removal of unassigned detections whose largest IoM over
+ * the iom_ignore_cat boxes is >= iom_thresh or whose largest IoU over the iou_ignore_cat boxes is >= iou_thresh (a NaN among
+ * them keeps the detection).  The rule is trackmpnn_amd.labeling.label_frame_host; every output equals it exactly.
+ *
+ * The store (all device memory): both sides sorted stably by (sequence, frame), packed over the sequences; frame f of sequence
+ * s is the global frame seq_base[s] + f, its detections det_first[.] .. det_first[. + 1], its GT rows gt_first likewise.
+ *     seq_base     [S + 1] int32          det_first, gt_first [n_frames + 1] int32
+ *     small_frames [n_small] int32        the global frames with at most tmpnn_label_wave_frame() rows on either side (one wave
+ *     big_frames   [n_big] int32          labels such a frame), and the others (one workgroup); every frame in exactly one list
+ *     det_frame, det_cat [n_det] int32    det_box [n_det][4] float32 x1 y1 x2 y2 (16-byte aligned)   det_score [n_det] float32
+ *     gt_frame, gt_track, gt_cat [n_gt] int32    gt_box [n_gt][4] float32 (16-byte aligned); det_frame / gt_frame: the frame
+ *                                         within the sequence, only handed on to the packed rows
+ * At most tmpnn_label_max_per_frame() detections and GT rows (ignore rows included) in a frame.
+ * ====================================================================================================== */
+typedef struct tmpnn_label_store {
+    int32_t S, reserved;
+    int64_t n_frames, n_det, n_gt; /* totals over the sequences; all < 2^31 - 1 */
+    int32_t iom_ignore_cat, iou_ignore_cat;
+    float iou_thresh, iom_thresh;
+    int64_t n_small, n_big; /* n_small + n_big == n_frames */
+    const int32_t* seq_base;
+    const int32_t* det_first;
+    const int32_t* gt_first;
+    const int32_t* small_frames;
+    const int32_t* big_frames;
+    const int32_t* det_frame;
+    const int32_t* det_cat;
+    const float* det_box;
+    const float* det_score;
+    const int32_t* gt_frame;
+    const int32_t* gt_track;
+    const int32_t* gt_cat;
+    const float* gt_box;
+} tmpnn_label_store;
+/* flag: 0, or 1 = a frame with more than tmpnn_label_max_per_frame() detections or GT rows, 2 = the store is inconsistent (an
+ * offset or a frame index out of range, a frame in neither list: nothing was read or written outside the arrays); frame: the
+ * first global frame with a flag, else -1; kept_det, kept_gt: the rows packed (a flagged frame packs none). */
+typedef struct tmpnn_label_record {
+    int64_t flag, frame, kept_det, kept_gt;
+} tmpnn_label_record;
+/* What the two entry points write (all device memory, the caller's):
+ *     track [n_det] int32 (-1: not assigned)   keep [n_det] u8   gt_keep [n_gt] u8       tmpnn_label_dets
+ *     det_cnt, gt_cnt [n_frames] int32  the kept rows of a frame   fflag [n_frames] u8   tmpnn_label_dets (_compact zeroes the
+ *                                                                                        counts of a flagged frame)
+ *     det_off, gt_off [n_frames + 1] int32    where a frame's kept rows start in the packed arrays    tmpnn_label_compact
+ *     seq_det_off, seq_gt_off [S + 1] int32   the same per sequence
+ *     o_det_frame, o_det_track, o_det_cat [n_det] int32, o_det_box [n_det][4] (16-byte aligned), o_det_score [n_det]: the kept
+ *     detections, packed, in the store's order; o_gt_frame, o_gt_track, o_gt_cat [n_gt], o_gt_box [n_gt][4]: the kept GT rows */
+typedef struct tmpnn_label_out {
+    tmpnn_label_record* record; /* 8-byte aligned */
+    int32_t* track;
+    uint8_t* keep;
+    uint8_t* gt_keep;
+    int32_t* det_cnt;
+    int32_t* gt_cnt;
+    uint8_t* fflag;
+    int32_t* det_off;
+    int32_t* gt_off;
+    int32_t* seq_det_off;
+    int32_t* seq_gt_off;
+    int32_t* o_det_frame;
+    int32_t* o_det_track;
+    int32_t* o_det_cat;
+    float* o_det_box;
+    float* o_det_score;
+    int32_t* o_gt_frame;
+    int32_t* o_gt_track;
+    int32_t* o_gt_cat;
+    float* o_gt_box;
+} tmpnn_label_out;
+int tmpnn_label_max_per_frame(void);
+int tmpnn_label_wave_frame(void);
+/* At most two launches (the wave frames, the workgroup frames): track, keep, gt_keep, det_cnt, gt_cnt, fflag. */
+int tmpnn_label_dets(const tmpnn_label_store* st, const tmpnn_label_out* out, tmpnn_stream stream);
+/* Two launches after tmpnn_label_dets on the same stream (one workgroup scans the per-frame counts and writes the record; one
+ * wave per frame packs the kept rows): everything else of tmpnn_label_out. */
+int tmpnn_label_compact(const tmpnn_label_store* st, const tmpnn_label_out* out, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Wide cells (H = 128 / 256, diff messages; BASELINE.json C5) as LDS-tiled GEMMs on bf16x6 split products

@@ -6,6 +6,8 @@ from .graph import (CallPlan, DeviceGraph, FrameGraph, device_graph_from_adjacen
                     graph_from_adjacency, graph_from_edges, plan_single, synth_window)
 from .capture import CapturedWindow
 from .chunks import ChunkSampler, DetectionStore, DrawnChunks, draw_chunks_host, make_chunks
+from .labeling import (BDD_RULES, KITTI_RULES, DetectionLabeler, LabelRules, label_detections_host, label_frame_host,
+                       label_overlaps_host, synth_label_sequence)
 from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
                    train_losses_windows)
 from .loops import train_chunk, train_chunks, train_epoch, validate
@@ -25,4 +27,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'make_chunks', 'DetectionStore', 'ChunkSampler', 'DrawnChunks', 'draw_chunks_host', 'train_epoch', 'AllChunksSkipped',
            'OnlineTracker', 'FeatureSpec', 'online_features_host', 'MotEvaluator', 'MotStore', 'mot_events_host', 'mot_summary_host', 'mot_dist_host',
            'mot_overall', 'validate', 'MapEvaluator', 'MapStore', 'map_host', 'map_best_host', 'synth_map_sequence',
-           'ValMonitor', 'val_counts_host', 'val_f1_host']
+           'ValMonitor', 'val_counts_host', 'val_f1_host', 'DetectionLabeler', 'LabelRules', 'KITTI_RULES', 'BDD_RULES',
+           'label_frame_host', 'label_detections_host', 'label_overlaps_host', 'synth_label_sequence']

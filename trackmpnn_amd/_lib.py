@@ -128,6 +128,22 @@ class CMapStore(C.Structure):
                                            'order', 'claim_off', 'claim_det')])
 
 
+class CLabelStore(C.Structure):
+    """struct tmpnn_label_store (include/tmpnn.h): both sides of S sequences sorted by frame, for the GT track-id labelling."""
+    _fields_ = ([('S', C.c_int32), ('reserved', C.c_int32)] + [(f, C.c_int64) for f in ('n_frames', 'n_det', 'n_gt')]
+                + [('iom_ignore_cat', C.c_int32), ('iou_ignore_cat', C.c_int32), ('iou_thresh', c_float), ('iom_thresh', c_float)]
+                + [(f, C.c_int64) for f in ('n_small', 'n_big')]
+                + [(f, c_void_p) for f in ('seq_base', 'det_first', 'gt_first', 'small_frames', 'big_frames', 'det_frame', 'det_cat',
+                                           'det_box', 'det_score', 'gt_frame', 'gt_track', 'gt_cat', 'gt_box')])
+
+
+class CLabelOut(C.Structure):
+    """struct tmpnn_label_out (include/tmpnn.h): what tmpnn_label_dets and tmpnn_label_compact write."""
+    _fields_ = [(f, c_void_p) for f in ('record', 'track', 'keep', 'gt_keep', 'det_cnt', 'gt_cnt', 'fflag', 'det_off', 'gt_off',
+                                        'seq_det_off', 'seq_gt_off', 'o_det_frame', 'o_det_track', 'o_det_cat', 'o_det_box',
+                                        'o_det_score', 'o_gt_frame', 'o_gt_track', 'o_gt_cat', 'o_gt_box')]
+
+
 _DGP = C.POINTER(CDGraph)
 _MPP = C.POINTER(CMpParams)
 _TRP = C.POINTER(CTrackRows)
@@ -136,6 +152,8 @@ _TBP = C.POINTER(CTrainBuild)
 _CDP = C.POINTER(CChunkDraw)
 _MSP = C.POINTER(CMotStore)
 _MAP = C.POINTER(CMapStore)
+_LSP = C.POINTER(CLabelStore)
+_LOP = C.POINTER(CLabelOut)
 
 # name -> (restype, argtypes); must mirror include/tmpnn.h (tests/test_abi.py cross-checks the names)
 _SIGNATURES = {
@@ -265,6 +283,10 @@ _SIGNATURES = {
     'tmpnn_map_best': (c_int, [_MAP, c_void_p, c_void_p]),
     'tmpnn_map_eval_ws': (c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     'tmpnn_map_eval': (c_int, [_MAP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'tmpnn_label_max_per_frame': (c_int, []),
+    'tmpnn_label_wave_frame': (c_int, []),
+    'tmpnn_label_dets': (c_int, [_LSP, _LOP, c_void_p]),
+    'tmpnn_label_compact': (c_int, [_LSP, _LOP, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

@@ -15,7 +15,9 @@ p = dropout_ratio = 0.2, and the features are computed from what is left.  Here 
         train_chunks(model, batch, drawn.features(batch))
 
 (`trackmpnn_amd.loops.train_epoch` is that loop with the optimizer step.)  Reading detection files stays outside the library:
-the store is built from arrays.
+the store is built from arrays
+(where only a detector's output and the labels are at hand, `trackmpnn_amd.labeling.DetectionLabeler.store_sequences()` gives the
+`track` ids: the reference's get_track_ids, on the plain boxes).
 
 The rules (kitti_mot.py, `t` = frame, W = image width, `frames` = the chunk's frame list):
   * rows of a chunk: the detections of its frames in list order, in load order within a frame (also under time reversal, so
