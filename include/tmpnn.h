@@ -1207,6 +1207,53 @@ int tmpnn_label_dets(const tmpnn_label_store* st, const tmpnn_label_out* out, tm
 int tmpnn_label_compact(const tmpnn_label_store* st, const tmpnn_label_out* out, tmpnn_stream stream);
 
 /* ======================================================================================================
+ * The visual head (csrc/vishead.hip; host definition: trackmpnn_amd.vishead.vis_head_host): the embedding CNN's map read at each
+ * box centre (reference dataset/kitti_mot.py:391-412), the softmax rows that are the 128 'vis' feature columns (:563-566) and the
+ * identity loss over the same rows (models/loss.py:162-181), per chunk, with its gradient wrt the maps.
+ *   centre   cx = trunc(((x1 + x2) / 2) * input_w / im_w / down_ratio), cy likewise with y, input_h, im_h: every operation one
+ *            correctly rounded float32 operation in this order; clamped to the map (flag bit 0, counted)
+ *   logits   maps[map_of][c][cy][cx], c < 128;  rows[d][col + c] = (softmax(logits)[c] - mean[c]) / std[c]
+ *   loss[b]  mean over the rows d of chunk b (offsets[b] <= d < offsets[b + 1]) with track[d] >= 0 of
+ *            logsumexp(logits[d]) - logits[d][track[d] % 128]; 0 for a chunk without such a row
+ *   dmaps    += g[b] / n_b * (softmax - onehot) at the row's pixel, for every labelled row; rows sharing a pixel are summed in
+ *            ascending row order by the lowest of them, which stores once: no atomics, bitwise reproducible
+ * A map_of outside [0, T) reads map 0 and sets flag bit 1; chunk boundaries that are not non-decreasing within [0, D] are
+ * clamped and counted: nothing is read or written outside the arrays, and the caller raises when it reads the counts.
+ * ====================================================================================================== */
+typedef struct {
+    int32_t T, Hm, Wm;          /* maps [T][128][Hm][Wm], T * Hm * Wm < 2^31 */
+    int32_t B;                  /* chunks (>= 1) */
+    int64_t D;                  /* detections, <= 131 072 (the backward's scan is D / 64 steps a row) */
+    float input_h, input_w, down_ratio;
+    float im_h, im_w;           /* the image size of every row when im_hw is NULL */
+    int32_t ld_rows, col;       /* row stride of `rows` in floats, first column written (col + 128 <= ld_rows) */
+    int32_t reserved;
+    const float* maps;
+    const float* box;           /* [D][4] x1 y1 x2 y2 */
+    const int32_t* map_of;      /* [D] */
+    const float* im_hw;         /* [D][2] (h, w), or NULL */
+    const int32_t* track;       /* [D], -1: no label; NULL: no row is labelled (inference) */
+    const int32_t* offsets;     /* [B + 1], or NULL with B = 1: one chunk of all rows */
+    const float* mean;          /* [128] */
+    const float* std;           /* [128] */
+    float* rows;                /* [D][ld_rows] */
+    float* logits;              /* [D][128] */
+    float* stat;                /* [D][2]: the row's maximum and the sum of exp(logit - maximum) */
+    float* nll;                 /* [D]: logsumexp - logit[track % 128]; 0 for a row without label */
+    int32_t* pix;               /* [D]: (map * Hm + cy) * Wm + cx */
+    int32_t* flag;              /* [D]: bit 0 centre clamped, bit 1 map_of out of range */
+    int32_t* chunk_of;          /* [D]: the row's chunk, -1: in none */
+    int32_t* key;               /* [D]: pix of a labelled row of a chunk, -1 otherwise: equal keys share a pixel of dmaps */
+    float* loss;                /* [B] */
+    int32_t* count;             /* [B][4]: labelled rows, clamped rows, bad rows + bad boundaries, rows */
+} tmpnn_vis_head;
+/* Two launches (one wave per detection; one wave per chunk, a fixed-order reduction): everything from `rows` on. */
+int tmpnn_vis_head_fwd(const tmpnn_vis_head* a, tmpnn_stream stream);
+/* After tmpnn_vis_head_fwd on the same stream, with the same struct: a memset of dmaps [T][128][Hm][Wm] and one launch (one wave
+ * per detection; a pairwise scan of the saved pixels finds the sharers).  g [B]: the gradient arriving at loss. */
+int tmpnn_vis_head_bwd(const tmpnn_vis_head* a, const float* g, float* dmaps, tmpnn_stream stream);
+
+/* ======================================================================================================
  * Wide cells (H = 128 / 256, diff messages; BASELINE.json C5) as LDS-tiled GEMMs on bf16x6 split products
  * (csrc/wide.hip).  Same arithmetic contract as the H <= 64 kernels: fp32 in / out, fp32 accumulate, error no larger
  * than the f32 MFMA chain.  tmpnn_wide_prepare splits the cell's two weight matrices into their MFMA operand images

@@ -18,6 +18,7 @@ from .online import FeatureSpec, OnlineTracker, online_features_host
 from .optim import BucketAdam
 from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
+from .vishead import VisHead, vis_centres_host, vis_head_host, vis_pixels_host
 from .train_batch import AllChunksSkipped, LossWindows, TrainBatch, build_train_batch, build_train_batch_device
 
 __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'create_targets', 'CELoss', 'FocalLoss', 'FrameGraph', 'CallPlan', 'graph_from_adjacency', 'graph_from_edges',
@@ -28,4 +29,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'OnlineTracker', 'FeatureSpec', 'online_features_host', 'MotEvaluator', 'MotStore', 'mot_events_host', 'mot_summary_host', 'mot_dist_host',
            'mot_overall', 'validate', 'MapEvaluator', 'MapStore', 'map_host', 'map_best_host', 'synth_map_sequence',
            'ValMonitor', 'val_counts_host', 'val_f1_host', 'DetectionLabeler', 'LabelRules', 'KITTI_RULES', 'BDD_RULES',
-           'label_frame_host', 'label_detections_host', 'label_overlaps_host', 'synth_label_sequence']
+           'label_frame_host', 'label_detections_host', 'label_overlaps_host', 'synth_label_sequence', 'VisHead', 'vis_centres_host',
+           'vis_pixels_host', 'vis_head_host']

@@ -144,6 +144,15 @@ class CLabelOut(C.Structure):
                                         'o_det_score', 'o_gt_frame', 'o_gt_track', 'o_gt_cat', 'o_gt_box')]
 
 
+class CVisHead(C.Structure):
+    """struct tmpnn_vis_head (include/tmpnn.h): one call of the visual head (box-centre gather, softmax rows, identity loss)."""
+    _fields_ = ([(f, C.c_int32) for f in ('T', 'Hm', 'Wm', 'B')] + [('D', C.c_int64)]
+                + [(f, c_float) for f in ('input_h', 'input_w', 'down_ratio', 'im_h', 'im_w')]
+                + [(f, C.c_int32) for f in ('ld_rows', 'col', 'reserved')]
+                + [(f, c_void_p) for f in ('maps', 'box', 'map_of', 'im_hw', 'track', 'offsets', 'mean', 'std', 'rows', 'logits',
+                                           'stat', 'nll', 'pix', 'flag', 'chunk_of', 'key', 'loss', 'count')])
+
+
 _DGP = C.POINTER(CDGraph)
 _MPP = C.POINTER(CMpParams)
 _TRP = C.POINTER(CTrackRows)
@@ -154,6 +163,7 @@ _MSP = C.POINTER(CMotStore)
 _MAP = C.POINTER(CMapStore)
 _LSP = C.POINTER(CLabelStore)
 _LOP = C.POINTER(CLabelOut)
+_VHP = C.POINTER(CVisHead)
 
 # name -> (restype, argtypes); must mirror include/tmpnn.h (tests/test_abi.py cross-checks the names)
 _SIGNATURES = {
@@ -287,6 +297,8 @@ _SIGNATURES = {
     'tmpnn_label_wave_frame': (c_int, []),
     'tmpnn_label_dets': (c_int, [_LSP, _LOP, c_void_p]),
     'tmpnn_label_compact': (c_int, [_LSP, _LOP, c_void_p]),
+    'tmpnn_vis_head_fwd': (c_int, [_VHP, c_void_p]),
+    'tmpnn_vis_head_bwd': (c_int, [_VHP, c_void_p, c_void_p, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),
