@@ -3,7 +3,7 @@
 // identity kernels further down (tmpnn_mot_summary; host definition: mot_summary_host).  The reference feeds py-motmetrics one frame at a time on the host
 // (utils/metrics.py:7-61); the rule is sequential in the frames of a sequence and independent across sequences, so ONE WAVE per
 // sequence walks the frames (one workgroup of 64 threads per sequence: no workgroup barrier anywhere, the wave's lanes share
-// LDS behind mot_wave_sync) and writes one record of integer counts.
+// LDS behind wave_sync) and writes one record of integer counts.
 //
 // Per frame t of the sequence's frame range, O = the GT rows of t (row order of the frame-sorted store), H = the detections of
 // t whose track is >= 0 (compacted in row order):
@@ -17,13 +17,9 @@
 //   counts    unmatched rows of O are misses, unmatched rows of H false positives; dist_sum adds the matched distances in
 //             ascending position in O (one lane, in order: bit-equal to the host's sum).
 //
-// The solver is scipy's linear_sum_assignment (rectangular_lsap.cpp: shortest augmenting paths in fp64, the matrix transposed
-// when it has more rows than columns) restated step for step INCLUDING its tie rules, as csrc/trackops.hip restates it for the
-// tracker's float costs (see the top of that file): the scan over `remaining` keeps the first column of minimal reduced cost
-// unless a later one of equal cost is unassigned (then the last such); `remaining` is filled in reverse and compacted by moving
-// its last entry into the hole.  Which optimum comes out decides the switches.  Lane l owns columns l, l + 64, l + 128, l + 192
-// (reduced costs, duals, path, position in `remaining` in registers); the row state lives in LDS.  Costs are read through the
-// L-fill on the fly from the distance matrix, which stays as it was for the counts.
+// The solver is scipy's linear_sum_assignment INCLUDING its tie rules (csrc/wave_lsap.h, shared with the tracker: which optimum
+// comes out decides the switches), the matrix transposed when it has more rows than columns.  Costs are read through the L-fill
+// on the fly from the distance matrix, which stays as it was for the counts.
 //
 // Every loop is bounded by a count read from the store AFTER it was checked against the store's totals: a frame's offsets must be
 // monotone inside the sequence's rows, permutation entries and object ids inside their ranges; a violation, a frame beyond
@@ -32,6 +28,7 @@
 #pragma clang fp contract(off)
 #include "block_scan.h"
 #include "common.h"
+#include "wave_lsap.h"
 
 using namespace tmpnn;
 
@@ -47,21 +44,15 @@ constexpr int MOT_NEVER = -0x7fffffff - 1;   // last_match of an object that was
 enum { FLAG_LIMIT = 1, FLAG_DUPLICATE = 2, FLAG_STORE = 4, FLAG_SOLVER = 8 };
 
 struct MotShared {
-    double u[MOT_MAX], spc[MOT_MAX];
+    LsapShared<MOT_MAX> L;
     double cost[MOT_LDS_COST];
     float4 obox[MOT_MAX], hbox[MOT_MAX];
-    int col4row[MOT_MAX], path[MOT_MAX];
     int oid[MOT_MAX], hid[MOT_MAX];
     int omatch[MOT_MAX];                     // position in H an object row was matched with, -1 none
     int m[MOT_LDS_OBJ], last[MOT_LDS_OBJ];
-    unsigned char SR[MOT_MAX], hmask[MOT_MAX];
+    unsigned char hmask[MOT_MAX];
 };
 
-__device__ __forceinline__ void mot_wave_sync() {          // LDS writes of this wave visible to its other lanes (one wave only)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 // np.maximum / np.minimum: the first operand where it is larger (smaller) or NaN
 __device__ __forceinline__ double mot_max(double a, double b) { return (a > b || a != a) ? a : b; }
 __device__ __forceinline__ double mot_min(double a, double b) { return (a < b || a != a) ? a : b; }
@@ -81,51 +72,6 @@ __device__ __forceinline__ double mot_dist(float4 o, float4 h) {
     return d;
 }
 
-__device__ __forceinline__ uint64_t mot_key(double x) {        // order-preserving: a < b  <=>  key(a) < key(b)   (no NaNs here)
-    const uint64_t b = (uint64_t)__double_as_longlong(x + 0.0);           // (-0.0 -> +0.0: scipy compares with ==)
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-// Wave-wide minima of unsigned keys: four DPP exchange steps inside each row of 16 lanes (quad_perm xor 1, xor 2,
-// row_half_mirror, row_mirror), then the four rows through v_readlane -- no LDS crossbar on the solver's scan.
-template <int CTRL>
-__device__ __forceinline__ uint32_t mot_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL>
-__device__ __forceinline__ uint64_t mot_min_step64(uint64_t x) {
-    const uint64_t y = ((uint64_t)mot_dpp<CTRL>((uint32_t)(x >> 32)) << 32) | mot_dpp<CTRL>((uint32_t)x);
-    return y < x ? y : x;
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t mot_min_step32(uint32_t x) { const uint32_t y = mot_dpp<CTRL>(x); return y < x ? y : x; }
-__device__ __forceinline__ uint64_t mot_wave_min64(uint64_t x) {
-    x = mot_min_step64<0xB1>(x);          // quad_perm [1,0,3,2]
-    x = mot_min_step64<0x4E>(x);          // quad_perm [2,3,0,1]
-    x = mot_min_step64<0x141>(x);         // row_half_mirror
-    x = mot_min_step64<0x140>(x);         // row_mirror: every lane of a row of 16 holds the row's minimum
-    uint64_t m = ~0ull;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const uint64_t y = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(x >> 32), 16 * r) << 32) | (uint32_t)__builtin_amdgcn_readlane((uint32_t)x, 16 * r);
-        m = y < m ? y : m;
-    }
-    return m;
-}
-__device__ __forceinline__ uint32_t mot_wave_min32(uint32_t x) {
-    x = mot_min_step32<0xB1>(x);
-    x = mot_min_step32<0x4E>(x);
-    x = mot_min_step32<0x141>(x);
-    x = mot_min_step32<0x140>(x);
-    uint32_t m = ~0u;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { const uint32_t y = (uint32_t)__builtin_amdgcn_readlane(x, 16 * r); m = y < m ? y : m; }
-    return m;
-}
-__device__ __forceinline__ double mot_readlane_f64(double x, int l) {
-    const long long b = __double_as_longlong(x);
-    return __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(b >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)b, l));
-}
-
 // The cost the solver sees: entry (row, col) of the problem is D[row * sr + col * sc] unless the object / hypothesis of the
 // pair was matched in step 1 or the distance is not finite -- then L.  (tr: the problem's rows are hypotheses.)
 struct MotCost {
@@ -141,107 +87,6 @@ struct MotCost {
         return (omatch[i] >= 0 || hmask[j] || !mot_finite(d)) ? L : d;
     }
 };
-
-// rows i < nr <= nc columns; result in S.col4row[0..nr); false when no augmenting path was found (cannot happen with finite costs)
-__device__ bool mot_wave_solve(MotShared& S, const MotCost& C, int nr, int nc, int lane) {
-    double v[MOT_K];
-    int r4c[MOT_K];
-#pragma unroll
-    for (int k = 0; k < MOT_K; ++k) { v[k] = 0.0; r4c[k] = -1; }
-    for (int i = lane; i < nr; i += 64) { S.u[i] = 0.0; S.col4row[i] = -1; }
-    mot_wave_sync();
-    const int KU = (nc + 63) >> 6;                        // column groups in use
-    for (int cur = 0; cur < nr; ++cur) {
-        double spc[MOT_K];
-        int path[MOT_K], pos[MOT_K];
-        bool alive[MOT_K], scj[MOT_K];
-#pragma unroll
-        for (int k = 0; k < MOT_K; ++k) {
-            const int j = lane + 64 * k;
-            spc[k] = __builtin_huge_val(); path[k] = -1; pos[k] = nc - 1 - j; alive[k] = j < nc; scj[k] = false;
-        }
-        for (int i = lane; i < nr; i += 64) S.SR[i] = 0;
-        mot_wave_sync();
-        int i = cur, sink = -1, num_rem = nc;
-        double min_val = 0.0;
-        while (sink < 0 && num_rem > 0) {
-            if (lane == 0) S.SR[i] = 1;
-            const double ui = S.u[i];
-            double m = __builtin_huge_val();
-#pragma unroll
-            for (int k = 0; k < MOT_K; ++k) {
-                if (k < KU && alive[k]) {
-                    const double r = min_val + C.at(i, lane + 64 * k) - ui - v[k];
-                    if (r < spc[k]) { path[k] = i; spc[k] = r; }
-                    m = spc[k] < m ? spc[k] : m;
-                }
-            }
-            // the minimum, then the scan's choice among the columns that attain it: an unassigned one if there is any (the one at
-            // the HIGHEST position of `remaining`), else the one at the lowest position -- one key: unassigned first
-            const uint64_t mk = mot_wave_min64(mot_key(m));
-            uint32_t sel = 0xFFFFFFFFu;
-#pragma unroll
-            for (int k = 0; k < MOT_K; ++k)
-                if (k < KU && alive[k] && mot_key(spc[k]) == mk) {
-                    const uint32_t q = r4c[k] == -1 ? (uint32_t)(MOT_MAX - 1 - pos[k]) : (uint32_t)(MOT_MAX + pos[k]);
-                    sel = q < sel ? q : sel;
-                }
-            sel = mot_wave_min32(sel);
-            if (sel == 0xFFFFFFFFu) return false;                // (no live column attains the minimum: never spin)
-            const int ipos = sel < (uint32_t)MOT_MAX ? MOT_MAX - 1 - (int)sel : (int)sel - MOT_MAX;
-            int jsel = -1, r4sel = -2;
-#pragma unroll
-            for (int k = 0; k < MOT_K; ++k) {
-                const bool mine = k < KU && alive[k] && pos[k] == ipos;
-                const unsigned long long bal = __ballot(mine);
-                if (bal) {                                       // (exactly one column sits at a position)
-                    const int src = __ffsll((long long)bal) - 1;
-                    jsel = src + 64 * k;
-                    r4sel = __builtin_amdgcn_readlane(r4c[k], src);
-                    m = mot_readlane_f64(spc[k], src);
-                }
-            }
-            if (jsel < 0) return false;
-            min_val = m;
-            if (r4sel == -1) sink = jsel; else i = r4sel;
-#pragma unroll
-            for (int k = 0; k < MOT_K; ++k) {
-                if (lane + 64 * k == jsel) { scj[k] = true; alive[k] = false; }
-                else if (alive[k] && pos[k] == num_rem - 1) pos[k] = ipos;
-            }
-            --num_rem;
-        }
-        if (sink < 0) return false;
-        // dual variables (with col4row as it was BEFORE the augmentation), then the augmentation along `path`
-#pragma unroll
-        for (int k = 0; k < MOT_K; ++k)
-            if (lane + 64 * k < nc) { S.spc[lane + 64 * k] = spc[k]; S.path[lane + 64 * k] = path[k]; }
-        mot_wave_sync();
-        for (int i2 = lane; i2 < nr; i2 += 64)
-            if (S.SR[i2]) S.u[i2] += (i2 == cur) ? min_val : (min_val - S.spc[S.col4row[i2]]);
-#pragma unroll
-        for (int k = 0; k < MOT_K; ++k)
-            if (scj[k]) v[k] -= min_val - spc[k];
-        mot_wave_sync();
-        int j = sink;
-        for (int step = 0;; ++step) {
-            if (step > nr) return false;                          // (a path visits a row once: never spin)
-            const int ip = S.path[j];
-            if (ip < 0 || ip >= nr) return false;
-#pragma unroll
-            for (int k = 0; k < MOT_K; ++k)
-                if (lane + 64 * k == j) r4c[k] = ip;
-            const int old = S.col4row[ip];
-            mot_wave_sync();
-            if (lane == 0) S.col4row[ip] = j;
-            mot_wave_sync();
-            j = old;
-            if (ip == cur) break;
-            if (j < 0 || j >= nc) return false;
-        }
-    }
-    return true;
-}
 
 struct MotSeq { int64_t gt_base, n_gt, det_base, n_det, off_base, n_frames, obj_base, n_obj; };
 // a sequence's slices of the store; false when one does not lie inside the store's totals: nothing may be indexed then (the host
@@ -304,7 +149,7 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
         }
         if (__ballot(bad)) { flag = FLAG_STORE; ok = false; }
         __threadfence();
-        mot_wave_sync();
+        wave_sync();
     }
     const int nF = ok ? (int)n_frames : 0;
     for (int f = 0; f < nF; ++f) {
@@ -333,7 +178,7 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
             S.oid[i] = o; S.obox[i] = gt_box[g0 + i]; S.omatch[i] = -1;
         }
         if (__ballot(bad)) { flag = FLAG_STORE | ((int64_t)(f + 1) << 8); break; }
-        mot_wave_sync();
+        wave_sync();
         // a hypothesis id twice in the frame: the host definition raises
         bool dup = false;
         for (int j = lane; j < nH; j += 64) {
@@ -347,7 +192,7 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
             double* D = nO * nH <= MOT_LDS_COST ? S.cost : gcost;
             double mx = -__builtin_huge_val();
             for (int x = lane; x < nO * nH; x += 64) D[x] = mot_dist(S.obox[x / nH], S.hbox[x % nH]);
-            mot_wave_sync();
+            wave_sync();
             // step 1: hypothesis ids are unique in the frame and so are the remembered ids of the objects matched at t - 1, so
             // the rows are independent and a lane per row gives the sequential result
             for (int i = lane; i < nO; i += 64) {
@@ -359,14 +204,14 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
                     if (j >= 0 && mot_finite(D[i * nH + j])) { S.omatch[i] = j; S.hmask[j] = 1; last[o] = t; }
                 }
             }
-            mot_wave_sync();
+            wave_sync();
             // step 2: the largest finite distance that is left, then the assignment over the L-filled matrix
             for (int x = lane; x < nO * nH; x += 64) {
                 const double d = D[x];
                 if (S.omatch[x / nH] < 0 && !S.hmask[x % nH] && mot_finite(d)) mx = d > mx ? d : mx;
             }
-            const uint64_t mxk = ~mot_wave_min64(~mot_key(mx));
-            if (mxk != mot_key(-__builtin_huge_val())) {
+            const uint64_t mxk = ~wave_min64(~key_f64(mx));
+            if (mxk != key_f64(-__builtin_huge_val())) {
                 // (undo the key map: the maximum itself, bit for bit)
                 const uint64_t b = (mxk >> 63) ? (mxk & 0x7fffffffffffffffull) : ~mxk;
                 mx = __longlong_as_double((long long)b);
@@ -377,8 +222,8 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
                 C.L = (double)(2 * (tr ? nH : nO)) * (mx + 1.0) + 1.0;
                 const int nr = tr ? nH : nO, nc = tr ? nO : nH;
                 // the solver must see the masks of step 1 only: its matches are collected first and applied afterwards
-                if (!mot_wave_solve(S, C, nr, nc, lane)) { flag = FLAG_SOLVER | ((int64_t)(f + 1) << 8); break; }
-                mot_wave_sync();
+                if (!wave_lsap_solve(S.L, C, nr, nc, lane)) { flag = FLAG_SOLVER | ((int64_t)(f + 1) << 8); break; }
+                wave_sync();
                 int sw = 0;
                 int newj[MOT_K];
 #pragma unroll
@@ -386,12 +231,12 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
                     newj[k] = -1;
                     const int r = lane + 64 * k;
                     if (r < nr) {
-                        const int c = S.col4row[r];
+                        const int c = S.L.col4row[r];
                         const int i = tr ? c : r, j = tr ? r : c;
                         if (c >= 0 && c < nc && S.omatch[i] < 0 && !S.hmask[j] && mot_finite(D[i * nH + j])) newj[k] = (i << 16) | j;
                     }
                 }
-                mot_wave_sync();
+                wave_sync();
 #pragma unroll
                 for (int k = 0; k < MOT_K; ++k)
                     if (newj[k] >= 0) {
@@ -400,7 +245,7 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
                         m[o] = h; last[o] = t;
                         S.omatch[i] = j; S.hmask[j] = 1;
                     }
-                mot_wave_sync();
+                wave_sync();
                 for (int d = 32; d >= 1; d >>= 1) sw += __shfl_xor(sw, d);
                 switches += sw;
             }
@@ -425,11 +270,11 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
                 } else if (state[o] == 1) state[o] = 2;
             }
         }
-        mot_wave_sync();
+        wave_sync();
     }
     int64_t mt = 0, pt = 0, ml = 0, fr = 0;
     if constexpr (IDENT) {
-        mot_wave_sync();
+        wave_sync();
         for (int64_t o = lane; o < n_walk; o += 64) {
             const int p = present[o];
             if (p > 0) {

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "graphconv_dev.h"
 #include "small_bn_dev.h"
+#include "wave_lsap.h"
 
 namespace tmpnn {
 
@@ -37,19 +38,13 @@ __device__ __forceinline__ int tk_block_scan(int v, int* s_wave, int* total) { r
 // Swept in ascending timestep t over the timesteps that edges lead into.  Rows of the problem: the dets with an edge into t
 // that are still unassociated (ascending graph row -- np.unique), columns: EVERY det of timestep t (ascending row), cost
 // 1 - score of the edge (fp32), 100 where there is none; an assignment is kept where its cost is <= 0.5.  The solver is scipy's
-// linear_sum_assignment (scipy/optimize/rectangular_lsap/rectangular_lsap.cpp: shortest augmenting paths in fp64, the matrix
-// transposed when it has more rows than columns) restated step for step, INCLUDING how it breaks ties, because which of several
-// optimal assignments comes out decides the tracks: the scan over the `remaining` columns keeps the first column of minimal
-// reduced cost unless a later one of equal cost is unassigned (then the last such), and `remaining` is filled in reverse and
-// compacted by moving its last entry into the hole.  One wave runs a problem: lane l owns columns l, l + 64, ... (reduced costs,
-// duals, path, position in `remaining` in registers), the row state lives in LDS; the scan's sequential rule is two wave
-// reductions over positions.  Problems of up to HG_MAX rows / columns; cost matrices of up to HG_LDS_COST entries in LDS, larger
-// ones in the caller's scratch.
-static constexpr int HG_MAX = 256, HG_K = HG_MAX / 64, HG_LDS_COST = 4096;
+// linear_sum_assignment with its tie rules, one wave per problem (csrc/wave_lsap.h: which of several optimal assignments comes
+// out decides the tracks); the matrix is transposed when it has more rows than columns, as scipy does.  Problems of up to HG_MAX
+// rows / columns; cost matrices of up to HG_LDS_COST entries in LDS, larger ones in the caller's scratch.
+static constexpr int HG_MAX = 256, HG_LDS_COST = 4096;
 struct HgShared {
-    double u[HG_MAX], spc[HG_MAX];
-    int col4row[HG_MAX], path[HG_MAX], rowlist[HG_MAX];
-    unsigned char SR[HG_MAX];
+    LsapShared<HG_MAX> L;
+    int rowlist[HG_MAX];
     float cost[HG_LDS_COST];
     unsigned char flag[4096];
     short ridx[4096];
@@ -68,72 +63,6 @@ struct HgMemo {
     int t[HG_MEMO_T], nr[HG_MEMO_T], nc[HG_MEMO_T], d0[HG_MEMO_T];
     short rows[HG_MEMO_T][HG_MEMO_R], assign[HG_MEMO_T][HG_MEMO_R];    // det index of a row; det index it was associated with, -1 none
 };
-__device__ __forceinline__ void hg_wave_sync() {          // LDS writes of this wave visible to its other lanes (one wave only)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-// Wave-wide minima without the LDS crossbar (__shfl_xor is a ds_bpermute: ~120 cycles a step, five reductions per scan made a
-// scan ~3600 cycles): four DPP exchange steps inside each row of 16 lanes (quad_perm xor 1, xor 2, row_half_mirror,
-// row_mirror), then the four rows through v_readlane and the scalar unit.  Keys are unsigned: a double goes through the usual
-// order-preserving map of its bits.
-template <int CTRL>
-__device__ __forceinline__ uint32_t hg_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL>
-__device__ __forceinline__ uint64_t hg_min_step64(uint64_t x) {
-    const uint64_t y = ((uint64_t)hg_dpp<CTRL>((uint32_t)(x >> 32)) << 32) | hg_dpp<CTRL>((uint32_t)x);
-    return y < x ? y : x;
-}
-// ROWS: rows of 16 lanes that can hold a live key (problems of <= 16 columns: the first row alone -- three pairs of v_readlane less)
-template <int ROWS = 4>
-__device__ __forceinline__ uint64_t hg_wave_min64(uint64_t x) {
-    x = hg_min_step64<0xB1>(x);          // quad_perm [1,0,3,2]
-    x = hg_min_step64<0x4E>(x);          // quad_perm [2,3,0,1]
-    x = hg_min_step64<0x141>(x);         // row_half_mirror
-    x = hg_min_step64<0x140>(x);         // row_mirror: every lane of a row of 16 holds the row's minimum
-    uint64_t m = ~0ull;
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-        const uint64_t y = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(x >> 32), 16 * r) << 32) | (uint32_t)__builtin_amdgcn_readlane((uint32_t)x, 16 * r);
-        m = y < m ? y : m;
-    }
-    return m;
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t hg_min_step32(uint32_t x) { const uint32_t y = hg_dpp<CTRL>(x); return y < x ? y : x; }
-template <int ROWS = 4>
-__device__ __forceinline__ uint32_t hg_wave_min32(uint32_t x) {
-    x = hg_min_step32<0xB1>(x);
-    x = hg_min_step32<0x4E>(x);
-    x = hg_min_step32<0x141>(x);
-    x = hg_min_step32<0x140>(x);
-    uint32_t m = ~0u;
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) { const uint32_t y = (uint32_t)__builtin_amdgcn_readlane(x, 16 * r); m = y < m ? y : m; }
-    return m;
-}
-// minima over a ROW of 16 lanes (the four DPP steps alone: every lane of the row ends up with its row's minimum)
-__device__ __forceinline__ uint32_t hg_row_min32(uint32_t x) {
-    x = hg_min_step32<0xB1>(x);
-    x = hg_min_step32<0x4E>(x);
-    x = hg_min_step32<0x141>(x);
-    return hg_min_step32<0x140>(x);
-}
-__device__ __forceinline__ uint64_t hg_row_min64(uint64_t x) {
-    x = hg_min_step64<0xB1>(x);
-    x = hg_min_step64<0x4E>(x);
-    x = hg_min_step64<0x141>(x);
-    return hg_min_step64<0x140>(x);
-}
-__device__ __forceinline__ uint64_t hg_key(double x) {        // order-preserving: a < b  <=>  key(a) < key(b)   (no NaNs here)
-    const uint64_t b = (uint64_t)__double_as_longlong(x + 0.0);           // (-0.0 -> +0.0: scipy compares with ==)
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ int hg_wave_min_i(int x) {          // (block-level helper of the sweep: ints >= 0 or INT_MAX)
-    return (int)hg_wave_min32((uint32_t)x);
-}
 // ---- y_pred[:, 2] ------------------------------------------------------------------------------------------
 // mode 0 (train, utils/graph.py:229-245): a true-positive det is associated through its ONE label-positive future
 //   edge (more than one: status bit 1); a false positive is "associated" with itself so that it stays inactive.
@@ -172,9 +101,9 @@ __device__ __forceinline__ void d_track_associate(tmpnn_dgraph g, const int32_t*
                             if (score[key] >= 0.5f && score[g.dst[cpos]] >= 0.5f) cand = key;
                         }
                     }
-                    first = (int)hg_row_min32((uint32_t)cand);
+                    first = (int)row_min32((uint32_t)cand);
                     // (its index among the edge rows rides along: the lane that holds `first` hands it to the group)
-                    first_pos = (int)hg_row_min32(cand == first ? (uint32_t)cpos : 0xFFFFFFFFu);
+                    first_pos = (int)row_min32(cand == first ? (uint32_t)cpos : 0xFFFFFFFFu);
                 }
                 if (first != 0x7fffffff) {
                     // first det row after `first`: `first` has first - pos[first] det rows in front of it (pos = its index among
@@ -195,7 +124,7 @@ __device__ __forceinline__ void d_track_associate(tmpnn_dgraph g, const int32_t*
                                     k = ((uint64_t)__float_as_uint(sc) << 32) | (uint32_t)(0x7fffffff - key);
                             }
                         }
-                        k = ~hg_row_min64(~k);
+                        k = ~row_min64(~k);
                         bestk = k > bestk ? k : bestk;
                     }
                     if (bestk) out = det_id[g.dst[g.pos[0x7fffffff - (int)(uint32_t)bestk]]];
@@ -228,167 +157,18 @@ __global__ __launch_bounds__(256) void k_track_associate(tmpnn_dgraph g, const i
     d_track_associate(g, det_id, labels, score, mode, assoc, status, (int)(blockIdx.x * 256 + threadIdx.x), (int)(gridDim.x * 256));
 }
 
-// rows i < nr <= nc columns; cost(i, j) = C[i * sr + j * sc]; result in S.col4row[0..nr)
-__device__ void hg_wave_solve(HgShared& S, const float* C, int sr, int sc, int nr, int nc, int lane) {
-    double v[HG_K];
-    int r4c[HG_K];
-#pragma unroll
-    for (int k = 0; k < HG_K; ++k) { v[k] = 0.0; r4c[k] = -1; }
-    for (int i = lane; i < nr; i += 64) { S.u[i] = 0.0; S.col4row[i] = -1; }
-    hg_wave_sync();
-    const int KU = (nc + 63) >> 6;                        // column groups in use
-    for (int cur = 0; cur < nr; ++cur) {
-        double spc[HG_K];
-        int path[HG_K], pos[HG_K];
-        bool alive[HG_K], scj[HG_K];
-#pragma unroll
-        for (int k = 0; k < HG_K; ++k) {
-            const int j = lane + 64 * k;
-            spc[k] = __builtin_huge_val(); path[k] = -1; pos[k] = nc - 1 - j; alive[k] = j < nc; scj[k] = false;
-        }
-        for (int i = lane; i < nr; i += 64) S.SR[i] = 0;
-        hg_wave_sync();
-        int i = cur, sink = -1, num_rem = nc;
-        double min_val = 0.0;
-        while (sink < 0 && num_rem > 0) {
-            if (lane == 0) S.SR[i] = 1;
-            const double ui = S.u[i];
-            double m = __builtin_huge_val();
-#pragma unroll
-            for (int k = 0; k < HG_K; ++k) {
-                if (k < KU && alive[k]) {
-                    const double c = (double)C[(size_t)i * sr + (size_t)(lane + 64 * k) * sc];
-                    const double r = min_val + c - ui - v[k];
-                    if (r < spc[k]) { path[k] = i; spc[k] = r; }
-                    m = spc[k] < m ? spc[k] : m;
-                }
-            }
-            // the minimum, then the scan's choice among the columns that attain it: an unassigned one if there is any (the one at
-            // the HIGHEST position of `remaining`), else the one at the lowest position -- one key: unassigned first
-            const uint64_t mk = hg_wave_min64(hg_key(m));
-            uint32_t sel = 0xFFFFFFFFu;
-#pragma unroll
-            for (int k = 0; k < HG_K; ++k)
-                if (k < KU && alive[k] && hg_key(spc[k]) == mk) {
-                    const uint32_t q = r4c[k] == -1 ? (uint32_t)(HG_MAX - 1 - pos[k]) : (uint32_t)(HG_MAX + pos[k]);
-                    sel = q < sel ? q : sel;
-                }
-            sel = hg_wave_min32(sel);
-            const int ipos = sel < (uint32_t)HG_MAX ? HG_MAX - 1 - (int)sel : (int)sel - HG_MAX;
-            int jsel = -1, r4sel = -2;
-#pragma unroll
-            for (int k = 0; k < HG_K; ++k) {
-                const bool mine = k < KU && alive[k] && pos[k] == ipos;
-                const unsigned long long bal = __ballot(mine);
-                if (bal) {                                       // (exactly one column sits at a position)
-                    const int src = __ffsll((long long)bal) - 1;
-                    jsel = src + 64 * k;
-                    r4sel = __builtin_amdgcn_readlane(r4c[k], src);
-                    m = __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(__double_as_longlong(spc[k]) >> 32), src) << 32) |
-                                             (unsigned)__builtin_amdgcn_readlane((int)__double_as_longlong(spc[k]), src));
-                }
-            }
-            min_val = m;
-            if (r4sel == -1) sink = jsel; else i = r4sel;
-#pragma unroll
-            for (int k = 0; k < HG_K; ++k) {
-                if (lane + 64 * k == jsel) { scj[k] = true; alive[k] = false; }
-                else if (alive[k] && pos[k] == num_rem - 1) pos[k] = ipos;
-            }
-            --num_rem;
-        }
-        if (sink < 0) { if (lane == 0) S.nr = -1; return; }        // (cannot happen with nr <= nc and finite costs: never spin)
-        // dual variables (with col4row as it was BEFORE the augmentation), then the augmentation along `path`
-#pragma unroll
-        for (int k = 0; k < HG_K; ++k)
-            if (lane + 64 * k < nc) { S.spc[lane + 64 * k] = spc[k]; S.path[lane + 64 * k] = path[k]; }
-        hg_wave_sync();
-        for (int i2 = lane; i2 < nr; i2 += 64)
-            if (S.SR[i2]) S.u[i2] += (i2 == cur) ? min_val : (min_val - S.spc[S.col4row[i2]]);
-#pragma unroll
-        for (int k = 0; k < HG_K; ++k)
-            if (scj[k]) v[k] -= min_val - spc[k];
-        hg_wave_sync();
-        int j = sink;
-        for (;;) {
-            const int ip = S.path[j];
-#pragma unroll
-            for (int k = 0; k < HG_K; ++k)
-                if (lane + 64 * k == j) r4c[k] = ip;
-            const int old = S.col4row[ip];
-            hg_wave_sync();
-            if (lane == 0) S.col4row[ip] = j;
-            hg_wave_sync();
-            j = old;
-            if (ip == cur) break;
-        }
-    }
-}
-
-// The same solver for problems of <= 64 columns (every KITTI / BDD frame): lane l is column l AND row l, all state in registers, the
-// only LDS traffic is the cost row of a scan; rows and columns are addressed with v_readlane / ballots instead of LDS arrays.
-__device__ __forceinline__ double hg_readlane_f64(double x, int l) {
-    const long long b = __double_as_longlong(x);
-    return __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(b >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)b, l));
-}
-template <int ROWS>
-__device__ void hg_wave_solve64(HgShared& S, const float* C, int sr, int sc, int nr, int nc, int lane) {
-    double v = 0.0, u = 0.0;
-    int r4c = -1, c4r = -1;
-    for (int cur = 0; cur < nr; ++cur) {
-        double spc = __builtin_huge_val();
-        int path = -1, pos = nc - 1 - lane;
-        bool alive = lane < nc, scj = false;
-        unsigned long long sr_mask = 0;
-        int i = cur, sink = -1, num_rem = nc;
-        double min_val = 0.0;
-        while (sink < 0 && num_rem > 0) {
-            i = __builtin_amdgcn_readfirstlane(i);
-            sr_mask |= 1ull << i;
-            const double ui = hg_readlane_f64(u, i);
-            if (alive) {
-                const double c = (double)C[(size_t)i * sr + (size_t)lane * sc];
-                const double r = min_val + c - ui - v;
-                if (r < spc) { path = i; spc = r; }
-            }
-            const uint64_t mk = hg_wave_min64<ROWS>(alive ? hg_key(spc) : ~0ull);
-            uint32_t sel = 0xFFFFFFFFu;
-            if (alive && hg_key(spc) == mk) sel = r4c == -1 ? (uint32_t)(HG_MAX - 1 - pos) : (uint32_t)(HG_MAX + pos);
-            sel = hg_wave_min32<ROWS>(sel);
-            const int ipos = sel < (uint32_t)HG_MAX ? HG_MAX - 1 - (int)sel : (int)sel - HG_MAX;
-            const unsigned long long bal = __ballot(alive && pos == ipos);
-            const int jsel = __ffsll((long long)bal) - 1;           // (exactly one column sits at a position)
-            const int r4sel = __builtin_amdgcn_readlane(r4c, jsel);
-            min_val = hg_readlane_f64(spc, jsel);
-            if (r4sel == -1) sink = jsel; else i = r4sel;
-            if (lane == jsel) { scj = true; alive = false; }
-            else if (alive && pos == num_rem - 1) pos = ipos;
-            --num_rem;
-        }
-        if (sink < 0) { if (lane == 0) S.nr = -1; return; }          // (cannot happen with nr <= nc and finite costs: never spin)
-        // dual variables (with the assignment as it was BEFORE the augmentation): row l needs the reduced cost of ITS column
-        const double spc_mine = __shfl(spc, c4r < 0 ? 0 : c4r);
-        if ((sr_mask >> lane) & 1ull) u += (lane == cur) ? min_val : (min_val - spc_mine);
-        if (scj) v -= min_val - spc;
-        int j = sink;
-        for (;;) {
-            const int ip = __builtin_amdgcn_readlane(path, j);
-            if (lane == j) r4c = ip;
-            const int old = __builtin_amdgcn_readlane(c4r, ip);
-            if (lane == ip) c4r = j;
-            j = old;
-            if (ip == cur) break;
-        }
-    }
-    if (lane < nr) S.col4row[lane] = c4r;
-}
+// The cost the solver sees: entry (row, col) of the problem over the sweep's fp32 matrix (the strides transpose it).
+struct HgCost {
+    const float* C;
+    int sr, sc;
+    __device__ __forceinline__ double at(int row, int col) const { return (double)C[(size_t)row * sr + (size_t)col * sc]; }
+};
 
 // the whole sweep, one block of TK_THREADS threads, graphs of <= FIN_LDS_DETS rows with <= HG_MAX dets per problem; status bit 2:
 // a problem exceeded HG_MAX or the scratch (the associations are then incomplete: the host falls back to its own matching).
 // What a timestep's passes need of an edge (the timestep it leads into, its endpoints' det indices, its cost) and of a det (its
 // timestep) is read ONCE into registers (four edges / dets per thread): a pass is then LDS and register work, not a chain of
 // dependent global loads per timestep; the result is kept per det index in LDS and written out once at the end.
-#define HG_STAMP(i) do { } while (0)
 __device__ void d_track_hungarian(tmpnn_dgraph g, const int32_t* __restrict__ ts, const int32_t* __restrict__ det_id,
                                   const float* __restrict__ score, int32_t* __restrict__ assoc, int32_t* __restrict__ status,
                                   float* __restrict__ cost_ws, int cost_ws_floats, const int* remap = nullptr, int n_out = 0,
@@ -426,13 +206,12 @@ __device__ void d_track_hungarian(tmpnn_dgraph g, const int32_t* __restrict__ ts
     for (int d = tid; d < Dn; d += TK_THREADS) S.flag[d] = 0;
     __syncthreads();
     for (;;) {
-        HG_STAMP(8);
         // the next timestep that edges lead into; its dets are a contiguous run of the det list (rows are in time order)
         {
             int m = 0x7fffffff;
 #pragma unroll
             for (int k = 0; k < PER; ++k) if (e_t[k] > t_done && e_t[k] < m) m = e_t[k];
-            m = hg_wave_min_i(m);
+            m = (int)wave_min32((uint32_t)m);                 // (ints >= 0 or INT_MAX)
             if ((tid & 63) == 0 && m != 0x7fffffff) atomicMin(&S.tnext, m);
         }
         __syncthreads();
@@ -500,30 +279,25 @@ __device__ void d_track_hungarian(tmpnn_dgraph g, const int32_t* __restrict__ ts
         __threadfence_block();
         __syncthreads();
         const bool tr = nc < nr;                              // (scipy transposes a tall matrix)
-        HG_STAMP(5);
         if (tid < 64) {
+            const HgCost Ct{C, 1, nc}, Cn{C, nc, 1};         // (transposed: the problem's rows are the matrix's columns)
+            bool ok;
             if (max(nr, nc) <= 64) {
-                // (the solver's columns: the longer side; lanes beyond them never hold a live key)
-                if (max(nr, nc) <= 16) {
-                    if (tr) hg_wave_solve64<1>(S, C, 1, nc, nc, nr, tid);
-                    else hg_wave_solve64<1>(S, C, nc, 1, nr, nc, tid);
-                } else {
-                    if (tr) hg_wave_solve64<4>(S, C, 1, nc, nc, nr, tid);
-                    else hg_wave_solve64<4>(S, C, nc, 1, nr, nc, tid);
-                }
+                // the register solver (every KITTI / BDD frame); its columns are the longer side, lanes beyond them never hold a
+                // live key
+                if (max(nr, nc) <= 16) ok = tr ? wave_lsap_solve64<1>(S.L, Ct, nc, nr, tid) : wave_lsap_solve64<1>(S.L, Cn, nr, nc, tid);
+                else ok = tr ? wave_lsap_solve64<4>(S.L, Ct, nc, nr, tid) : wave_lsap_solve64<4>(S.L, Cn, nr, nc, tid);
             } else {
-                if (tr) hg_wave_solve(S, C, 1, nc, nc, nr, tid);
-                else hg_wave_solve(S, C, nc, 1, nr, nc, tid);
+                ok = tr ? wave_lsap_solve(S.L, Ct, nc, nr, tid) : wave_lsap_solve(S.L, Cn, nr, nc, tid);
             }
+            if (!ok && tid == 0) S.nr = -1;                   // (status bit 2 below)
         }
-        HG_STAMP(6);
         __threadfence_block();
         __syncthreads();
-        HG_STAMP(7);
         if (S.nr < 0) { if (tid == 0) atomicOr(status, 2); __syncthreads(); continue; }
         const int na = tr ? nc : nr;
         for (int i = tid; i < na; i += TK_THREADS) {
-            const int j = S.col4row[i];
+            const int j = S.L.col4row[i];
             const int pr = tr ? j : i, cu = tr ? i : j;          // (row of the problem = prev det, column = det of timestep t)
             if (C[pr * nc + cu] <= 0.5f) {
                 S.ad[S.rowlist[pr]] = (short)(d0 + cu);
@@ -948,7 +722,7 @@ __device__ __forceinline__ void d_track_finalize(tmpnn_dgraph g, const int32_t* 
                 jump[k] = nk > k ? nk : -1;
                 if (s_flag[k] & 1) s_flag[k] |= 4;
             }
-            hg_wave_sync();
+            wave_sync();
             for (;;) {
                 int more = 0;
                 for (int k = lane; k < Dn; k += 64) {
@@ -960,14 +734,14 @@ __device__ __forceinline__ void d_track_finalize(tmpnn_dgraph g, const int32_t* 
                         more |= jj >= 0 ? 1 : 0;
                     }
                 }
-                hg_wave_sync();
+                wave_sync();
                 if (__ballot(more != 0) == 0) break;
             }
             for (int k = lane; k < Dn; k += 64) {
                 const int nk = s_next[k];
                 if (nk > k && (s_flag[k] & 4)) s_flag[nk] |= 2;
             }
-            hg_wave_sync();
+            wave_sync();
             int run = s_max + 1;                                        // next free track id
             for (int base = 0; base < Dn; base += 64) {
                 const int k = base + lane;
@@ -983,7 +757,7 @@ __device__ __forceinline__ void d_track_finalize(tmpnn_dgraph g, const int32_t* 
                 }
                 run += __popcll(bal);
             }
-            hg_wave_sync();
+            wave_sync();
             for (;;) {
                 int more = 0;
                 for (int k = lane; k < Dn; k += 64) {
@@ -996,7 +770,7 @@ __device__ __forceinline__ void d_track_finalize(tmpnn_dgraph g, const int32_t* 
                         more |= jj >= 0 ? 1 : 0;
                     }
                 }
-                hg_wave_sync();
+                wave_sync();
                 if (__ballot(more != 0) == 0) break;
             }
         }
