@@ -158,8 +158,10 @@ def test_update_rule_on_the_gradients_of_training_chunks(name):
     from trackmpnn_amd import BucketAdam
     from trackmpnn_amd.dist import GradBucket
     from trackmpnn_amd.loops import train_chunk
+    from tests.golden_util import chunk_tp
     gold = Golden(name)
     X, y = gold.t('X'), gold.t('y')
+    tp = chunk_tp(gold)             # (a *_notp fixture: the node output head's gradient is zero in every step)
     # record: the gradients of 10 consecutive training steps, taken from the bucket before each step
     model = _chunk_model(gold)
     bucket = GradBucket(model)
@@ -168,7 +170,7 @@ def test_update_rule_on_the_gradients_of_training_chunks(name):
     grads = []
     for _ in range(10):
         opt.zero_grad()
-        train_chunk(model, X, y, DEV)
+        train_chunk(model, X, y, DEV, tp)
         grads.append(bucket.flat.detach().cpu().clone())
         opt.step()
     assert all(bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0 for g in grads)

@@ -144,9 +144,16 @@ def test_committed_fixtures_regenerate_from_the_reference(tmp_path):
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
     subprocess.run([sys.executable, os.path.join(root, 'oracle', 'gen_golden.py'), '--reference-path', REFERENCE,
                     '--out', str(tmp_path)], check=True, env=env, cwd=root, stdout=subprocess.DEVNULL)
-    committed = sorted(glob.glob(os.path.join(root, 'tests', 'golden', '*.npz')))
-    fresh = sorted(glob.glob(os.path.join(str(tmp_path), '*.npz')))
-    assert [os.path.basename(f) for f in fresh] == [os.path.basename(f) for f in committed]
+    # (parts/: the arrays a fixture keeps in a file of their own, tests/golden_util.Golden)
+    committed = sorted(glob.glob(os.path.join(root, 'tests', 'golden', '*.npz')) +
+                       glob.glob(os.path.join(root, 'tests', 'golden', 'parts', '*.npz')))
+    fresh = sorted(glob.glob(os.path.join(str(tmp_path), '*.npz')) + glob.glob(os.path.join(str(tmp_path), 'parts', '*.npz')))
+    rel = lambda fs, base: [os.path.relpath(f, base) for f in fs]
+    assert rel(fresh, str(tmp_path)) == rel(committed, os.path.join(root, 'tests', 'golden'))
+    for f in committed:                                     # what the parts are for: each file of a split fixture under 1 MiB
+        if os.path.basename(os.path.dirname(f)) == 'parts':
+            base = os.path.join(root, 'tests', 'golden', os.path.basename(f).split('.')[0] + '.npz')
+            assert os.path.getsize(f) < 2 ** 20 and os.path.getsize(base) < 2 ** 20, f
     for fc, ff in zip(committed, fresh):
         a, b = np.load(fc, allow_pickle=False), np.load(ff, allow_pickle=False)
         assert sorted(a.files) == sorted(b.files), os.path.basename(fc)

@@ -247,13 +247,21 @@ def test_train_chunks_equals_train_chunk_one_by_one(tp, monkeypatch):
 
 
 @pytest.mark.parametrize('name', chunk_golden_names())
-def test_reference_chunk_inside_a_batch(name, monkeypatch):
+def test_reference_chunk_inside_a_batch(name):
+    """A chunk the real reference ran (fixture chunk_*), in the fixture's mode (with the TP classifier or without), as one
+    window of a 17-chunk batch: the windowed loss's terms of every call within 1e-4 relative of the reference's, the targets it
+    wrote equal to the reference's create_targets on every row the window lists, the window's scores closer to the reference's
+    than the fixture's min_margin and its counts equal to the reference's tp / fp / fn, the gradients of the window's loss alone.
+    Then as a batch of one through train_chunks with a monitor: loss_c, loss_f and the total, gradients (a parameter the
+    reference leaves at zero holds a zero tensor), BatchNorm buffers, and the windowed counts of every call against the
+    reference's tp / fp / fn."""
+    from tests.golden_util import assert_chunk_buffers, assert_chunk_grads, chunk_tp
     from tests.test_parity_gpu import build_model
-    from trackmpnn_amd import build_train_batch, loops, train_losses_windows
+    from trackmpnn_amd import TrainMonitor, build_train_batch, classification_counts_windows, train_losses_windows
     from trackmpnn_amd.functional import weight_cache
     from trackmpnn_amd.loops import train_chunks
     gold = Golden(name)
-    m = gold.meta
+    m, tp = gold.meta, chunk_tp(gold)
     X, y = gold.t('X')[0], gold.t('y')[0].numpy()
     ys = _mixed_chunks(16, seed=61)
     ys[8] = _chunks(1, seed=62)[0]                               # (no skipped chunk here: 16 kept)
@@ -268,41 +276,50 @@ def test_reference_chunk_inside_a_batch(name, monkeypatch):
     model = build_model(dict(m, mode='train'), gold.params())
     # the loop by hand, keeping every call's per-window terms; then the backward of the fixture window's loss alone
     Xz = batch.stacked_features([x.to(DEV) for x in Xs])
-    h, acc_c, acc_f, per_call = None, 0, 0, []
+    h, acc_c, acc_f, per_call, worst = None, 0, 0, [], 0.0
     with weight_cache():
         for c, plan in enumerate(batch.plans):
             nxt = batch.plans[c + 1].n_new if c + 1 < len(batch.plans) else 0
             scores, logits, h, _ = model.forward_graph(Xz.index_select(0, batch.feat_src[c]), h, plan, reserve_rows=nxt)
-            lc, lf = train_losses_windows(scores, logits, batch.call_labels(c), plan, batch.windows[c], True)
-            per_call.append((float(lc[b]), float(lf[b])))
+            lc, lf, targets = train_losses_windows(scores, logits, batch.call_labels(c), plan, batch.windows[c], tp,
+                                                   return_targets=True)
+            per_call.append((float(lc[b].detach()), float(lf[b].detach())))
             acc_c, acc_f = acc_c + lc, acc_f + lf
+            if c < m['ncalls']:
+                rows, _ = _subgraph(plan, batch.windows[c], b)      # the window's rows ascending = the chunk's own row order
+                assert torch.equal(targets[rows].cpu(), gold.t(f'c{c}/targets')), c
+                # scores closer to the reference's than the smallest |score - 0.5| it counted: the same predictions, so the
+                # same counts
+                worst = max(worst, float((scores.detach()[rows, 0].cpu() - gold.t(f'c{c}/scores')).abs().max()))
+                cnt = classification_counts_windows(scores, targets, plan, batch.windows[c], tp)[:, b].cpu().numpy()
+                assert tuple(cnt[:3]) == tuple(gold.d['counts'][c]) and cnt[3] == rows.numel(), (c, cnt, gold.d['counts'][c])
+    print(f'{name}: max |score - reference score| {worst:.2e}, min_margin {m["min_margin"]:.2e}')
+    # (worst < min_margin carries the weight: the margins of the fixtures committed first are below 1e-4)
+    assert worst < m['min_margin'] and worst <= 1e-4, (worst, m['min_margin'])
     model.zero_grad(set_to_none=True)
     (acc_c[b] + acc_f[b]).backward()
     ref = gold.d['per_call']
     for c in range(m['ncalls']):
         for k in range(2):
             assert abs(per_call[c][k] - ref[c, k]) <= 1e-4 * abs(ref[c, k]), (c, k, per_call[c][k], ref[c, k])
-    gmax = max(float(np.abs(gold.d['grad/' + k]).max()) for k, _ in model.named_parameters())
-    for k, p in model.named_parameters():
-        err = float((p.grad.cpu() - gold.t('grad/' + k)).abs().max())
-        assert err <= 2e-4 * gmax, (k, err, gmax)
+    assert_chunk_grads(model, gold)
     # B = 1: train_chunks is the reference's schedule -- loss, gradients and the BatchNorm buffers after the chunk
     model = build_model(dict(m, mode='train'), gold.params())
     one = build_train_batch([y], DEV)
     model.zero_grad(set_to_none=True)
-    loss, per_chunk, ncalls, _ = train_chunks(model, one, X.to(DEV))
+    mon = TrainMonitor(DEV)
+    loss, per_chunk, ncalls, _ = train_chunks(model, one, X.to(DEV), tp, monitor=mon)
     assert ncalls == m['ncalls']
-    ref_total = float(gold.d['loss_c']) + float(gold.d['loss_f'])
-    assert abs(float(loss.detach()) - ref_total) <= 1e-4 * abs(ref_total)
-    for k, p in model.named_parameters():
-        err = float((p.grad.cpu() - gold.t('grad/' + k)).abs().max())
-        assert err <= 2e-4 * gmax, (k, err, gmax)
-    for k, buf in model.named_buffers():
-        r = gold.t('buf_after/' + k)
-        if buf.dtype.is_floating_point:
-            assert float((buf.cpu() - r).abs().max()) <= 1e-5 * max(1.0, float(r.abs().max())), k
-        else:
-            assert int(buf) == int(r), k
+    ref_c, ref_f = float(gold.d['loss_c']), float(gold.d['loss_f'])
+    assert abs(float(loss.detach()) - (ref_c + ref_f)) <= 1e-4 * abs(ref_c + ref_f)
+    assert tuple(per_chunk.shape) == (1, 2)
+    for got, r in zip(per_chunk[0].tolist(), (ref_c, ref_f)):
+        assert abs(got - r) <= 1e-4 * abs(r), (got, r)
+    assert_chunk_grads(model, gold)
+    assert_chunk_buffers(model, gold)
+    counts = mon.last_counts.cpu().numpy()
+    assert counts.shape == (m['ncalls'], 4, 1)
+    assert np.array_equal(counts[:, :3, 0], gold.d['counts']) and np.array_equal(counts[:, 3, 0], ref[:, 2].astype(np.int64))
 
 
 def _b1_cases():
@@ -312,7 +329,7 @@ def _b1_cases():
     return out
 
 
-@pytest.mark.parametrize('case', range(4))
+@pytest.mark.parametrize('case', range(len(chunk_golden_names()) + 2))
 def test_batch_of_one_equals_track_graph(case):
     """At B = 1 every call's graph and labels are the ones train_chunk's composition (TrackGraph, mode='train') produces."""
     from trackmpnn_amd import TrackGraph, build_train_batch

@@ -2,7 +2,7 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from tests.conftest import golden_names
+from tests.conftest import chunk_golden_names, golden_names
 from tests.golden_util import Golden
 from tests.test_parity_gpu import build_model, DEV
 from trackmpnn_amd import graph_from_adjacency, plan_single
@@ -39,3 +39,29 @@ for name in golden_names():
     worst = max(((prm.grad.cpu() - grads[k]).abs().max().item() / gscale, k) for k, prm in model.named_parameters())
     print(f'{name:40s} score {max(es):.1e} logit {max(el):.1e} (rel {max(ml):.1e}) h {max(eh):.1e} '
           f'loss {abs(loss.item()-float(gold.d["loss"])):.1e} grad/gmax {worst[0]:.1e} ({worst[1]})', flush=True)
+
+
+# whole training chunks (chunk_*: the default TP-classifier mode, *_notp: --no-tp-classifier): train_chunk in the fixture's mode
+# against the reference's per-call loss terms, scores and gradients
+from tests.golden_util import LossTermsRecorder, chunk_tp
+from trackmpnn_amd.loops import train_chunk
+
+for name in chunk_golden_names():
+    gold = Golden(name)
+    meta, tp = gold.meta, chunk_tp(gold)
+    model = build_model(dict(meta, mode='train'), gold.params())
+    model.train()
+    model.zero_grad(set_to_none=True)
+    with LossTermsRecorder() as rec:
+        train_chunk(model, gold.t('X'), gold.t('y'), DEV, tp)
+    ref = gold.d['per_call']
+    e_loss = max(abs(float(call[k]) - ref[c, i]) / abs(ref[c, i]) for c, call in enumerate(rec.calls)
+                 for i, k in enumerate(('loss_c', 'loss_f')))
+    e_score = 0.0
+    for c, call in enumerate(rec.calls):
+        idx = (torch.cat([call['det_row'], call['edge_row']]) if tp else call['edge_row']).cpu()
+        e_score = max(e_score, (call['scores'].cpu()[idx] - gold.t(f'c{c}/scores')[idx]).abs().max().item())
+    gmax = max(float(gold.t('grad/' + k).abs().max()) for k, _ in model.named_parameters())
+    worst = max(((prm.grad.cpu() - gold.t('grad/' + k)).abs().max().item() / gmax, k) for k, prm in model.named_parameters())
+    print(f'{name:40s} {"tp" if tp else "no-tp":5s} H={meta["nhidden"]:<3d} per-call loss rel {e_loss:.1e} counted score {e_score:.1e} '
+          f'(min_margin {meta["min_margin"]:.1e}) grad/gmax {worst[0]:.1e} ({worst[1]})', flush=True)
