@@ -68,7 +68,8 @@ def _run(c, N, R, R_old, up, split):
 
 
 @pytest.mark.parametrize('R,R_old', [(1, 0), (31, 0), (32, 0), (33, 17), (100, 37), (255, 224), (4097, 1000),
-                                     (8191 + 32 * 300, 5003)])
+                                     (8191 + 32 * 300, 5003),
+                                     (2048, 0), (2049, 0)])      # the zero-state kernel's 64 / 65 slabs: reduced directly / folded first
 def test_zero_state_split_matches_the_full_kernel(R, R_old):
     from trackmpnn_amd import _lib
     if not _lib.load().tmpnn_gru_bwd_fused_zero_state_available(H, H, 1):

@@ -698,11 +698,13 @@ def test_gradients_bitwise_equal_across_processes():
     assert digests[0] == digests[1]
 
 
-@pytest.mark.parametrize('R', [1, 31, 32, 33, 255, 4097, 8191 + 32 * 300])
+@pytest.mark.parametrize('R', [1, 31, 32, 33, 255, 2048, 2049, 4097, 8191 + 32 * 300])
 def test_one_pass_backward_ragged_sizes_match_the_two_kernels(R):
     """tmpnn_gru_bwd_fused (one read of the gates) against tmpnn_gru_bwd_data + tmpnn_gru_bwd_weights on row counts
     around its tile (32 rows), pipeline (prologue stages tile 0 and requests tile 1) and grid (256 persistent blocks)
-    boundaries: every xmode / upstream / fused-adjoint variant, scattered row ids, outputs outside `rows` untouched."""
+    boundaries, and on both sides of the 64 -> 65 slabs at which the weight-gradient slabs are folded before the final reduce
+    (R = 2048 / 2049): every xmode (the concat cell, xmode 2, with IN = 2H: d_msg and dW_ih 2H wide) / upstream / fused-adjoint
+    variant, scattered row ids, outputs outside `rows` untouched."""
     from trackmpnn_amd import _lib
     lib = _lib.load()
     H = 64
@@ -718,10 +720,15 @@ def test_one_pass_backward_ragged_sizes_match_the_two_kernels(R):
     gates = torch.cat([torch.sigmoid(r32(2, N, H)), torch.tanh(r32(1, N, H)), r32(1, N, H)], 0).contiguous()
     wih, whh = 0.3 * r32(3 * H, H), 0.3 * r32(3 * H, H)
     st = torch.cuda.current_stream().cuda_stream
-    ws_b = max(lib.tmpnn_gru_bwd_weights_ws(R, H, H), lib.tmpnn_gru_bwd_fused_ws(R, H, H))
+    ws_b = max(f(R, IN, H) for f in (lib.tmpnn_gru_bwd_weights_ws, lib.tmpnn_gru_bwd_fused_ws) for IN in (H, 2 * H))
     ws = torch.empty(ws_b // 4 + 1, device=DEV)
     dmsg_init = r32(N, H)
-    for xmode in (0, 1):
+    wih2, dmsg_init2 = 0.3 * r32(3 * H, 2 * H), r32(N, 2 * H)      # the concat cell: W_ih = [W1 | W2], d_msg [N][2H]
+    for xmode in (0, 1, 2):
+        if xmode == 2 and not lib.tmpnn_gru_bwd_fused_available(H, 2 * H, 2):
+            assert os.environ.get('TMPNN_BWD_TWO') == '0' and os.environ.get('TMPNN_TEST_VARIANTS') == '1'
+            continue                  # (a comparison build on its four-wave form: the concat halves exist in the eight-wave one only)
+        IN, w_in, dm_init = (2 * H, wih2, dmsg_init2) if xmode == 2 else (H, wih, dmsg_init)
         for up in (1, 2, 3):
             for fuse in (False, True):
                 if fuse and xmode == 0 and os.environ.get('TMPNN_TEST_VARIANTS', '0') != '1':
@@ -732,25 +739,25 @@ def test_one_pass_backward_ragged_sizes_match_the_two_kernels(R):
                 mp = msg.data_ptr() if xmode == 0 else None
                 outs = []
                 inside = torch.isin(torch.arange(N, device=DEV), rows.long())
-                base = torch.where(inside[:, None], torch.full((N, H), 7.0, device=DEV), dmsg_init)
+                base = torch.where(inside[:, None], torch.full((N, IN), 7.0, device=DEV), dm_init)
                 for one_pass in (False, True):
                     dmsg = base.clone()
                     add = dmsg                                        # as the model calls it: the adjoint's table IS d_msg
                     dh = torch.full((N, H), 5.0, device=DEV)
-                    gW = [torch.full((3 * H, H), 0.5, device=DEV), torch.full((3 * H, H), 0.25, device=DEV),
+                    gW = [torch.full((3 * H, IN), 0.5, device=DEV), torch.full((3 * H, H), 0.25, device=DEV),
                           torch.full((3 * H,), 1.0, device=DEV), torch.full((3 * H,), 2.0, device=DEV)]
                     fa = (src.data_ptr(), dst.data_ptr(), add.data_ptr()) if fuse else (None, None, None)
                     if one_pass:
-                        _lib.call('tmpnn_gru_bwd_fused', rows.data_ptr(), R, xmode, sp, dp, mp, H, 1, H, h.data_ptr(), H, H,
-                                  wih.data_ptr(), whh.data_ptr(), gates.data_ptr(), N * H, dho, H, dyp, whp,
-                                  dmsg.data_ptr(), H, dh.data_ptr(), H, fa[0], fa[1], fa[2], H,
+                        _lib.call('tmpnn_gru_bwd_fused', rows.data_ptr(), R, xmode, sp, dp, mp, H, 1, IN, h.data_ptr(), H, H,
+                                  w_in.data_ptr(), whh.data_ptr(), gates.data_ptr(), N * H, dho, H, dyp, whp,
+                                  dmsg.data_ptr(), IN, dh.data_ptr(), H, fa[0], fa[1], fa[2], IN,
                                   gW[0].data_ptr(), gW[1].data_ptr(), gW[2].data_ptr(), gW[3].data_ptr(),
                                   ws.data_ptr(), ws.numel() * 4, st)
                     else:
-                        _lib.call('tmpnn_gru_bwd_data', rows.data_ptr(), R, H, h.data_ptr(), H, H, wih.data_ptr(),
-                                  whh.data_ptr(), gates.data_ptr(), N * H, dho, H, dyp, whp, dmsg.data_ptr(), H,
-                                  dh.data_ptr(), H, fa[0], fa[1], fa[2], H, st)
-                        _lib.call('tmpnn_gru_bwd_weights', rows.data_ptr(), R, xmode, sp, dp, mp, H, 1, H, h.data_ptr(), H, H,
+                        _lib.call('tmpnn_gru_bwd_data', rows.data_ptr(), R, IN, h.data_ptr(), H, H, w_in.data_ptr(),
+                                  whh.data_ptr(), gates.data_ptr(), N * H, dho, H, dyp, whp, dmsg.data_ptr(), IN,
+                                  dh.data_ptr(), H, fa[0], fa[1], fa[2], IN, st)
+                        _lib.call('tmpnn_gru_bwd_weights', rows.data_ptr(), R, xmode, sp, dp, mp, H, 1, IN, h.data_ptr(), H, H,
                                   gates.data_ptr(), N * H, dho, H, dyp, whp, gW[0].data_ptr(), gW[1].data_ptr(),
                                   gW[2].data_ptr(), gW[3].data_ptr(), ws.data_ptr(), ws.numel() * 4, st)
                     torch.cuda.synchronize()
@@ -763,6 +770,65 @@ def test_one_pass_backward_ragged_sizes_match_the_two_kernels(R):
                 for a, b in zip(g0, g1):
                     assert float((a - b).abs().max()) <= 2e-5 * max(1.0, float(a.abs().max())), tag
                 assert bool((h1[~inside] == 5.0).all()) and bool((m1[~inside] == base[~inside]).all()), tag
+                if R in (2048, 2049):
+                    # both routes share the slab fold and the final reduce: at its switch, each against the weight gradients
+                    # formed in fp64 from the same planes (the bound is the one above)
+                    for got in (g0, g1):
+                        for name, a, ref, b0 in zip(('dW_ih', 'dW_hh', 'db_ih', 'db_hh'), got,
+                                                    _weight_grads_fp64(xmode, up, rows, src, dst, msg, h, gates, dout, dyv, w_head),
+                                                    (0.5, 0.25, 1.0, 2.0)):
+                            err, sc = float((a.double() - b0 - ref).abs().max()), max(1.0, float(ref.abs().max()))
+                            assert err <= 2e-5 * sc, (tag, name, err, sc)
+
+
+def _weight_grads_fp64(xmode, up, rows, src, dst, msg, h, gates, dout, dyv, w_head):
+    """dW_ih, dW_hh, db_ih, db_hh of a GRU cell over `rows` in fp64, from the saved planes r, z, n, hn = W_hn h + b_hn:
+    h' = (1 - z) n + z h with n = tanh(i_n + r hn); the message is msg (by list position), h[src] - h[dst] or [h[src] | h[dst]]."""
+    d64 = lambda t: t.double()                                        # noqa: E731
+    ro, s, d = rows.long(), src.long(), dst.long()
+    r, z, n, hn = (d64(gates[k][ro]) for k in range(4))
+    hp = d64(h[ro])
+    dh = (d64(dout[ro]) if up & 1 else 0.0) + (d64(dyv[ro])[:, None] * d64(w_head)[None, :] if up & 2 else 0.0)
+    x = d64(msg) if xmode == 0 else d64(h[s]) - d64(h[d]) if xmode == 1 else torch.cat([d64(h[s]), d64(h[d])], 1)
+    dn = dh * (1 - z) * (1 - n * n)
+    dz = dh * (hp - n) * z * (1 - z)
+    dr = dn * hn * r * (1 - r)
+    gi, gh = torch.cat([dr, dz, dn], 1), torch.cat([dr, dz, dn * r], 1)
+    return gi.t() @ x, gh.t() @ hp, gi.sum(0), gh.sum(0)
+
+
+@pytest.mark.parametrize('R', [4096, 4097])
+def test_weight_gradient_alone_on_both_sides_of_the_slab_fold(R):
+    """tmpnn_gru_bwd_weights on the generic kernel (H = 32, IN = 32: one slab per 64 rows) with 64 slabs, reduced directly, and
+    65, folded 32:1 first: dW_ih, dW_hh, db_ih, db_hh added into non-zero buffers against an fp64 autograd of the cell,
+    within the one-pass test's 2e-5 x scale."""
+    from trackmpnn_amd import _lib
+    lib = _lib.load()
+    H = IN = 32
+    gen = torch.Generator().manual_seed(R)
+    r64 = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64).to(DEV)      # noqa: E731
+    x, h, dout = r64(R, IN), r64(R, H), r64(R, H)
+    P = [(0.3 * r64(3 * H, IN)).requires_grad_(), (0.3 * r64(3 * H, H)).requires_grad_(),
+         r64(3 * H).requires_grad_(), r64(3 * H).requires_grad_()]
+    gi, gh = x @ P[0].t() + P[2], h @ P[1].t() + P[3]
+    r, z = torch.sigmoid(gi[:, :H] + gh[:, :H]), torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+    n = torch.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+    ((1 - z) * n + z * h).mul(dout).sum().backward()
+    f32 = lambda t: t.detach().float().contiguous()                                     # noqa: E731
+    gates = torch.stack([f32(r), f32(z), f32(n), f32(gh[:, 2 * H:])]).contiguous()
+    rows = torch.arange(R, dtype=torch.int32, device=DEV)
+    xD, hD, doutD = f32(x), f32(h), f32(dout)
+    got = [torch.full(tuple(p.shape), 0.5, device=DEV) for p in P]
+    ws_b = lib.tmpnn_gru_bwd_weights_ws(R, IN, H)
+    ws = torch.empty(ws_b // 4 + 1, device=DEV)
+    _lib.call('tmpnn_gru_bwd_weights', rows.data_ptr(), R, 0, None, None, xD.data_ptr(), IN, 1, IN, hD.data_ptr(), H, H,
+              gates.data_ptr(), R * H, doutD.data_ptr(), H, None, None, got[0].data_ptr(), got[1].data_ptr(),
+              got[2].data_ptr(), got[3].data_ptr(), ws.data_ptr(), ws_b, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    for name, a, p in zip(('dW_ih', 'dW_hh', 'db_ih', 'db_hh'), got, P):
+        err, scale = float((a.double() - 0.5 - p.grad).abs().max()), max(1.0, float(p.grad.abs().max()))
+        print(f'R={R} {name}: err {err:.3e} scale {scale:.3e}')
+        assert err <= 2e-5 * scale, (R, name)
 
 
 @pytest.mark.parametrize('H', [64, 256])

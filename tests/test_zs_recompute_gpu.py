@@ -93,7 +93,7 @@ def _bwd(c, N, R, up, gates, gate_plane, expect_rc=0):
     return dmsg, gW
 
 
-@pytest.mark.parametrize('R', [1, 31, 32, 33, 4097])
+@pytest.mark.parametrize('R', [1, 31, 32, 33, 2048, 2049, 4097])      # (2048 / 2049: 64 / 65 slabs, reduced directly / folded first)
 def test_recomputed_gates_match_the_saved_planes(R):
     from trackmpnn_amd import _lib
     if not _lib.load().tmpnn_gru_bwd_fused_zero_state_available(H, H, 1):

@@ -390,17 +390,21 @@ __global__ void k_fold_slabs(const float* __restrict__ slabs, size_t stride, int
 
 size_t reduce_slabs_ws_floats(int nslab, size_t n) { return nslab > 64 ? (size_t)ceil_div(nslab, 32) * n : 0; }
 
+int launch_fold_slabs(const float* slabs, size_t stride, int nslab, float* out, size_t n, hipStream_t st) {
+    hipLaunchKernelGGL(k_fold_slabs, dim3(ceil_div((long)n, 256), ceil_div(nslab, 32)), dim3(256), 0, st, slabs, stride, nslab,
+                       out, n);
+    return check_launch("fold_slabs");
+}
+
 int launch_reduce_slabs(const float* slabs, size_t stride, int nslab, float* dst, size_t n, int accumulate,
                         hipStream_t st, float* ws2) {
     if (n == 0) return TMPNN_OK;
     if (nslab > 64 && ws2 != nullptr) {
-        const int ng = ceil_div(nslab, 32);
-        hipLaunchKernelGGL(k_fold_slabs, dim3(ceil_div((long)n, 256), ng), dim3(256), 0, st, slabs, stride, nslab, ws2, n);
-        int rc = check_launch("fold_slabs");
+        int rc = launch_fold_slabs(slabs, stride, nslab, ws2, n, st);
         if (rc) return rc;
         slabs = ws2;
         stride = n;
-        nslab = ng;
+        nslab = ceil_div(nslab, 32);
     }
     hipLaunchKernelGGL(k_reduce_slabs, dim3(ceil_div((long)n, 256)), dim3(256), 0, st, slabs, stride, nslab, dst,
                        n, accumulate);

@@ -86,6 +86,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 size_t reduce_slabs_ws_floats(int nslab, size_t n);
 int launch_reduce_slabs(const float* slabs, size_t stride, int nslab, float* dst, size_t n, int accumulate,
                         hipStream_t st, float* ws2 = nullptr);
+// the 32:1 fold alone: out[g*n + i] = sum over the g-th group of 32 slabs, g < ceil(nslab / 32)
+int launch_fold_slabs(const float* slabs, size_t stride, int nslab, float* out, size_t n, hipStream_t st);
 
 // Generic small dense product on the vector ALU (tiny operands only: input transform, attention
 // projections).  C[crow(m)*ldc + n] (+)= sum_k A[arow(m)*sam + k*sak] * B[k*sbk + n*sbn] (+ bias[n])

@@ -1,4 +1,4 @@
-// Shared pieces of the GRU-cell kernels (csrc/gru_fwd.hip, csrc/gru_bwd.hip): the bf16x6 split-product helpers, the argument
+// Shared pieces of the GRU-cell kernels (csrc/gru_fwd.hip, csrc/gru_bwd.hip, csrc/gru_bwd_fused.hip): the bf16x6 split-product helpers, the argument
 // structs of the generic kernels and the transposing 32 x 32 store through a per-wave LDS tile.
 #pragma once
 #include "common.h"
@@ -78,6 +78,26 @@ __device__ __forceinline__ void split1(float x, uint16_t& q1, uint16_t& q2, uint
     uint32_t p1, p2, p3;
     split_pair(x, 0.f, p1, p2, p3);
     q1 = (uint16_t)p1; q2 = (uint16_t)p2; q3 = (uint16_t)p3;
+}
+__device__ __forceinline__ void f4_to_arr(const float4& u, const float4& v, float* o) {
+    o[0] = u.x; o[1] = u.y; o[2] = u.z; o[3] = u.w; o[4] = v.x; o[5] = v.y; o[6] = v.z; o[7] = v.w;
+}
+__device__ __forceinline__ Split8 split8_arr(const float* x) {
+    return split8(make_float4(x[0], x[1], x[2], x[3]), make_float4(x[4], x[5], x[6], x[7]));
+}
+
+// the transposing LDS read of the bf16x6 backward kernels (ds_read_b64_tr_b16: a 16-lane group reads 4 rows x 16 columns of a
+// row-major bf16 image and receives them column-major) and the swizzle that keeps its four rows in different bank windows
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint2 lds_read_tr(const uint16_t* p) {
+    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+        (__attribute__((address_space(3))) s16x4*)(p));
+    return __builtin_bit_cast(uint2, v);
+}
+// element offset of (row, col) in a swizzled row-major bf16 image with `cols` columns (cols*2 bytes a multiple of 256)
+template <int COLS>
+__device__ __forceinline__ int swz_off(int row, int col) {
+    return row * COLS + ((((col >> 5) ^ (row & 3)) << 5) | (col & 31));
 }
 
 // row (within the wave's 32) held by accumulator register `reg` of lane-half `half`
