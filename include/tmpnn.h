@@ -61,7 +61,10 @@ extern "C" {
                                    added, none changed);
                                still 13, for the same reason: + struct tmpnn_label_store, struct tmpnn_label_record, struct
                                    tmpnn_label_out, tmpnn_label_dets, tmpnn_label_compact, tmpnn_label_max_per_frame,
-                                   tmpnn_label_wave_frame (entry points added, none changed) */
+                                   tmpnn_label_wave_frame (entry points added, none changed);
+                               still 13, for the same reason: + struct tmpnn_chunk_vis, tmpnn_chunk_draw_vis, struct
+                                   tmpnn_frames_gather_args, tmpnn_frames_gather (entry points added, none changed; the
+                                   reserved word of struct tmpnn_chunk_draw, zero so far, is now ldx: 0 means F as before) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -688,7 +691,7 @@ typedef struct tmpnn_chunk_draw {
     float p_drop;
     float p_reverse;
     float p_flip;
-    float reserved;
+    int32_t ldx;                /* row stride of X in floats, >= F; 0 (the field was reserved and zero before): F */
     const int32_t* indices;     /* [B] */
     const int32_t* chunks;      /* [nchunks][4 + L] */
     const int32_t* seq_base;    /* [nseq + 1] */
@@ -699,11 +702,56 @@ typedef struct tmpnn_chunk_draw {
     int32_t* count;             /* [B] */
     uint8_t* flags;             /* [B] */
     int64_t* offsets;           /* [B + 1] */
-    float* X;                   /* [n_max][F] */
+    float* X;                   /* [n_max][ldx] */
     int64_t* y;                 /* [n_max][2], 16-byte aligned */
 } tmpnn_chunk_draw;
 int tmpnn_chunk_draw_count(const tmpnn_chunk_draw* d, tmpnn_stream stream);
 int tmpnn_chunk_draw_fill(const tmpnn_chunk_draw* d, tmpnn_stream stream);
+
+/* What a store with the 'vis' feature group adds to a draw: per kept row the box its features were made from, its image's
+ * size, the image it needs and its track id -- the arguments of tmpnn_vis_head_fwd.  The store holds, per detection, the plain
+ * and the mirrored box (box[det][0 / 1][4], float32: the flip in float64 on the raw box, then narrowed, as for stat) and per
+ * sequence the image size.  slot[b][k] is the image of listed frame k of drawn chunk b: the row of the draw's frame plan, built
+ * on the host from the same Philox block j = 0 that decides the flip (trackmpnn_amd.chunks.ChunkSampler.frame_plan).
+ *   tmpnn_chunk_draw_vis: one launch behind tmpnn_chunk_draw_fill with the same descriptor (offsets written by
+ *     tmpnn_chunk_draw_count); one workgroup per chunk, the same decisions once more.  Kept row k of chunk b goes to row
+ *     offsets[b] + k: o_box = the plain or the mirrored box (one 16-byte store), o_im_hw = the sequence's (h, w), o_map_of =
+ *     slot[b][list index of the row's frame], o_track = the track id.  Time reversal changes none of them.  Rows from offsets[B]
+ *     on are not written, and a chunk with TMPNN_CD_FLAG_BAD writes nothing.  No atomics. */
+typedef struct tmpnn_chunk_vis {
+    const float* box;           /* [ndets][2][4] x1 y1 x2 y2: plain, mirrored; 16-byte aligned */
+    const float* seq_hw;        /* [nseq][2]: image height, width; 8-byte aligned */
+    const int32_t* slot;        /* [B][L] */
+    float* o_box;               /* [n_max][4], 16-byte aligned */
+    float* o_im_hw;             /* [n_max][2], 8-byte aligned */
+    int32_t* o_map_of;          /* [n_max] */
+    int32_t* o_track;           /* [n_max] */
+} tmpnn_chunk_vis;
+int tmpnn_chunk_draw_vis(const tmpnn_chunk_draw* d, const tmpnn_chunk_vis* v, tmpnn_stream stream);
+
+/* The CNN's input for the frames of a draw (csrc/frames.hip; trackmpnn_amd.frames.FrameStore; host definition: frames_host).
+ * The store keeps every frame of every sequence, already resized to the CNN's input size H x W, as planar uint8 [3][H][W]; frame
+ * f of sequence s lies at byte (seq_base[s] + f) * 3 * H * W (int64).  Output image i is frame plan[i] = (sequence, frame,
+ * mirrored 0 / 1), mirrored along W where flagged, as float32 [T][3][H][W] with out = table[c][v]: the table, built on the host
+ * with the float32 torch ops v.float().div(255).sub(mean[c]).div(std[c]) (ToTensor, then Normalize), is the definition of the
+ * value, so the output is selected, not computed.
+ *   tmpnn_frames_gather: one launch; a workgroup converts a run of whole rows of one image (about 4 KiB of pixels): 16-byte loads
+ *     of the run into LDS (the table is staged there too), then 16-byte stores of four pixels a thread, threads along W; the
+ *     mirrored read reverses within the row in LDS.  Any W up to TMPNN_FR_MAX_W: unaligned heads and tails are single loads and
+ *     stores.  A plan row outside the store writes nothing (the host validates the plan).  T = 0 launches nothing. */
+#define TMPNN_FR_MAX_W 8192
+typedef struct tmpnn_frames_gather_args {
+    int32_t T;                  /* images of the plan */
+    int32_t H, W;               /* 1 <= W <= TMPNN_FR_MAX_W */
+    int32_t nseq;
+    int64_t nframes;            /* frames of the store = seq_base[nseq] */
+    const uint8_t* frames;      /* [nframes][3][H][W], 16-byte aligned */
+    const int64_t* seq_base;    /* [nseq + 1] */
+    const int64_t* plan;        /* [T][3]: sequence, frame, mirrored */
+    const float* table;         /* [3][256] */
+    float* out;                 /* [T][3][H][W], 16-byte aligned */
+} tmpnn_frames_gather_args;
+int tmpnn_frames_gather(const tmpnn_frames_gather_args* a, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Batch-1 path (the reference's real call pattern, train.py:92-107 / infer.py:60-87: ONE small

@@ -5,12 +5,13 @@
 from .graph import (CallPlan, DeviceGraph, FrameGraph, device_graph_from_adjacency, WindowBuilder, batch_windows, concat_static_graphs, dense_static_graph,
                     graph_from_adjacency, graph_from_edges, plan_single, synth_window)
 from .capture import CapturedWindow
-from .chunks import ChunkSampler, DetectionStore, DrawnChunks, draw_chunks_host, make_chunks
+from .chunks import ChunkSampler, DetectionStore, DrawnChunks, FramePlan, HostDraw, draw_chunks_host, make_chunks
+from .frames import FrameStore
 from .labeling import (BDD_RULES, KITTI_RULES, DetectionLabeler, LabelRules, label_detections_host, label_frame_host,
                        label_overlaps_host, synth_label_sequence)
 from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
                    train_losses_windows)
-from .loops import train_chunk, train_chunks, train_epoch, validate
+from .loops import VisTraining, train_chunk, train_chunks, train_epoch, validate
 from .monitor import TrainMonitor, ValMonitor, val_counts_host, val_f1_host
 from .mapeval import MapEvaluator, MapStore, map_best_host, map_host, synth_map_sequence
 from .moteval import MotEvaluator, MotStore, mot_dist_host, mot_events_host, mot_overall, mot_summary_host
@@ -30,4 +31,4 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'mot_overall', 'validate', 'MapEvaluator', 'MapStore', 'map_host', 'map_best_host', 'synth_map_sequence',
            'ValMonitor', 'val_counts_host', 'val_f1_host', 'DetectionLabeler', 'LabelRules', 'KITTI_RULES', 'BDD_RULES',
            'label_frame_host', 'label_detections_host', 'label_overlaps_host', 'synth_label_sequence', 'VisHead', 'vis_centres_host',
-           'vis_pixels_host', 'vis_head_host']
+           'vis_pixels_host', 'vis_head_host', 'FramePlan', 'HostDraw', 'FrameStore', 'VisTraining']

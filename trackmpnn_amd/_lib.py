@@ -110,9 +110,20 @@ class CChunkDraw(C.Structure):
     """struct tmpnn_chunk_draw (include/tmpnn.h): a seeded draw of augmented training chunks from the detection store."""
     _fields_ = ([(f, C.c_int32) for f in ('B', 'nchunks', 'L', 'nseq', 'F', 'Fs', 'fr_range', 'transforms')]
                 + [(f, C.c_int64) for f in ('ndets', 'nframes', 'n_max')] + [('seed', C.c_uint64), ('step', C.c_uint64)]
-                + [(f, c_float) for f in ('p_drop', 'p_reverse', 'p_flip', 'reserved')]
+                + [(f, c_float) for f in ('p_drop', 'p_reverse', 'p_flip')] + [('ldx', C.c_int32)]
                 + [(f, c_void_p) for f in ('indices', 'chunks', 'seq_base', 'first', 'track', 'stat', 'table',
                                            'count', 'flags', 'offsets', 'X', 'y')])
+
+
+class CChunkDrawVis(C.Structure):
+    """struct tmpnn_chunk_vis (include/tmpnn.h): what a store with the 'vis' feature group adds to a draw."""
+    _fields_ = [(f, c_void_p) for f in ('box', 'seq_hw', 'slot', 'o_box', 'o_im_hw', 'o_map_of', 'o_track')]
+
+
+class CFramesGather(C.Structure):
+    """struct tmpnn_frames_gather_args (include/tmpnn.h): the CNN's input images of a frame plan from the resident uint8 frames."""
+    _fields_ = ([(f, C.c_int32) for f in ('T', 'H', 'W', 'nseq')] + [('nframes', C.c_int64)]
+                + [(f, c_void_p) for f in ('frames', 'seq_base', 'plan', 'table', 'out')])
 
 
 class CMotStore(C.Structure):
@@ -159,6 +170,8 @@ _TRP = C.POINTER(CTrackRows)
 _LWP = C.POINTER(CLossWindows)
 _TBP = C.POINTER(CTrainBuild)
 _CDP = C.POINTER(CChunkDraw)
+_CVP = C.POINTER(CChunkDrawVis)
+_FGP = C.POINTER(CFramesGather)
 _MSP = C.POINTER(CMotStore)
 _MAP = C.POINTER(CMapStore)
 _LSP = C.POINTER(CLabelStore)
@@ -280,6 +293,8 @@ _SIGNATURES = {
     'tmpnn_train_build_fill': (c_int, [_TBP, c_int, c_void_p]),
     'tmpnn_chunk_draw_count': (c_int, [_CDP, c_void_p]),
     'tmpnn_chunk_draw_fill': (c_int, [_CDP, c_void_p]),
+    'tmpnn_chunk_draw_vis': (c_int, [_CDP, _CVP, c_void_p]),
+    'tmpnn_frames_gather': (c_int, [_FGP, c_void_p]),
     'tmpnn_online_features': (c_int, [c_int] * 8 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p]),
     'tmpnn_mot_max_per_frame': (c_int, []),

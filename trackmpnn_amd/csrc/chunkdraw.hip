@@ -40,6 +40,7 @@ __device__ __forceinline__ bool cd_event(uint32_t word, float p) { return (float
 // one drawn chunk: sizes, the ends of its frame list, its decisions
 struct CdChunk {
     int n;          // rows before dropout (0: an empty or a rejected chunk)
+    int seq;        // sequence of the chunk
     int nfr;        // frames of the list
     int t_lo, t_hi; // first and last frame of the list
     uint32_t ci;    // chunk index = word 1 of the counter
@@ -57,7 +58,7 @@ struct CdLds {
 __device__ CdChunk cd_setup(const tmpnn_chunk_draw& d, int b, CdLds& L) {
     const int tid = threadIdx.x;
     CdChunk c;
-    c.n = 0; c.nfr = 0; c.t_lo = 0; c.t_hi = 0; c.flags = 0;
+    c.n = 0; c.seq = 0; c.nfr = 0; c.t_lo = 0; c.t_hi = 0; c.flags = 0;
     const int ci = d.indices[b];
     c.ci = (uint32_t)ci;
     int bad = ci < 0 || ci >= d.nchunks;
@@ -90,6 +91,7 @@ __device__ CdChunk cd_setup(const tmpnn_chunk_draw& d, int b, CdLds& L) {
         return c;
     }
     c.n = total;
+    c.seq = seq;
     c.nfr = nfr;
     c.t_lo = L.frame[0];
     c.t_hi = L.frame[nfr - 1];
@@ -162,7 +164,7 @@ __global__ __launch_bounds__(CD_THREADS) void k_cd_fill(tmpnn_chunk_draw d) {
     if (c.n == 0 || o0 < 0 || o1 < o0 || o1 > d.n_max || o1 - o0 > c.n) return;        // (block-uniform)
     const bool rev = c.flags & TMPNN_CD_FLAG_REVERSED;
     const int flip = (c.flags & TMPNN_CD_FLAG_FLIPPED) ? 1 : 0;
-    const int F = d.F, Fs = d.Fs;
+    const int F = d.F, Fs = d.Fs, ld = d.ldx ? d.ldx : d.F;
     CdLabel* yout = reinterpret_cast<CdLabel*>(d.y);
     int64_t row0 = o0;                                // first output row of the tile
     for (int base = 0; base < c.n; base += CD_THREADS) {
@@ -195,13 +197,56 @@ __global__ __launch_bounds__(CD_THREADS) void k_cd_fill(tmpnn_chunk_draw d) {
         }
         __syncthreads();
         // X: threads over (row, column) of the tile's kept rows, so a wave stores 64 consecutive floats
-        float* xo = d.X + row0 * F;
+        float* xo = d.X + row0 * ld;
         for (int e = tid; e < tot * F; e += CD_THREADS) {
             const int rr = e / F, col = e - rr * F;
-            xo[e] = col < Fs ? d.stat[((int64_t)s_det[rr] * 2 + flip) * Fs + col] : d.table[2 * s_tm[rr] + (col - Fs)];
+            xo[(int64_t)rr * ld + col] = col < Fs ? d.stat[((int64_t)s_det[rr] * 2 + flip) * Fs + col] : d.table[2 * s_tm[rr] + (col - Fs)];
         }
         row0 += tot;
         __syncthreads();                              // (s_det / s_tm are rewritten by the next tile)
+    }
+}
+
+// The rows a vis store adds to a draw (tmpnn_chunk_draw_vis): the decisions are the fill's (cd_setup, cd_keep), so kept row k of
+// chunk b lands on row offsets[b] + k here as it does there.  Every thread stores its own row: the box as one 16-byte store.
+__global__ __launch_bounds__(CD_THREADS) void k_cd_vis(tmpnn_chunk_draw d, tmpnn_chunk_vis v) {
+    __shared__ CdLds L;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const CdChunk c = cd_setup(d, b, L);
+    const int64_t o0 = d.offsets[b], o1 = d.offsets[b + 1];
+    if (c.n == 0 || o0 < 0 || o1 < o0 || o1 > d.n_max || o1 - o0 > c.n) return;        // (block-uniform; FLAG_BAD has n = 0)
+    const int flip = (c.flags & TMPNN_CD_FLAG_FLIPPED) ? 1 : 0;
+    const float2 hw = reinterpret_cast<const float2*>(v.seq_hw)[c.seq];
+    const float4* box = reinterpret_cast<const float4*>(v.box);
+    float4* o_box = reinterpret_cast<float4*>(v.o_box);
+    float2* o_hw = reinterpret_cast<float2*>(v.o_im_hw);
+    const int32_t* slot = v.slot + (int64_t)b * d.L;
+    int64_t row0 = o0;
+    for (int base = 0; base < c.n; base += CD_THREADS) {
+        const int r = base + tid;
+        bool k = false;
+        int det = 0, li = 0;
+        if (r < c.n) {
+            int lo = 0, hi = c.nfr - 1;                // frame of row r: the last i with pre[i] <= r
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (L.pre[mid] <= r) lo = mid; else hi = mid - 1;
+            }
+            det = L.first[lo] + (r - L.pre[lo]);
+            li = lo;
+            k = cd_keep(d, c, r);
+        }
+        int tot;
+        const int p = block_scan<CD_THREADS>(k ? 1 : 0, L.wave, &tot);
+        if (row0 + tot > o1) return;                  // (block-uniform, as in the fill)
+        if (k) {
+            const int64_t o = row0 + p;
+            o_box[o] = box[(int64_t)det * 2 + flip];
+            o_hw[o] = hw;
+            v.o_map_of[o] = slot[li];
+            v.o_track[o] = d.track[det];
+        }
+        row0 += tot;
     }
 }
 
@@ -210,6 +255,7 @@ int cd_check(const tmpnn_chunk_draw* d, const char* what) {
     TM_REQUIRE(d->B >= 1 && d->nchunks >= 1 && d->nseq >= 1, "%s: B=%d nchunks=%d nseq=%d", what, d->B, d->nchunks, d->nseq);
     TM_REQUIRE(d->L >= 1 && d->L <= TMPNN_CD_MAX_FRAMES, "%s: L=%d (1 .. %d)", what, d->L, TMPNN_CD_MAX_FRAMES);
     TM_REQUIRE(d->Fs >= 1 && (d->F == d->Fs || d->F == d->Fs + 2), "%s: F=%d Fs=%d (F = Fs or Fs + 2)", what, d->F, d->Fs);
+    TM_REQUIRE(d->ldx == 0 || d->ldx >= d->F, "%s: ldx=%d F=%d (0, or >= F)", what, d->ldx, d->F);
     TM_REQUIRE(d->fr_range >= 1, "%s: fr_range=%d", what, d->fr_range);
     TM_REQUIRE(d->ndets >= 0 && d->ndets <= INT32_MAX && d->nframes >= 1 && d->nframes < INT32_MAX, "%s: ndets=%lld nframes=%lld",
                what, (long long)d->ndets, (long long)d->nframes);
@@ -239,6 +285,19 @@ int tmpnn_chunk_draw_fill(const tmpnn_chunk_draw* d, tmpnn_stream stream) {
     TM_REQUIRE(aligned16(d->y), "chunk_draw_fill: y is not 16-byte aligned");
     hipLaunchKernelGGL(k_cd_fill, dim3(d->B), dim3(CD_THREADS), 0, as_stream(stream), *d);
     return check_launch("chunk_draw_fill");
+}
+
+int tmpnn_chunk_draw_vis(const tmpnn_chunk_draw* d, const tmpnn_chunk_vis* v, tmpnn_stream stream) {
+    if (int rc = cd_check(d, "chunk_draw_vis")) return rc;
+    TM_REQUIRE(v, "chunk_draw_vis: the vis struct is null");
+    if (d->n_max == 0) return TMPNN_OK;
+    TM_REQUIRE(d->track && v->box && v->seq_hw && v->slot && v->o_box && v->o_im_hw && v->o_map_of && v->o_track,
+               "chunk_draw_vis: null pointer");
+    TM_REQUIRE(aligned16(v->box) && aligned16(v->o_box), "chunk_draw_vis: box or o_box is not 16-byte aligned");
+    TM_REQUIRE((reinterpret_cast<uintptr_t>(v->seq_hw) & 7u) == 0 && (reinterpret_cast<uintptr_t>(v->o_im_hw) & 7u) == 0,
+               "chunk_draw_vis: seq_hw or o_im_hw is not 8-byte aligned");
+    hipLaunchKernelGGL(k_cd_vis, dim3(d->B), dim3(CD_THREADS), 0, as_stream(stream), *d, *v);
+    return check_launch("chunk_draw_vis");
 }
 
 }  // extern "C"

@@ -27,14 +27,15 @@ given a `TrainMonitor` (monitor.py) -- counts after every forward, one fold per 
 from __future__ import annotations
 
 import time
-from typing import Dict, Optional
+from dataclasses import dataclass
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from .loss import CELoss, FocalLoss, train_losses, train_losses_windows
 from .tracking import TrackGraph
-from .train_batch import AllChunksSkipped
+from .train_batch import AllChunksSkipped, _to_device
 
 
 class _Stages:
@@ -170,17 +171,39 @@ def train_chunks(model, batch, Xs, tp_classifier: bool = True, stages: Optional[
     return loss, torch.stack([acc_c.detach(), acc_f.detach()], 1), batch.ncalls, batch.edge_iters
 
 
-def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier: bool = True, monitor=None, scheduler=None) -> int:
+@dataclass
+class VisTraining:
+    """What train_epoch needs for a store with 'vis' features (the reference's default, train.py:132: loss_d + loss_c + loss_f)."""
+    head: Any               # vishead.VisHead: the CNN's input size, down ratio and the 128 'vis' statistics
+    frames: Any             # frames.FrameStore: the resized frames of the store's sequences, in the store's order
+    embed_net: Any          # the embedding CNN: images [T, 3, H, W] -> maps [T, 128, Hm, Wm]
+    embed_opt: Any          # its optimizer (zero_grad / step next to the tracker's)
+
+
+def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier: bool = True, monitor=None, scheduler=None,
+                vis: Optional[VisTraining] = None) -> int:
     """One epoch of train.py:54-135 over a ChunkSampler (trackmpnn_amd.chunks): `sampler.epoch_order(epoch)` in slices of
     `batch_size`, per slice draw -> DrawnChunks.batch() -> opt.zero_grad() -> train_chunks -> opt.step().  Every draw of the
     epoch uses step = epoch: a chunk's draw is keyed by (seed, step, chunk index) and a chunk comes up once per epoch, so the
     augmented data of an epoch do not depend on batch_size.  A slice in which the reference would skip every chunk (the
     build's AllChunksSkipped) takes no step.  `scheduler`, if given, is stepped once at the end (train.py:330's StepLR
     over `opt`; BucketAdam has no epoch step of its own).  Returns the number of optimizer steps.  A composition only: the
-    waits for the device are the build's two per step."""
+    waits for the device are the build's two per step.
+
+    A store with 'vis' features needs `vis` (a VisTraining).  Per slice: drawn.batch() first (a slice whose chunks are all
+    skipped runs no CNN), images = vis.frames.gather(drawn.plan), maps = vis.embed_net(images), loss_d =
+    drawn.attach_vis(vis.head, maps) (the rows into the last 128 columns of X, detached as the reference's features.detach()),
+    both optimizers' zero_grad, train_chunks, loss_d[batch.kept].sum().backward() (the identity loss of the chunks the batch
+    kept: the reference `continue`s past a skipped chunk before its backward, train.py:56-67), both optimizers' step.  loss_d
+    is not handed to the monitor."""
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f'train_epoch: batch_size={batch_size}')
+    if sampler.store.vis and vis is None:
+        raise ValueError("train_epoch: the sampler's store draws 'vis' features: pass vis=VisTraining(head, frames, embed_net, "
+                         'embed_opt)')
+    if vis is not None and not sampler.store.vis:
+        raise ValueError("train_epoch: vis= was given, but the sampler's store was built without 'vis' features")
     order = sampler.epoch_order(epoch)
     steps = 0
     for s in range(0, len(order), batch_size):
@@ -192,8 +215,14 @@ def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier:
             batch = drawn.batch()
         except AllChunksSkipped:
             continue
+        if vis is not None:
+            loss_d = drawn.attach_vis(vis.head, vis.embed_net(vis.frames.gather(drawn.plan)))
+            vis.embed_opt.zero_grad()
         opt.zero_grad()
         train_chunks(model, batch, drawn.features(batch), tp_classifier, monitor=monitor)
+        if vis is not None:
+            loss_d.index_select(0, _to_device(batch.kept, loss_d.device)).sum().backward()
+            vis.embed_opt.step()
         opt.step()
         steps += 1
     if scheduler is not None:

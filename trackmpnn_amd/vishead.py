@@ -180,20 +180,24 @@ class _VisCall:
 
 class _VisFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, maps, head, box, map_of, im_hw, track, offsets):
-        call = head._launch(maps, box, map_of, im_hw, track, offsets, None, 0)
+    def forward(ctx, maps, head, box, map_of, im_hw, track, offsets, dest):
+        # dest = (out, col): a tuple, so that `out` is not an input of the node (it is written in place and carries no gradient)
+        call = head._launch(maps, box, map_of, im_hw, track, offsets, dest[0], dest[1])
         ctx.call, ctx.head = call, head
+        if dest[0] is not None:
+            return call.loss
         ctx.mark_non_differentiable(call.rows)
         return call.rows, call.loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, _d_rows, d_loss):
+    def backward(ctx, *grads):
         call, head = ctx.call, ctx.head
+        d_loss = grads[-1]
         g = d_loss.detach().to(torch.float32).contiguous()
         dmaps = torch.empty(call.maps_shape, dtype=torch.float32, device=head.device)
         _lib.call('tmpnn_vis_head_bwd', C.byref(call.c), g.data_ptr(), dmaps.data_ptr(), _lib.raw_stream(head.device))
-        return dmaps, None, None, None, None, None, None
+        return dmaps, None, None, None, None, None, None, None
 
 
 class VisHead:
@@ -205,7 +209,8 @@ class VisHead:
     device       a cuda device
 
         head.rows(maps, box, map_of, im_hw, out=None, col=0)        -> rows [D, 128], or `out` with columns col .. col + 127 written
-        head.forward(maps, box, map_of, im_hw, track, offsets)      -> (rows [D, 128] detached, loss [B]); loss.sum().backward()
+        head.forward(maps, box, map_of, im_hw, track, offsets, out=None, col=0)
+                                                                    -> (rows [D, 128] detached, loss [B]); loss.sum().backward()
                                                                         reaches the CNN through `maps`
         head.record()                                               -> the counts of the last call (one host read)
 
@@ -308,12 +313,15 @@ class VisHead:
         with torch.no_grad():
             return self._launch(maps, box, map_of, im_hw, None, None, out, col).rows
 
-    def forward(self, maps, box, map_of, im_hw, track, offsets):
+    def forward(self, maps, box, map_of, im_hw, track, offsets, out: Optional[torch.Tensor] = None, col: int = 0):
         """(rows [D, 128], loss [B]): the feature columns (detached, as the reference's features.detach()) and the identity loss
-        of every chunk, differentiable wrt `maps`."""
+        of every chunk, differentiable wrt `maps`.  With `out` [D, F] the rows are written into its columns col .. col + 127 as
+        rows() writes them, and `out` itself is returned in their place."""
         if track is None or offsets is None:
             raise ValueError('VisHead.forward: track and offsets are needed (rows() is the call without a loss)')
-        return _VisFn.apply(maps, self, box, map_of, im_hw, track, offsets)
+        if out is None:
+            return _VisFn.apply(maps, self, box, map_of, im_hw, track, offsets, (None, 0))
+        return out, _VisFn.apply(maps, self, box, map_of, im_hw, track, offsets, (out, col))
 
     def last_logits(self) -> torch.Tensor:
         """The gathered logits [D, 128] of the last call (a view of its buffer)."""
