@@ -64,7 +64,9 @@ extern "C" {
                                    tmpnn_label_wave_frame (entry points added, none changed);
                                still 13, for the same reason: + struct tmpnn_chunk_vis, tmpnn_chunk_draw_vis, struct
                                    tmpnn_frames_gather_args, tmpnn_frames_gather (entry points added, none changed; the
-                                   reserved word of struct tmpnn_chunk_draw, zero so far, is now ldx: 0 means F as before) */
+                                   reserved word of struct tmpnn_chunk_draw, zero so far, is now ldx: 0 means F as before);
+                               still 13, for the same reason: + struct tmpnn_frames_resize_args, tmpnn_frames_resize,
+                                   tmpnn_frames_resize_ws (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -752,6 +754,41 @@ typedef struct tmpnn_frames_gather_args {
     float* out;                 /* [T][3][H][W], 16-byte aligned */
 } tmpnn_frames_gather_args;
 int tmpnn_frames_gather(const tmpnn_frames_gather_args* a, tmpnn_stream stream);
+
+/* Frames as decoded to the CNN's input size (csrc/resize.hip; trackmpnn_amd.frames.FrameStore.from_raw, FramePrep; host
+ * definition: resize_host, prep_host).  n frames of one source size h x w, uint8 interleaved [n][h][w][3] as decoders and cameras
+ * deliver them, become planar [n][3][H][W]: uint8 (what the store keeps) when table is NULL, else float32 table[c][v] (the CNN's
+ * input, selected from the [3][256] table of tmpnn_frames_gather).  The resize is the 8-bit bilinear resize of the reference's
+ * transforms.Resize on a PIL image: a horizontal pass when W != w, its result rounded to uint8, then a vertical pass when H != h,
+ * a copy when neither differs.  Per axis the host builds bounds [out][2] = (first source index, taps) and coef [out][ksize] int32
+ * (2^22 fixed point, zero beyond the taps) in doubles (trackmpnn_amd.frames.resize_coeffs); an output sample is
+ * clamp((2^21 + sum_x src[first + x] * coef[x]) >> 22, 0, 255), integer arithmetic only, so the device equals resize_host byte
+ * for byte.  All four tables are always passed (those of an axis that keeps its size are not read).
+ *   tmpnn_frames_resize: two launches -- the horizontal pass over all n frames into the workspace [n][h][W][3], the vertical pass
+ *     from it (one launch from src when W == w).  A thread owns 16 consecutive output pixels, threads along W; 16-byte loads and
+ *     stores where W keeps rows aligned (W % 16 == 0; float32 output: W % 4 == 0), single accesses otherwise and for a row's tail,
+ *     so any W up to TMPNN_FR_MAX_W works.  No LDS for pixels, no atomics; ksize <= TMPNN_FR_MAX_TAPS keeps the int32
+ *     accumulator (at most 255 * (2^22 + ksize) + 2^21).  A bounds row outside the source gives 0.  n = 0 launches nothing.
+ *   tmpnn_frames_resize_ws: bytes of that workspace (0 when W == w, when n == 0, or for sizes the call refuses). */
+#define TMPNN_FR_MAX_TAPS 1024
+typedef struct tmpnn_frames_resize_args {
+    int32_t n;                  /* frames */
+    int32_t h, w;               /* source size */
+    int32_t H, W;               /* output size, 1 <= W <= TMPNN_FR_MAX_W */
+    int32_t kx, ky;             /* columns of coef_x, coef_y: 1 <= ksize <= TMPNN_FR_MAX_TAPS */
+    int32_t reserved;           /* 0 */
+    const uint8_t* src;         /* [n][h][w][3] */
+    const int32_t* bounds_x;    /* [W][2] */
+    const int32_t* coef_x;      /* [W][kx] */
+    const int32_t* bounds_y;    /* [H][2] */
+    const int32_t* coef_y;      /* [H][ky] */
+    const float* table;         /* [3][256], or NULL for uint8 output */
+    void* out;                  /* uint8 or float32 [n][3][H][W] */
+    void* ws;                   /* tmpnn_frames_resize_ws bytes, 16-byte aligned (NULL when W == w) */
+    size_t ws_bytes;
+} tmpnn_frames_resize_args;
+size_t tmpnn_frames_resize_ws(int n, int h, int w, int H, int W);
+int tmpnn_frames_resize(const tmpnn_frames_resize_args* a, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Batch-1 path (the reference's real call pattern, train.py:92-107 / infer.py:60-87: ONE small

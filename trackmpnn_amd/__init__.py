@@ -6,7 +6,7 @@ from .graph import (CallPlan, DeviceGraph, FrameGraph, device_graph_from_adjacen
                     graph_from_adjacency, graph_from_edges, plan_single, synth_window)
 from .capture import CapturedWindow
 from .chunks import ChunkSampler, DetectionStore, DrawnChunks, FramePlan, HostDraw, draw_chunks_host, make_chunks
-from .frames import FrameStore
+from .frames import FramePrep, FrameStore, prep_host, resize_coeffs, resize_host
 from .labeling import (BDD_RULES, KITTI_RULES, DetectionLabeler, LabelRules, label_detections_host, label_frame_host,
                        label_overlaps_host, synth_label_sequence)
 from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
@@ -15,7 +15,7 @@ from .loops import VisTraining, train_chunk, train_chunks, train_epoch, validate
 from .monitor import TrainMonitor, ValMonitor, val_counts_host, val_f1_host
 from .mapeval import MapEvaluator, MapStore, map_best_host, map_host, synth_map_sequence
 from .moteval import MotEvaluator, MotStore, mot_dist_host, mot_events_host, mot_overall, mot_summary_host
-from .online import FeatureSpec, OnlineTracker, online_features_host
+from .online import FeatureSpec, OnlineTracker, OnlineVis, online_features_host
 from .optim import BucketAdam
 from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
@@ -31,4 +31,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'mot_overall', 'validate', 'MapEvaluator', 'MapStore', 'map_host', 'map_best_host', 'synth_map_sequence',
            'ValMonitor', 'val_counts_host', 'val_f1_host', 'DetectionLabeler', 'LabelRules', 'KITTI_RULES', 'BDD_RULES',
            'label_frame_host', 'label_detections_host', 'label_overlaps_host', 'synth_label_sequence', 'VisHead', 'vis_centres_host',
-           'vis_pixels_host', 'vis_head_host', 'FramePlan', 'HostDraw', 'FrameStore', 'VisTraining']
+           'vis_pixels_host', 'vis_head_host', 'FramePlan', 'HostDraw', 'FrameStore', 'VisTraining',
+           'FramePrep', 'OnlineVis', 'resize_coeffs', 'resize_host', 'prep_host']

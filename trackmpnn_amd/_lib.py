@@ -126,6 +126,13 @@ class CFramesGather(C.Structure):
                 + [(f, c_void_p) for f in ('frames', 'seq_base', 'plan', 'table', 'out')])
 
 
+class CFramesResize(C.Structure):
+    """struct tmpnn_frames_resize_args (include/tmpnn.h): raw interleaved frames to the CNN's input size, planar uint8 or float32."""
+    _fields_ = ([(f, C.c_int32) for f in ('n', 'h', 'w', 'H', 'W', 'kx', 'ky', 'reserved')]
+                + [(f, c_void_p) for f in ('src', 'bounds_x', 'coef_x', 'bounds_y', 'coef_y', 'table', 'out', 'ws')]
+                + [('ws_bytes', c_size_t)])
+
+
 class CMotStore(C.Structure):
     """struct tmpnn_mot_store (include/tmpnn.h): both sides of S sequences sorted by frame, for the MOT evaluation."""
     _fields_ = ([('S', C.c_int32), ('reserved', C.c_int32)] + [(f, C.c_int64) for f in ('n_gt', 'n_det', 'n_off', 'n_obj')]
@@ -172,6 +179,7 @@ _TBP = C.POINTER(CTrainBuild)
 _CDP = C.POINTER(CChunkDraw)
 _CVP = C.POINTER(CChunkDrawVis)
 _FGP = C.POINTER(CFramesGather)
+_FRP = C.POINTER(CFramesResize)
 _MSP = C.POINTER(CMotStore)
 _MAP = C.POINTER(CMapStore)
 _LSP = C.POINTER(CLabelStore)
@@ -295,6 +303,8 @@ _SIGNATURES = {
     'tmpnn_chunk_draw_fill': (c_int, [_CDP, c_void_p]),
     'tmpnn_chunk_draw_vis': (c_int, [_CDP, _CVP, c_void_p]),
     'tmpnn_frames_gather': (c_int, [_FGP, c_void_p]),
+    'tmpnn_frames_resize_ws': (c_size_t, [c_int] * 5),
+    'tmpnn_frames_resize': (c_int, [_FRP, c_void_p]),
     'tmpnn_online_features': (c_int, [c_int] * 8 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p]),
     'tmpnn_mot_max_per_frame': (c_int, []),

@@ -12,6 +12,17 @@ have arrived), through the same `TrackGraph` calls and the same native driver.  
         trk.push(cat, score, box)
         ids = trk.tracks()                             # -1: not finalised yet
 
+With a 'vis' model the 128 visual columns come from the live frame, on the device (`OnlineVis`: resize + ToTensor + Normalize by
+`frames.FramePrep`, the user's CNN, `VisHead.rows` writing straight into the feature buffer; no host round trip):
+
+    spec = FeatureSpec(ncategories=8, feats='2d+temp+vis', mean=mean, std=std)
+    vis = OnlineVis(VisHead((384, 1280), 4, mean, std), FramePrep((384, 1280), img_mean, img_std), embed_net)
+    trk = OnlineTracker(model, cur_win_size=5, spec=spec, vis=vis)
+    for img, (cat, score, box) in camera:              # img [h, w, 3] uint8 as decoded
+        trk.push(cat, score, box, frame=img)
+
+(`push(cat, score, box, vis=host_array)` still takes ready-made visual features.)
+
 The per-sequence buffers of `TrackGraph` (features, detection ids, tracks, finalisation scratch) are capacity-sized here and
 grow by doubling with a device-side copy; raw detections become standardised feature rows in one launch
 (`tmpnn_online_features`, csrc/online.hip) whose host definition is `online_features_host`.
@@ -66,9 +77,9 @@ class FeatureSpec:
         self.pair = np.ascontiguousarray(np.concatenate((np.sin(a), np.cos(a)), axis=1).astype(np.float32))
 
 
-def _raw_arrays(spec: FeatureSpec, cat, score, box, vis):
+def _raw_arrays(spec: FeatureSpec, cat, score, box, vis, from_frame: bool = False):
     """The raw detections of one frame, validated, as (cat int64 [D], score float32 [D], box float32 [D, 4], vis float32
-    [D, 128] or None)."""
+    [D, 128] or None).  from_frame: the 'vis' columns come from the frame on the device (OnlineVis), not from `vis`."""
     cat = np.asarray(cat)
     if cat.size and not np.issubdtype(cat.dtype, np.integer):
         raise ValueError(f'online features: cat must be integers, got {cat.dtype}')
@@ -82,7 +93,9 @@ def _raw_arrays(spec: FeatureSpec, cat, score, box, vis):
         raise ValueError(f'online features: a cat outside 1 .. {spec.ncat}')
     if not (np.isfinite(box).all() and np.isfinite(score).all()):
         raise ValueError('online features: a box or score is not finite')
-    if spec.vis:
+    if from_frame:
+        vis = None
+    elif spec.vis:
         if vis is None:
             raise ValueError("online features: the spec has 'vis' columns: pass vis [D, 128]")
         if isinstance(vis, torch.Tensor):
@@ -115,6 +128,42 @@ def online_features_host(spec: FeatureSpec, cat, score, box, t: int, vis=None) -
     return ((np.concatenate(cols, axis=1) - spec.mean[None, :]) / spec.std[None, :]).astype(np.float32)
 
 
+class OnlineVis:
+    """What turns a live frame into the 'vis' columns of its detections on the device (`OnlineTracker(..., vis=OnlineVis(...))`,
+    then `push(cat, score, box, frame=img)`):
+
+    head        a VisHead: the box-centre gather and the standardised softmax rows
+    prep        a FramePrep with the head's input size: resize, ToTensor, Normalize
+    embed_net   the embedding CNN (any callable): [1, 3, H, W] float32 -> maps [1, 128, H / down_ratio, W / down_ratio]
+
+    `columns(frame, box_d, out, col)` runs, without an autograd graph and without a host round trip, maps =
+    embed_net(prep.prep(frame)) and head.rows(maps, box, 0, (h, w), out, col)."""
+
+    def __init__(self, head, prep, embed_net):
+        for obj, names, what in ((head, ('input_h', 'input_w', 'mean', 'std', 'rows'), 'head: a VisHead'),
+                                 (prep, ('input_hw', 'prep'), 'prep: a FramePrep')):
+            if not all(hasattr(obj, n) for n in names):
+                raise ValueError(f'OnlineVis: {what} expected, got {type(obj).__name__}')
+        if not callable(embed_net):
+            raise ValueError('OnlineVis: embed_net must be callable')
+        want = (float(head.input_h), float(head.input_w))
+        if tuple(float(v) for v in prep.input_hw) != want:
+            raise ValueError(f"OnlineVis: prep resizes to {tuple(prep.input_hw)}, the head's input size is "
+                             f'{(head.input_h, head.input_w)}')
+        self.head, self.prep, self.embed_net = head, prep, embed_net
+        self._zeros = None                         # map_of of every row: the one map of the frame
+
+    def columns(self, frame, box_d: torch.Tensor, out: torch.Tensor, col: int) -> None:
+        """Write columns col .. col + 127 of out [D, F] (device rows) for the boxes box_d [D, 4] (device float32) of `frame`
+        [h, w, 3] uint8."""
+        D = int(box_d.shape[0])
+        if self._zeros is None or self._zeros.shape[0] < D:
+            self._zeros = torch.zeros(max(D, 256), dtype=torch.int32, device=box_d.device)
+        with torch.no_grad():
+            maps = self.embed_net(self.prep.prep(frame))
+            self.head.rows(maps, box_d, self._zeros[:D], (int(frame.shape[0]), int(frame.shape[1])), out=out, col=col)
+
+
 class OnlineTracker:
     """The inference loop of infer.py:35-87, one pushed frame at a time (module docstring).
 
@@ -129,7 +178,8 @@ class OnlineTracker:
     for a second non-empty frame are decoded only once it arrives.)"""
 
     def __init__(self, model, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
-                 tp_classifier: bool = True, spec: Optional[FeatureSpec] = None, device='cuda:0', max_dets: int = 16384):
+                 tp_classifier: bool = True, spec: Optional[FeatureSpec] = None, device='cuda:0', max_dets: int = 16384,
+                 vis: Optional[OnlineVis] = None):
         self.cur_win_size, self.ret_win_size = int(cur_win_size), int(ret_win_size)
         if self.cur_win_size < 2:
             raise ValueError(f'OnlineTracker: cur_win_size={cur_win_size}; >= 2 expected (with 1 the decode that follows a '
@@ -152,7 +202,16 @@ class OnlineTracker:
             raise ValueError(f'OnlineTracker: the spec builds {spec.F} feature columns, the model takes {self.F}')
         if getattr(model, 'training', False):
             raise ValueError('OnlineTracker: the model must be in eval mode')
-        self.model, self.spec, self.device = model, spec, dev
+        if vis is not None:
+            if not isinstance(vis, OnlineVis):
+                raise ValueError('OnlineTracker: vis must be an OnlineVis')
+            if spec is None or not spec.vis:
+                raise ValueError("OnlineTracker: vis=OnlineVis(...) needs a FeatureSpec with the 'vis' columns "
+                                 f'(spec={None if spec is None else spec.feats!r})')
+            hm, hs = (np.asarray(v, np.float32).ravel() for v in (vis.head.mean, vis.head.std))
+            if not (np.array_equal(hm, spec.mean[-VIS_COLS:]) and np.array_equal(hs, spec.std[-VIS_COLS:])):
+                raise ValueError("OnlineTracker: the head's 128 mean / std values differ from the last 128 of the spec's")
+        self.model, self.spec, self.device, self.vis = model, spec, dev, vis
         self.use_hungarian, self.tp_classifier = bool(use_hungarian), bool(tp_classifier)
         self._cap0 = int(max_dets)
         self._cap = 0
@@ -234,13 +293,25 @@ class OnlineTracker:
             raise ValueError('OnlineTracker: 2^24 frames pushed')
 
     # ---- the two ways in -------------------------------------------------------------------------------------------
-    def push(self, cat, score, box, vis=None, last: bool = False) -> None:
-        """The raw detections of the next frame: cat [D] 1-based ints, score [D], box [D, 4] x1 y1 x2 y2, vis [D, 128] with a
-        'vis' spec; D may be 0.  One host -> device copy of the packed detections and one launch build their rows."""
+    def push(self, cat, score, box, vis=None, last: bool = False, frame=None) -> None:
+        """The raw detections of the next frame: cat [D] 1-based ints, score [D], box [D, 4] x1 y1 x2 y2; D may be 0.  With a
+        'vis' spec either vis [D, 128] (host values, uploaded with the detections) or, on a tracker built with
+        vis=OnlineVis(...), frame [h, w, 3] uint8 as decoded: the frame is resized, normalised and run through the CNN on the
+        device and the head writes the 'vis' columns in place (D = 0 runs no CNN and no launch).  One host -> device copy of
+        the packed detections and one launch build the other columns."""
         if self.spec is None:
             raise ValueError('OnlineTracker.push: raw detections need a FeatureSpec (spec=...); push_features takes ready rows')
         sp = self.spec
-        cat, s32, b32, vis = _raw_arrays(sp, cat, score, box, vis)
+        if frame is not None:
+            if vis is not None:
+                raise ValueError('OnlineTracker.push: frame= and vis= together; the frame gives the vis columns')
+            if self.vis is None:
+                raise ValueError('OnlineTracker.push: frame= needs a tracker built with vis=OnlineVis(...)')
+            fshape = tuple(getattr(frame, 'shape', ()))
+            fdtype = getattr(frame, 'dtype', None)
+            if len(fshape) != 3 or fshape[2] != 3 or min(fshape) < 1 or fdtype not in (torch.uint8, np.dtype(np.uint8)):
+                raise ValueError(f'OnlineTracker.push: frame [h, w, 3] uint8 expected, got {fshape} {fdtype}')
+        cat, s32, b32, vis = _raw_arrays(sp, cat, score, box, vis, from_frame=frame is not None)
         D = int(cat.size)
         self._check_open(D)
         nd = self._ndets
@@ -248,7 +319,7 @@ class OnlineTracker:
             self._reserve(nd + D)
             if self._spec_d is None:
                 self._spec_d = self._upload(torch.from_numpy(np.concatenate([sp.mean, sp.std, sp.pair.ravel()])))
-            V = VIS_COLS if sp.vis else 0
+            V = VIS_COLS if sp.vis and frame is None else 0      # (V = 0 with the same ld_x leaves the last 128 columns alone)
             raw = np.empty((D, 6), np.int32)
             raw[:, 0] = cat
             rf = raw.view(np.float32)
@@ -259,6 +330,9 @@ class OnlineTracker:
             _lib.call('tmpnn_online_features', D, nd, self._cap, self._frames % sp.fr_range, sp.fr_range, sp.ncat, int(sp.temp), V,
                       pk.data_ptr(), pk.data_ptr() + 4 * 6 * D if V else None, V, sd, sd + 4 * sp.F, sd + 8 * sp.F,
                       self._X.data_ptr(), self.F, self._y_track.data_ptr(), self._ids.data_ptr(), _lib.raw_stream(self.device))
+            if frame is not None:
+                box_d = pk.view(torch.float32).view(D, 6)[:, 2:6]        # the float32 boxes, already on the device
+                self.vis.columns(frame, box_d, self._X[nd:nd + D], self.F - VIS_COLS)
         self._advance(D, last)
 
     def push_features(self, x, last: bool = False) -> None:
