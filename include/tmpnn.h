@@ -66,7 +66,9 @@ extern "C" {
                                    tmpnn_frames_gather_args, tmpnn_frames_gather (entry points added, none changed; the
                                    reserved word of struct tmpnn_chunk_draw, zero so far, is now ldx: 0 means F as before);
                                still 13, for the same reason: + struct tmpnn_frames_resize_args, tmpnn_frames_resize,
-                                   tmpnn_frames_resize_ws (entry points added, none changed) */
+                                   tmpnn_frames_resize_ws (entry points added, none changed);
+                               still 13, for the same reason: + struct tmpnn_hota_record, tmpnn_hota, tmpnn_hota_ws (entry
+                                   points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1151,6 +1153,32 @@ size_t tmpnn_mot_summary_ws(int S, int64_t n_obj, int64_t n_det, int64_t n_pair)
  * (parallel over sequences and frames, integer atomics), the assignment (one workgroup per sequence). */
 int tmpnn_mot_summary(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, void* ws, size_t ws_bytes,
                       tmpnn_mot_summary_record* out, tmpnn_stream stream);
+
+/* HOTA (trackmpnn_amd.hota.HotaEvaluator; csrc/hota.hip) over the same store and tracks: the record of every sequence equals
+ * trackmpnn_amd.hota.hota_host -- integers exactly, every double bit for bit (every float sum has a stated sequential order and
+ * there is no float atomic).  All arrays run over the 19 localisation thresholds alpha = 0.05 .. 0.95.  flag as in
+ * tmpnn_mot_record; a flagged sequence's sums are zero.  The derived figures (DetA, AssA, LocA, HOTA ...) are host arithmetic on
+ * the record (trackmpnn_amd.hota). */
+typedef struct tmpnn_hota_record {
+    int64_t tp[19];                 /* matched pairs with similarity >= thresholds[a] */
+    int64_t gt_dets, tracker_dets;  /* GT rows, kept detections (fn = gt_dets - tp, fp = tracker_dets - tp) */
+    int64_t objects, hypotheses;    /* distinct GT ids, distinct tracks >= 0 */
+    int64_t flag;
+    double loc_sum[19];             /* the similarities of the counted pairs: per frame by position among the GT rows, then by frame */
+    double ass_a_num[19], ass_re_num[19], ass_pr_num[19]; /* sums of m (m / max(1, gc + tc - m)), .. / max(1, gc), .. / max(1, tc) over
+                                       the pairs' match counts m: per object by hypothesis index, then by object */
+} tmpnn_hota_record;
+/* bytes; n_off = the store's n_off, n_pair = the sum over the sequences of n_obj x n_det (84 bytes an entry: a double and 19
+ * int32).  0 when an argument is negative, n_det >= 2^28 or n_pair > 2^31 / 84 (the pair workspace stays under 2 GiB). */
+size_t tmpnn_hota_ws(int S, int64_t n_obj, int64_t n_det, int64_t n_off, int64_t n_pair);
+/* The arguments of tmpnn_mot_events, and thresholds: 19 ascending doubles in HOST memory, read during the call (numpy's
+ * arange(0.05, 0.99, 0.05) - eps: a matched pair counts at index a iff its similarity >= thresholds[a]).  out [S].  One clear
+ * of the workspace's head and four launches, whatever S: the hypothesis index and the per-id row counts (one workgroup per
+ * sequence), the alignment pass (one wave per sequence, frames in order), the matching (parallel over sequences and frames, a
+ * wave per frame, integer atomics), the fold (one workgroup per sequence).  A frame takes tmpnn_mot_max_per_frame() rows on
+ * either side. */
+int tmpnn_hota(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, const double* thresholds, void* ws,
+               size_t ws_bytes, tmpnn_hota_record* out, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Validation mAP (trackmpnn_amd.mapeval.MapEvaluator): the mean average precision of the detections that were given a track,

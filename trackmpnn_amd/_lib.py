@@ -314,6 +314,8 @@ _SIGNATURES = {
     'tmpnn_mot_summary_limit': (c_int, [c_int]),
     'tmpnn_mot_summary_ws': (c_size_t, [c_int, C.c_int64, C.c_int64, C.c_int64]),
     'tmpnn_mot_summary': (c_int, [_MSP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'tmpnn_hota_ws': (c_size_t, [c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    'tmpnn_hota': (c_int, [_MSP, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     'tmpnn_map_tile': (c_int, []),
     'tmpnn_map_best': (c_int, [_MAP, c_void_p, c_void_p]),
     'tmpnn_map_eval_ws': (c_size_t, [C.c_int64, C.c_int64, C.c_int64]),

@@ -317,7 +317,7 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
 
 
 def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
-             tp_classifier: bool = True, map_evaluator=None, monitor=None) -> Dict:
+             tp_classifier: bool = True, map_evaluator=None, monitor=None, hota_evaluator=None) -> Dict:
     """The validation pass of train.py:177-282 up to the MOTA that chooses the checkpoint (train.py:300): the model in eval
     mode for the pass (its mode is restored afterwards), infer_sequence over every sequence, all tracks handed to
     `evaluator.evaluate` and read once.  sequences: one dict per sequence with 'X' [1, ND, F] and 'y' [1, ND, 2] as
@@ -338,12 +338,18 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     monitor: a monitor.ValMonitor (or None: nothing more is done and nothing more returned).  It is reset, counts every forward
     call of every sequence that runs (one launch each, on either inference path; a skipped sequence contributes none) and is
     read once, after the evaluator: the result gains 'f1' (train.py:278, the mean over the forwards, as a fraction) and
-    'f1_forwards'."""
+    'f1_forwards'.
+    hota_evaluator: a hota.HotaEvaluator built over the same sequences in the same order (or None: nothing more is done and
+    nothing more returned).  It is handed the same track list and read after the other evaluators: the result gains 'hota',
+    'deta', 'assa', 'loca', 'detre', 'detpr', 'assre', 'asspr' (hota_overall's means over the alphas, as fractions) and
+    'hota_per_sequence' (the dicts of hota_host, None for a sequence left out)."""
     store = evaluator.store
     if len(sequences) != store.S:
         raise ValueError(f'validate: {len(sequences)} sequences, the evaluator holds {store.S}')
     if map_evaluator is not None and [int(n) for n in np.diff(map_evaluator.store.det_base)] != [int(n) for n in store.seq[:, 3]]:
         raise ValueError('validate: map_evaluator was not built over the sequences of evaluator')
+    if hota_evaluator is not None and [int(n) for n in hota_evaluator.store.seq[:, 3]] != [int(n) for n in store.seq[:, 3]]:
+        raise ValueError('validate: hota_evaluator was not built over the sequences of evaluator')
     was_training = model.training
     model.eval()
     if monitor is not None:
@@ -363,9 +369,12 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
         evaluator.evaluate(tracks)
         if map_evaluator is not None:
             map_evaluator.evaluate(tracks)
+        if hota_evaluator is not None:
+            hota_evaluator.evaluate(tracks)
         per, overall = evaluator.read()
         mres = map_evaluator.read() if map_evaluator is not None else None
         vres = monitor.read() if monitor is not None else None
+        hres = hota_evaluator.read() if hota_evaluator is not None else None
     finally:
         model.train(was_training)
     out = dict(overall)
@@ -377,6 +386,9 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     if vres is not None:
         out['f1'] = vres['f1']
         out['f1_forwards'] = vres['forwards']
+    if hres is not None:
+        out.update({k: hres[1][k] for k in ('hota', 'deta', 'assa', 'loca', 'detre', 'detpr', 'assre', 'asspr')})
+        out['hota_per_sequence'] = hres[0]
     return out
 
 

@@ -364,6 +364,39 @@ class MotStore:
         self.n_gt, self.n_det, self.n_off, self.n_obj = g_base, d_base, f_base, o_base
 
 
+def _pack_tracks(st: MotStore, tracks: Sequence, buf: torch.Tensor, who: str) -> List[bool]:
+    """The tracks of an evaluation into `buf` (int32 [n_det] on the device, every sequence at its det_base): host arrays go up in
+    one packed copy at the most (-1 for a sequence given as None), device tensors are copied on the device.  Returns, per
+    sequence, whether it was left out."""
+    if len(tracks) != st.S:
+        raise ValueError(f'{who}: {len(tracks)} track arrays for {st.S} sequences')
+    host = np.full(st.n_det, -1, np.int32)
+    on_device = []
+    left_out = []
+    host_used = False
+    for s, tr in enumerate(tracks):
+        base, n = int(st.seq[s, 2]), int(st.seq[s, 3])
+        left_out.append(tr is None)
+        if tr is None:
+            host_used |= n > 0                                  # (its slice is filled with -1)
+            continue
+        if isinstance(tr, torch.Tensor) and tr.is_cuda:
+            if tr.dtype.is_floating_point or tr.numel() != n:
+                raise ValueError(f'{who}: sequence {s}: an int tensor of {n} tracks expected')
+            on_device.append((base, n, tr))
+        else:
+            a = _ints(tr, f'{who}: sequence {s}: tracks', n)
+            if a.size and (a.max() >= 2 ** 31 or a.min() < -2 ** 31):
+                raise ValueError(f'{who}: sequence {s}: track ids are int32')
+            host[base:base + n] = a
+            host_used |= n > 0
+    if host_used:
+        buf[:st.n_det].copy_(torch.from_numpy(host), non_blocking=True)       # the one packed upload
+    for base, n, tr in on_device:
+        buf[base:base + n].copy_(tr.reshape(-1))
+    return left_out
+
+
 RECORD_WORDS = 9               # struct tmpnn_mot_record: seven int64 counts, the flag word, dist_sum (double)
 SUMMARY_WORDS = 16             # struct tmpnn_mot_summary_record: the same, then SUMMARY_KEYS, idtp, hypotheses
 
@@ -416,33 +449,7 @@ class MotEvaluator:
         self._pending = False
 
     def evaluate(self, tracks: Sequence) -> None:
-        st = self.store
-        if len(tracks) != st.S:
-            raise ValueError(f'MotEvaluator.evaluate: {len(tracks)} track arrays for {st.S} sequences')
-        host = np.full(st.n_det, -1, np.int32)
-        on_device = []
-        left_out = []
-        host_used = False
-        for s, tr in enumerate(tracks):
-            base, n = int(st.seq[s, 2]), int(st.seq[s, 3])
-            left_out.append(tr is None)
-            if tr is None:
-                host_used |= n > 0                                  # (its slice is filled with -1)
-                continue
-            if isinstance(tr, torch.Tensor) and tr.is_cuda:
-                if tr.dtype.is_floating_point or tr.numel() != n:
-                    raise ValueError(f'MotEvaluator.evaluate: sequence {s}: an int tensor of {n} tracks expected')
-                on_device.append((base, n, tr))
-            else:
-                a = _ints(tr, f'MotEvaluator.evaluate: sequence {s}: tracks', n)
-                if a.size and (a.max() >= 2 ** 31 or a.min() < -2 ** 31):
-                    raise ValueError(f'MotEvaluator.evaluate: sequence {s}: track ids are int32')
-                host[base:base + n] = a
-                host_used |= n > 0
-        if host_used:
-            self._tracks[:st.n_det].copy_(torch.from_numpy(host), non_blocking=True)       # the one packed upload
-        for base, n, tr in on_device:
-            self._tracks[base:base + n].copy_(tr.reshape(-1))
+        left_out = _pack_tracks(self.store, tracks, self._tracks, 'MotEvaluator.evaluate')
         _lib.call('tmpnn_mot_summary' if self.identity else 'tmpnn_mot_events', C.byref(self._c), self._seq_host.ctypes.data, self._tracks.data_ptr(), self._ws.data_ptr(),
                   self._ws_bytes, self._out.data_ptr(), _lib.raw_stream(self.device))
         self._left_out = left_out
