@@ -197,6 +197,8 @@ int tmpnn_segsum_fwd(const tmpnn_graph* g, const float* in, int ld_in, float* ou
  * of a sum).  row_limit >= N reads every row.  Ignored by the dense / window plans (they take the plain form). */
 int tmpnn_segsum_fwd_live(const tmpnn_graph* g, const float* in, int ld_in, float* out, int ld_out,
                           int H, int compact_out, int row_limit, tmpnn_stream stream);
+/* The backward of row F: tmpnn_gather_diff_fwd applied to gradients (the same kernel, the same bits):
+ * d_in[edge_row[e], 0:H] (=|+=) d_out[src[e], 0:H] - d_out[dst[e], 0:H]. */
 int tmpnn_segsum_bwd(const tmpnn_graph* g, const float* d_out, int ld_dout, float* d_in, int ld_din,
                      int H, int accumulate, tmpnn_stream stream);
 

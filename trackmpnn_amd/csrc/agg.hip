@@ -939,9 +939,12 @@ const char* tmpnn_last_error(void) { return tmpnn::g_err; }
 // H > 256 (multiples of 128): the row movers run once per slice of <= 256 columns (a row is moved by H / 4 adjacent lanes of
 // ONE wave); rows are strided, so a slice is the same call on shifted pointers.  Not for the concat forms (their second half
 // sits H columns further on).
-#define TM_SLICED(H_, call_)                                                              \
+#define TM_SLICED(H_, wa_, lda_, ldb_, call_)                                             \
     do {                                                                                  \
         if (supported_H_big(H_)) {                                                        \
+            /* (a slice's own check sees its <= 256 columns only, not the whole row) */   \
+            TM_REQUIRE((lda_) >= (wa_) && (ldb_) >= (H_),                                 \
+                       "leading dimension too small for H=%d (%d, %d)", H_, lda_, ldb_);  \
             for (int c0 = 0; c0 < (H_); c0 += 256) {                                      \
                 const int w = (H_) - c0 < 256 ? (H_) - c0 : 256;                          \
                 const int rc_ = call_;                                                    \
@@ -953,7 +956,7 @@ const char* tmpnn_last_error(void) { return tmpnn::g_err; }
 
 int tmpnn_gather_diff_fwd(const tmpnn_graph* g, const float* in, int ld_in, float* out, int ld_out, int H,
                           int accumulate, tmpnn_stream stream) {
-    TM_SLICED(H, gather(g, in + c0, ld_in, out + c0, ld_out, w, accumulate, false, stream));
+    TM_SLICED(H, H, ld_in, ld_out, gather(g, in + c0, ld_in, out + c0, ld_out, w, accumulate, false, stream));
     return gather(g, in, ld_in, out, ld_out, H, accumulate, false, stream);
 }
 int tmpnn_gather_concat_fwd(const tmpnn_graph* g, const float* in, int ld_in, float* out, int ld_out, int H,
@@ -962,29 +965,29 @@ int tmpnn_gather_concat_fwd(const tmpnn_graph* g, const float* in, int ld_in, fl
 }
 int tmpnn_gather_diff_bwd(const tmpnn_graph* g, const float* d_out, int ld_dout, float* d_in, int ld_din, int H,
                           int accumulate, tmpnn_stream stream) {
-    TM_SLICED(H, segsum(g, d_out + c0, ld_dout, d_in + c0, ld_din, w, accumulate, -1.0f, 0, 0, stream));
+    TM_SLICED(H, H, ld_dout, ld_din, segsum(g, d_out + c0, ld_dout, d_in + c0, ld_din, w, accumulate, -1.0f, 0, 0, stream));
     return segsum(g, d_out, ld_dout, d_in, ld_din, H, accumulate, -1.0f, 0, 0, stream);
 }
 int tmpnn_gather_concat_bwd(const tmpnn_graph* g, const float* d_out, int ld_dout, float* d_in, int ld_din, int H,
                             int accumulate, tmpnn_stream stream) {
     // (slices of the two halves [h[src] | h[dst]] of a 2H-wide row: the second half stays H columns further on)
-    TM_SLICED(H, segsum(g, d_out + c0, ld_dout, d_in + c0, ld_din, w, accumulate, 1.0f, H, 0, stream));
+    TM_SLICED(H, 2 * H, ld_dout, ld_din, segsum(g, d_out + c0, ld_dout, d_in + c0, ld_din, w, accumulate, 1.0f, H, 0, stream));
     return segsum(g, d_out, ld_dout, d_in, ld_din, H, accumulate, 1.0f, H, 0, stream);
 }
 int tmpnn_segsum_fwd(const tmpnn_graph* g, const float* in, int ld_in, float* out, int ld_out, int H, int accumulate,
                      int compact_out, tmpnn_stream stream) {
-    TM_SLICED(H, segsum(g, in + c0, ld_in, out + c0, ld_out, w, accumulate, -1.0f, 0, compact_out, stream));
+    TM_SLICED(H, H, ld_in, ld_out, segsum(g, in + c0, ld_in, out + c0, ld_out, w, accumulate, -1.0f, 0, compact_out, stream));
     return segsum(g, in, ld_in, out, ld_out, H, accumulate, -1.0f, 0, compact_out, stream);
 }
 int tmpnn_segsum_fwd_live(const tmpnn_graph* g, const float* in, int ld_in, float* out, int ld_out, int H, int compact_out,
                           int row_limit, tmpnn_stream stream) {
     TM_REQUIRE(row_limit >= 0, "segsum_fwd_live: row_limit %d", row_limit);
-    TM_SLICED(H, segsum(g, in + c0, ld_in, out + c0, ld_out, w, 0, -1.0f, 0, compact_out, stream, row_limit));
+    TM_SLICED(H, H, ld_in, ld_out, segsum(g, in + c0, ld_in, out + c0, ld_out, w, 0, -1.0f, 0, compact_out, stream, row_limit));
     return segsum(g, in, ld_in, out, ld_out, H, 0, -1.0f, 0, compact_out, stream, row_limit);
 }
 int tmpnn_segsum_bwd(const tmpnn_graph* g, const float* d_out, int ld_dout, float* d_in, int ld_din, int H,
                      int accumulate, tmpnn_stream stream) {
-    TM_SLICED(H, gather(g, d_out + c0, ld_dout, d_in + c0, ld_din, w, accumulate, false, stream));
+    TM_SLICED(H, H, ld_dout, ld_din, gather(g, d_out + c0, ld_dout, d_in + c0, ld_din, w, accumulate, false, stream));
     return gather(g, d_out, ld_dout, d_in, ld_din, H, accumulate, false, stream);
 }
 
