@@ -68,7 +68,9 @@ extern "C" {
                                still 13, for the same reason: + struct tmpnn_frames_resize_args, tmpnn_frames_resize,
                                    tmpnn_frames_resize_ws (entry points added, none changed);
                                still 13, for the same reason: + struct tmpnn_hota_record, tmpnn_hota, tmpnn_hota_ws (entry
-                                   points added, none changed) */
+                                   points added, none changed);
+                               still 13, for the same reason: + struct tmpnn_result_store, struct tmpnn_result_record,
+                                   tmpnn_results_apply, tmpnn_results_ws (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1181,6 +1183,57 @@ size_t tmpnn_hota_ws(int S, int64_t n_obj, int64_t n_det, int64_t n_off, int64_t
  * either side. */
 int tmpnn_hota(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, const double* thresholds, void* ws,
                size_t ws_bytes, tmpnn_hota_record* out, tmpnn_stream stream);
+
+/* ======================================================================================================
+ * Tracking results (trackmpnn_amd.results.TrackResults; csrc/results.hip): the last step of the reference's inference
+ * (infer.py:91-96; dataset/kitti_mot.py:21-73, dataset/bdd100k_mot.py:22-67) -- a track whose category (the largest category id
+ * over its rows) has a threshold and whose best detection score is below it is removed as a whole, and the kept rows are put
+ * in frame order for the result table.  The rule is trackmpnn_amd.results.results_host; ids, order and counts equal it exactly.
+ *
+ * The store holds what does not change between calls, packed over the sequences (all device memory, built by
+ * trackmpnn_amd.results.ResultStore):
+ *     seq      [S][8] int64    tab_base, n_tab, det_base, n_det, off_base, n_frames of a sequence, two reserved words;
+ *                              n_tab: the slots of its track table in the workspace, a power of two >= 2 n_det (0 without rows)
+ *     det_off  [n_off] int32   per sequence n_frames + 1 offsets of its frames over the sorted positions, relative to det_base
+ *     det_perm [n_det] int32   sorted position (stable by frame) -> arrival index, relative to det_base
+ *     det_fidx [n_det] int32   frame index (frame - first frame) of a sorted position
+ *     det_cat  [n_det] int32   category ids in arrival order, 0 <= id < n_cat
+ *     det_key  [n_det] uint32  the scores in arrival order as integers of the same order (trackmpnn_amd.results.score_keys)
+ *     thr_key  [n_cat] uint32  per category id the key of the threshold, 0 = none
+ * tracks [n_det] int32: y_out[:, 1] of every sequence in ARRIVAL order at its det_base; -1 = no track.
+ * ====================================================================================================== */
+typedef struct tmpnn_result_store {
+    int32_t S, n_cat;
+    int64_t n_det, n_off, n_tab; /* totals over the sequences: the lengths of the arrays below and of the tables */
+    const int64_t* seq;
+    const int32_t* det_off;
+    const int32_t* det_perm;
+    const int32_t* det_fidx;
+    const int32_t* det_cat;
+    const uint32_t* det_key;
+    const uint32_t* thr_key;
+} tmpnn_result_store;
+/* One per sequence.  kept_rows: rows whose filtered id is not -1 (the length of the sequence's part of `order`); removed_rows:
+ * rows of removed tracks.  flag: 0, or in its low byte 2 = a kept id twice in a frame (flag >> 8: the 1-based index of the first
+ * such frame in the sequence's range), 4 = the store is inconsistent (an offset, a permutation entry, a category or a table size
+ * out of range: nothing was read outside the arrays), 16 = an id below -1. */
+typedef struct tmpnn_result_record {
+    int64_t kept_rows, kept_tracks, removed_rows, removed_tracks;
+    int64_t flag;
+    int64_t reserved[3];
+} tmpnn_result_record;
+/* bytes: the track tables (four words a slot, cleared by every call), the flag words, the slot of every row.  0 when an argument
+ * is negative, S > 65535, n_det >= 2^31 or n_tab >= 2^34. */
+size_t tmpnn_results_ws(int S, int64_t n_det, int64_t n_tab);
+/* out [S]; filtered [n_det] int32: the ids after the filter, arrival order, every sequence at its det_base; order [n_det] int32:
+ * at a sequence's det_base the arrival indices (relative to det_base) of its kept rows sorted stably by frame, -1 behind them.
+ * seq_host: the HOST copy of st->seq, checked before the launches (the kernels check the device copy again, and every index).
+ * One clear of the workspace's head and four launches, whatever S: the grouping of rows by id with the per-track integer maxima
+ * (a thread per row, integer CAS / max), the filter (a thread per row), the duplicate check (a thread per sorted position), the
+ * compaction and the counts (one workgroup per sequence).  ws: 16-byte aligned, tmpnn_results_ws bytes; its contents need not
+ * survive between calls.  No float arithmetic and no float atomic: the output does not depend on the order of execution. */
+int tmpnn_results_apply(const tmpnn_result_store* st, const int64_t* seq_host, const int32_t* tracks, void* ws, size_t ws_bytes,
+                        tmpnn_result_record* out, int32_t* filtered, int32_t* order, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Validation mAP (trackmpnn_amd.mapeval.MapEvaluator): the mean average precision of the detections that were given a track,

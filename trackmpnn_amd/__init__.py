@@ -11,7 +11,9 @@ from .labeling import (BDD_RULES, KITTI_RULES, DetectionLabeler, LabelRules, lab
                        label_overlaps_host, synth_label_sequence)
 from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
                    train_losses_windows)
-from .loops import VisTraining, train_chunk, train_chunks, train_epoch, validate
+from .loops import VisTraining, infer_dataset, train_chunk, train_chunks, train_epoch, validate
+from .results import (BDD_RESULT_RULES, KITTI_RESULT_RULES, ResultRules, TrackResults, bdd_document_host, kitti_lines_host,
+                      results_host, synth_result_sequence)
 from .monitor import TrainMonitor, ValMonitor, val_counts_host, val_f1_host
 from .mapeval import MapEvaluator, MapStore, map_best_host, map_host, synth_map_sequence
 from .hota import HotaEvaluator, hota_host, hota_overall, hota_sim_host
@@ -33,4 +35,6 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'ValMonitor', 'val_counts_host', 'val_f1_host', 'DetectionLabeler', 'LabelRules', 'KITTI_RULES', 'BDD_RULES',
            'label_frame_host', 'label_detections_host', 'label_overlaps_host', 'synth_label_sequence', 'VisHead', 'vis_centres_host',
            'vis_pixels_host', 'vis_head_host', 'FramePlan', 'HostDraw', 'FrameStore', 'VisTraining',
-           'FramePrep', 'OnlineVis', 'resize_coeffs', 'resize_host', 'prep_host']
+           'FramePrep', 'OnlineVis', 'resize_coeffs', 'resize_host', 'prep_host', 'infer_dataset', 'ResultRules',
+           'KITTI_RESULT_RULES', 'BDD_RESULT_RULES', 'TrackResults', 'results_host', 'kitti_lines_host', 'bdd_document_host',
+           'synth_result_sequence']

@@ -139,6 +139,12 @@ class CMotStore(C.Structure):
                 + [(f, c_void_p) for f in ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')])
 
 
+class CResultStore(C.Structure):
+    """struct tmpnn_result_store (include/tmpnn.h): the detections of S sequences sorted by frame, for the result filter."""
+    _fields_ = ([('S', C.c_int32), ('n_cat', C.c_int32)] + [(f, C.c_int64) for f in ('n_det', 'n_off', 'n_tab')]
+                + [(f, c_void_p) for f in ('seq', 'det_off', 'det_perm', 'det_fidx', 'det_cat', 'det_key', 'thr_key')])
+
+
 class CMapStore(C.Structure):
     """struct tmpnn_map_store (include/tmpnn.h): GT rows by (class, sequence, frame), claim lists and per-class order, for mAP."""
     _fields_ = ([('S', C.c_int32), ('C', C.c_int32)] + [(f, C.c_int64) for f in ('n_gt', 'n_det', 'n_grp', 'n_live', 'n_claim')]
@@ -182,6 +188,7 @@ _FGP = C.POINTER(CFramesGather)
 _FRP = C.POINTER(CFramesResize)
 _MSP = C.POINTER(CMotStore)
 _MAP = C.POINTER(CMapStore)
+_RSP = C.POINTER(CResultStore)
 _LSP = C.POINTER(CLabelStore)
 _LOP = C.POINTER(CLabelOut)
 _VHP = C.POINTER(CVisHead)
@@ -316,6 +323,8 @@ _SIGNATURES = {
     'tmpnn_mot_summary': (c_int, [_MSP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     'tmpnn_hota_ws': (c_size_t, [c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     'tmpnn_hota': (c_int, [_MSP, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'tmpnn_results_ws': (c_size_t, [c_int, C.c_int64, C.c_int64]),
+    'tmpnn_results_apply': (c_int, [_RSP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tmpnn_map_tile': (c_int, []),
     'tmpnn_map_best': (c_int, [_MAP, c_void_p, c_void_p]),
     'tmpnn_map_eval_ws': (c_size_t, [C.c_int64, C.c_int64, C.c_int64]),

@@ -316,8 +316,39 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
     return y_out, ncalls, edge_iters
 
 
+def infer_dataset(model, sequences, results, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
+                  tp_classifier: bool = True) -> list:
+    """infer.py's loop over the sequences (infer.py:35-97) up to the result tables: the model in eval mode for the pass (its
+    mode is restored afterwards), infer_sequence over every sequence, then one `results.apply` and one `results.read()`.
+    sequences: one dict per sequence with 'X' [1, ND, F] and 'y' [1, ND, 2] as infer_sequence takes them; results: a
+    results.TrackResults built over the same sequences in the same order (its store holds their frames, categories and scores).
+    A sequence without detections is skipped as infer.py:38-40 skips it: it runs no inference and has None in the list.
+    Returns what results.read() returns: per sequence the dict of results_host; results.write_kitti(out_dir, per) /
+    write_bdd(out_dir, per) write the files from it."""
+    store = results.store
+    if len(sequences) != store.S:
+        raise ValueError(f'infer_dataset: {len(sequences)} sequences, the results hold {store.S}')
+    was_training = model.training
+    model.eval()
+    try:
+        tracks = []
+        for s, q in enumerate(sequences):
+            X, y = q['X'], q['y']
+            if int(y.shape[1]) != int(store.seq[s, 3]):
+                raise ValueError(f'infer_dataset: sequence {s} has {int(y.shape[1])} detections, the results hold {int(store.seq[s, 3])}')
+            if int(X.shape[1]) == 0:
+                tracks.append(None)
+                continue
+            y_out, _, _ = infer_sequence(model, X, y, cur_win_size, ret_win_size, use_hungarian, results.device, tp_classifier)
+            tracks.append(y_out[:, 1])
+        results.apply(tracks)
+        return results.read()
+    finally:
+        model.train(was_training)
+
+
 def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
-             tp_classifier: bool = True, map_evaluator=None, monitor=None, hota_evaluator=None) -> Dict:
+             tp_classifier: bool = True, map_evaluator=None, monitor=None, hota_evaluator=None, results=None) -> Dict:
     """The validation pass of train.py:177-282 up to the MOTA that chooses the checkpoint (train.py:300): the model in eval
     mode for the pass (its mode is restored afterwards), infer_sequence over every sequence, all tracks handed to
     `evaluator.evaluate` and read once.  sequences: one dict per sequence with 'X' [1, ND, F] and 'y' [1, ND, 2] as
@@ -342,8 +373,14 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     hota_evaluator: a hota.HotaEvaluator built over the same sequences in the same order (or None: nothing more is done and
     nothing more returned).  It is handed the same track list and read after the other evaluators: the result gains 'hota',
     'deta', 'assa', 'loca', 'detre', 'detpr', 'assre', 'asspr' (hota_overall's means over the alphas, as fractions) and
-    'hota_per_sequence' (the dicts of hota_host, None for a sequence left out)."""
+    'hota_per_sequence' (the dicts of hota_host, None for a sequence left out).
+    results: a results.TrackResults built over the same sequences in the same order (or None: nothing more is done and nothing
+    more returned).  The tracks go through `results.apply` first and every evaluator scores `results.filtered_tracks()` -- the
+    tracks a submission would contain (infer.py:91-96), handed over on the device; the result gains 'results', the counts
+    (kept_rows, kept_tracks, removed_rows, removed_tracks) summed over the sequences that took part, read after the evaluators."""
     store = evaluator.store
+    if results is not None and [int(n) for n in results.store.seq[:, 3]] != [int(n) for n in store.seq[:, 3]]:
+        raise ValueError('validate: results was not built over the sequences of evaluator')
     if len(sequences) != store.S:
         raise ValueError(f'validate: {len(sequences)} sequences, the evaluator holds {store.S}')
     if map_evaluator is not None and [int(n) for n in np.diff(map_evaluator.store.det_base)] != [int(n) for n in store.seq[:, 3]]:
@@ -366,6 +403,9 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
             y_out, ncalls, _ = infer_sequence(model, X, y, cur_win_size, ret_win_size, use_hungarian, evaluator.device,
                                               tp_classifier, monitor=monitor)
             tracks.append(y_out[:, 1] if ncalls > 0 else None)
+        if results is not None:
+            results.apply(tracks)
+            tracks = [None if t is None else f for t, f in zip(tracks, results.filtered_tracks())]
         evaluator.evaluate(tracks)
         if map_evaluator is not None:
             map_evaluator.evaluate(tracks)
@@ -375,6 +415,7 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
         mres = map_evaluator.read() if map_evaluator is not None else None
         vres = monitor.read() if monitor is not None else None
         hres = hota_evaluator.read() if hota_evaluator is not None else None
+        rres = results.read() if results is not None else None
     finally:
         model.train(was_training)
     out = dict(overall)
@@ -389,6 +430,9 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     if hres is not None:
         out.update({k: hres[1][k] for k in ('hota', 'deta', 'assa', 'loca', 'detre', 'detpr', 'assre', 'asspr')})
         out['hota_per_sequence'] = hres[0]
+    if rres is not None:
+        from .results import results_overall
+        out['results'] = results_overall(rres)
     return out
 
 
