@@ -70,7 +70,9 @@ extern "C" {
                                still 13, for the same reason: + struct tmpnn_hota_record, tmpnn_hota, tmpnn_hota_ws (entry
                                    points added, none changed);
                                still 13, for the same reason: + struct tmpnn_result_store, struct tmpnn_result_record,
-                                   tmpnn_results_apply, tmpnn_results_ws (entry points added, none changed) */
+                                   tmpnn_results_apply, tmpnn_results_ws (entry points added, none changed);
+                               still 13, for the same reason: + struct tmpnn_evalprep_store, struct tmpnn_evalprep_record,
+                                   tmpnn_evalprep, tmpnn_evalprep_max_per_frame (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1183,6 +1185,57 @@ size_t tmpnn_hota_ws(int S, int64_t n_obj, int64_t n_det, int64_t n_off, int64_t
  * either side. */
 int tmpnn_hota(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, const double* thresholds, void* ws,
                size_t ws_bytes, tmpnn_hota_record* out, tmpnn_stream stream);
+
+/* ======================================================================================================
+ * Benchmark preprocessing (trackmpnn_amd.evalprep.EvalPrep; csrc/evalprep.hip): what the KITTI benchmark does to a set of tracks
+ * before it scores one class (TrackEval, datasets/kitti_2d_box.py:get_preprocessed_seq_data) -- per frame one assignment of the
+ * class's tracker rows to the GT rows of the class and its distractors by the similarity of tmpnn_hota (entries below 0.5 - eps
+ * are 0, a pair is matched iff its score exceeds eps); a row matched to a distractor or to an occluded / truncated object is
+ * removed, and so is an unmatched row whose float32 height is <= height_thr or whose intersection with an ignore region exceeds
+ * 0.5 + eps of its own area.  The rule is trackmpnn_amd.evalprep.evalprep_frame_host; tracks_out and the counts equal it exactly.
+ *
+ * The store holds what does not change between calls, packed over the sequences (all device memory, built by
+ * trackmpnn_amd.evalprep.EvalPrepStore): both sides' rows sorted stably by frame, EVERY row kept,
+ *     seq      [S][8] int64    gt_base, n_gt, det_base, n_det, off_base, n_frames of a sequence, two reserved words
+ *     gt_off   [n_off] int32   per sequence n_frames + 1 offsets over the union frame range, relative to gt_base; det_off likewise
+ *     gt_code  [n_gt] uint8    the rules resolved by the host: 0 the row takes no part, 1 of the class and scored, 2 of the class
+ *                              but occluded or truncated, 3 a distractor, 4 an ignore region
+ *     det_code [n_det] uint8   1 iff the row's category is the class (sorted order)
+ *     gt_box   [n_gt][4], det_box [n_det][4] float32  x1 y1 x2 y2 (16-byte aligned)
+ *     det_perm [n_det] int32   sorted position -> arrival index of a detection, relative to det_base
+ * tracks [n_det] int32: y_out[:, 1] of every sequence in ARRIVAL order at its det_base; negative = no track.
+ * ====================================================================================================== */
+typedef struct tmpnn_evalprep_store {
+    int32_t S, reserved;
+    int64_t n_gt, n_det, n_off; /* totals over the sequences: the lengths of the arrays below */
+    double height_thr;          /* min_height + eps, formed by the host */
+    const int64_t* seq;
+    const int32_t* gt_off;
+    const int32_t* det_off;
+    const uint8_t* gt_code;
+    const uint8_t* det_code;
+    const float* gt_box;
+    const float* det_box;
+    const int32_t* det_perm;
+} tmpnn_evalprep_store;
+/* One per sequence.  count: rows_in (rows with a track), other_class, removed_distractor, removed_occluded, removed_small,
+ * removed_ignored, kept -- the last six sum to the first.  flag: 0, or in its low byte 1 = a frame with more than
+ * tmpnn_evalprep_max_per_frame() detection rows or GT rows (all categories), 4 = the store is inconsistent (an offset or a
+ * permutation entry out of range: nothing was read outside the arrays), 8 = the solver found no augmenting path; above it
+ * (flag >> 8) the 1-based index of the frame in the sequence's range.  A flagged sequence's counts and tracks_out are not to be
+ * used. */
+typedef struct tmpnn_evalprep_record {
+    int64_t count[7];
+    int64_t flag;
+} tmpnn_evalprep_record;
+int tmpnn_evalprep_max_per_frame(void);
+/* out [S]; tracks_out [n_det] int32 (not `tracks`): the ids after the preprocessing, arrival order, every sequence at its
+ * det_base, -1 where the row had no track, another class, or was removed.  seq_host: the HOST copy of st->seq, checked against
+ * the totals before the launch (the kernel checks the device copy again, and every offset it indexes by).  One clear of the
+ * records and one launch, whatever S: parallel over sequences and frames, a wave per frame, integer atomics for the counts.  No
+ * workspace. */
+int tmpnn_evalprep(const tmpnn_evalprep_store* st, const int64_t* seq_host, const int32_t* tracks, int32_t* tracks_out,
+                   tmpnn_evalprep_record* out, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Tracking results (trackmpnn_amd.results.TrackResults; csrc/results.hip): the last step of the reference's inference

@@ -17,6 +17,8 @@ from .results import (BDD_RESULT_RULES, KITTI_RESULT_RULES, ResultRules, TrackRe
 from .monitor import TrainMonitor, ValMonitor, val_counts_host, val_f1_host
 from .mapeval import MapEvaluator, MapStore, map_best_host, map_host, synth_map_sequence
 from .hota import HotaEvaluator, hota_host, hota_overall, hota_sim_host
+from .evalprep import (KITTI_CAR, KITTI_PEDESTRIAN, EvalPrep, PrepRules, evalprep_frame_host, evalprep_host, evalprep_ioa_host,
+                       synth_prep_sequence)
 from .moteval import MotEvaluator, MotStore, mot_dist_host, mot_events_host, mot_overall, mot_summary_host
 from .online import FeatureSpec, OnlineTracker, OnlineVis, online_features_host
 from .optim import BucketAdam
@@ -37,4 +39,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'vis_pixels_host', 'vis_head_host', 'FramePlan', 'HostDraw', 'FrameStore', 'VisTraining',
            'FramePrep', 'OnlineVis', 'resize_coeffs', 'resize_host', 'prep_host', 'infer_dataset', 'ResultRules',
            'KITTI_RESULT_RULES', 'BDD_RESULT_RULES', 'TrackResults', 'results_host', 'kitti_lines_host', 'bdd_document_host',
-           'synth_result_sequence']
+           'synth_result_sequence', 'EvalPrep', 'PrepRules', 'KITTI_CAR', 'KITTI_PEDESTRIAN', 'evalprep_frame_host', 'evalprep_host',
+           'evalprep_ioa_host', 'synth_prep_sequence']

@@ -139,6 +139,13 @@ class CMotStore(C.Structure):
                 + [(f, c_void_p) for f in ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')])
 
 
+class CEvalPrepStore(C.Structure):
+    """struct tmpnn_evalprep_store (include/tmpnn.h): both sides of S sequences sorted by frame, the rules as one code byte a row."""
+    _fields_ = ([('S', C.c_int32), ('reserved', C.c_int32)] + [(f, C.c_int64) for f in ('n_gt', 'n_det', 'n_off')]
+                + [('height_thr', C.c_double)]
+                + [(f, c_void_p) for f in ('seq', 'gt_off', 'det_off', 'gt_code', 'det_code', 'gt_box', 'det_box', 'det_perm')])
+
+
 class CResultStore(C.Structure):
     """struct tmpnn_result_store (include/tmpnn.h): the detections of S sequences sorted by frame, for the result filter."""
     _fields_ = ([('S', C.c_int32), ('n_cat', C.c_int32)] + [(f, C.c_int64) for f in ('n_det', 'n_off', 'n_tab')]
@@ -323,6 +330,8 @@ _SIGNATURES = {
     'tmpnn_mot_summary': (c_int, [_MSP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     'tmpnn_hota_ws': (c_size_t, [c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     'tmpnn_hota': (c_int, [_MSP, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'tmpnn_evalprep_max_per_frame': (c_int, []),
+    'tmpnn_evalprep': (c_int, [C.POINTER(CEvalPrepStore), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tmpnn_results_ws': (c_size_t, [c_int, C.c_int64, C.c_int64]),
     'tmpnn_results_apply': (c_int, [_RSP, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tmpnn_map_tile': (c_int, []),

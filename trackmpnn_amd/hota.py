@@ -12,9 +12,10 @@ dependency of this library and no fixture pins it: parity with its numbers is by
 rule by hand-computed cases.  TrackEval sums floats with np.sum (pairwise, in an order numpy chooses); the rule fixes a
 sequential order for every float sum instead, so that a device can equal it exactly.
 
-TrackEval's KITTI preprocessing (class filtering, the removal of detections on DontCare regions) is NOT part of this: the
-rows that are given are scored, as MotEvaluator scores them.  DetectionLabeler.eval_sequences() is the way to drop DontCare and
-Van detections first.
+The rows that are given are scored, as MotEvaluator scores them.  TrackEval's KITTI preprocessing (the class, its distractor
+class, occluded and truncated objects, small boxes, DontCare regions) is evalprep.EvalPrep: build the evaluator over
+`EvalPrep.eval_sequences()` and hand `EvalPrep.filtered_tracks()` to `evaluate` (or pass `validate(..., prep=ep)`) to score
+what the benchmark scores.  It uses hota_sim_host, so the two stages agree on every bit.
 """
 from __future__ import annotations
 
@@ -219,7 +220,7 @@ class HotaEvaluator:
     Every record field equals hota_host: integers exactly, float64 bit for bit.  A frame takes at most moteval.MAX_PER_FRAME rows on
     either side (beyond: FLAG_LIMIT for that sequence only).  The workspace holds objects x detections entries of PAIR_BYTES per
     sequence: a store beyond MAX_HOTA_PAIRS entries (or a workspace beyond 2 GiB) raises ValueError -- score it with hota_host.
-    No class filtering and no DontCare removal: DetectionLabeler.eval_sequences() drops such detections first."""
+    No class filtering and no DontCare removal here: evalprep.EvalPrep is the benchmark's preprocessing in front of this."""
 
     def __init__(self, sequences: Sequence[Dict], device='cuda:0'):
         dev = torch.device(device)

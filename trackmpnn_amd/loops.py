@@ -348,7 +348,7 @@ def infer_dataset(model, sequences, results, cur_win_size: int = 5, ret_win_size
 
 
 def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
-             tp_classifier: bool = True, map_evaluator=None, monitor=None, hota_evaluator=None, results=None) -> Dict:
+             tp_classifier: bool = True, map_evaluator=None, monitor=None, hota_evaluator=None, results=None, prep=None) -> Dict:
     """The validation pass of train.py:177-282 up to the MOTA that chooses the checkpoint (train.py:300): the model in eval
     mode for the pass (its mode is restored afterwards), infer_sequence over every sequence, all tracks handed to
     `evaluator.evaluate` and read once.  sequences: one dict per sequence with 'X' [1, ND, F] and 'y' [1, ND, 2] as
@@ -377,8 +377,15 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     results: a results.TrackResults built over the same sequences in the same order (or None: nothing more is done and nothing
     more returned).  The tracks go through `results.apply` first and every evaluator scores `results.filtered_tracks()` -- the
     tracks a submission would contain (infer.py:91-96), handed over on the device; the result gains 'results', the counts
-    (kept_rows, kept_tracks, removed_rows, removed_tracks) summed over the sequences that took part, read after the evaluators."""
+    (kept_rows, kept_tracks, removed_rows, removed_tracks) summed over the sequences that took part, read after the evaluators.
+    prep: an evalprep.EvalPrep built over the same sequences in the same order (or None: nothing more is done and nothing more
+    returned); the evaluators are then to be built over `prep.eval_sequences()`, the ground truth the benchmark scores.  After
+    `results.apply`, if any, the tracks go through `prep.apply` and every evaluator scores `prep.filtered_tracks()` -- the rows
+    the KITTI benchmark scores for the class of prep.rules, handed over on the device; the result gains 'prep', the counts of
+    evalprep_host (rows_in, other_class, the four removal counts, kept) summed over the sequences that took part, read last."""
     store = evaluator.store
+    if prep is not None and [int(n) for n in prep.store.seq[:, 3]] != [int(n) for n in store.seq[:, 3]]:
+        raise ValueError('validate: prep was not built over the sequences of evaluator')
     if results is not None and [int(n) for n in results.store.seq[:, 3]] != [int(n) for n in store.seq[:, 3]]:
         raise ValueError('validate: results was not built over the sequences of evaluator')
     if len(sequences) != store.S:
@@ -406,6 +413,9 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
         if results is not None:
             results.apply(tracks)
             tracks = [None if t is None else f for t, f in zip(tracks, results.filtered_tracks())]
+        if prep is not None:
+            prep.apply(tracks)
+            tracks = [None if t is None else f for t, f in zip(tracks, prep.filtered_tracks())]
         evaluator.evaluate(tracks)
         if map_evaluator is not None:
             map_evaluator.evaluate(tracks)
@@ -416,6 +426,7 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
         vres = monitor.read() if monitor is not None else None
         hres = hota_evaluator.read() if hota_evaluator is not None else None
         rres = results.read() if results is not None else None
+        pres = prep.read() if prep is not None else None
     finally:
         model.train(was_training)
     out = dict(overall)
@@ -433,6 +444,8 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     if rres is not None:
         from .results import results_overall
         out['results'] = results_overall(rres)
+    if pres is not None:
+        out['prep'] = pres[1]
     return out
 
 
