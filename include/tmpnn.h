@@ -221,6 +221,9 @@ int tmpnn_segsum_bwd(const tmpnn_graph* g, const float* d_out, int ld_dout, floa
  * erec [E][8]: everything an edge-owned pass needs to know about edge e, as one 32-byte record: the DET INDICES of its
  *   src / dst endpoint, its CSR positions in the src det's and in the dst det's run (the inverse of inc) | the graph rows
  *   of src, dst and of the edge itself, 0.
+ * Buffer sizes: score max(2E, 1) * K floats, alpha K * 2E, stats Dn * K * 2, esk K * Dn * H, ha Dn * K * H.  A graph without
+ *   edges (E == 0, Dn > 0) may pass inc == NULL, keep == NULL and erec == NULL: no edge array is read then (score's first K
+ *   floats are, as a stand-in, which is why score holds at least K floats), out and esk become 0 and stats (0, 1).
  * One read of h[inc row p] per CSR position serves every head; launches: 1 GEMM + 2 kernels. */
 int tmpnn_att_fwd(const tmpnn_graph* g, const int32_t* erec, const float* h, int ld_h, int H, int K,
                   const float* W_cat, const float* a, const uint8_t* keep, float p_drop,

@@ -419,11 +419,16 @@ __global__ __launch_bounds__(256) void k_att_bwd_edge(AttArgs A, const float* __
         if (e0 - slot + slots * U < e_hi) load_ids(e0 + slots * U);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const float ts = group_sum(dot4(gs[u], x[u]), lpr);
-            const float td = group_sum(dot4(gd[u], x[u]), lpr);
+            // 1/K goes onto h[e] BEFORE the dot, as the forward put it into es_k (w = +-alpha / K, es_k += w h[e]): on a run of ONE
+            // position (alpha = 1) sign t / K and <g, es_k> are then the same fp32 number and ds is exactly 0, as it is in exact
+            // arithmetic, whatever K.  With invK * <g, h[e]> that held for K = 1, 2, 4, 8 only; K = 3, 5 left ~1e-7 |t| per
+            // edge on dets with a single edge, which a hub at their other end summed over its whole run.
+            const float4 xs = make_float4(invK * x[u].x, invK * x[u].y, invK * x[u].z, invK * x[u].w);
+            const float ts = group_sum(dot4(gs[u], xs), lpr);
+            const float td = group_sum(dot4(gd[u], xs), lpr);
             float wsum = 0.f, ds[KT], dp_[KT];
             {
-                const float sgt = (lg & 1) ? -invK * td : invK * ts;       // sign_p t_p / K of this lane's side
+                const float sgt = (lg & 1) ? -td : ts;                     // sign_p t_p / K of this lane's side
 #pragma unroll
                 for (int k = 0; k < KT; ++k) {
                     const float al = expf(sc[u][k] - R[u][k].x) / R[u][k].y;
@@ -712,7 +717,13 @@ int tmpnn_att_fwd(const tmpnn_graph* g, const int32_t* erec, const float* h,
     }
     AttArgs A{g->N, g->E, g->Dn, H, K, g->det_row, g->rowptr, g->inc,
               g->det_order, erec, nullptr, h, ld_h, a, keep, keep ? 1.0f / (1.0f - p_drop) : 1.0f, ha, score, stats, esk, alpha};
-    if (g->E > 0) {
+    if (g->E == 0) {
+        // every run is empty, but a dead slot of k_att_fwd still ISSUES its loads at position 0 (inc, keep, K scores; the
+        // select discards them) and an edgeless graph may carry inc == NULL and keep == NULL: `score` holds at least K
+        // floats (tmpnn.h) and stands in for both
+        A.inc = reinterpret_cast<const int32_t*>(score);
+        A.keep = nullptr;
+    } else {
         const int rpb = 256 / (H >> 2);
         const int U = K <= 2 ? 4 : (K <= 4 ? 2 : 1);
         long nb = ((long)g->E + (long)rpb * U - 1) / ((long)rpb * U);
