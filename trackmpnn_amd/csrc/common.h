@@ -78,6 +78,51 @@ inline bool supported_H_cell(int H) { return supported_H(H) || supported_H_big(H
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline hipStream_t as_stream(tmpnn_stream s) { return reinterpret_cast<hipStream_t>(s); }
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// carves a workspace into arrays that start at multiples of 16 bytes, in the order of the calls
+struct WsCarver {
+    char* p;
+    template <class T> T* take(size_t count) {
+        T* at = reinterpret_cast<T*>(p);
+        p += align16(count * sizeof(T));
+        return at;
+    }
+};
+
+// What tmpnn_mot_events, tmpnn_mot_summary, tmpnn_hota and tmpnn_evalprep check of a store of S sequences and of the host copy
+// of its sequence table (seq_host: S rows of 8), before anything is launched.  n_obj: null for a store without objects.  The caller
+// has evaluated its own pointers: `pointers` (named by pointer_names) must hold once S > 0, `offsets` / `gt_arrays` /
+// `det_arrays` where the store has such rows.  max_det / max_obj: what a sequence's counts must stay below.
+constexpr int64_t EVAL_NO_LIMIT = INT64_MAX;
+inline int eval_check_store(const char* fn, int S, int64_t n_gt, int64_t n_det, int64_t n_off, const int64_t* n_obj, const int64_t* seq_host,
+                            bool pointers, const char* pointer_names, bool offsets, bool gt_arrays, bool det_arrays, const void* gt_box,
+                            const void* det_box, int64_t max_det, int64_t max_obj) {
+    if (n_obj == nullptr)
+        TM_REQUIRE(S >= 0 && n_gt >= 0 && n_det >= 0 && n_off >= 0, "%s: S=%d n_gt=%lld n_det=%lld n_off=%lld", fn, S, (long long)n_gt,
+                   (long long)n_det, (long long)n_off);
+    else
+        TM_REQUIRE(S >= 0 && n_gt >= 0 && n_det >= 0 && n_off >= 0 && *n_obj >= 0, "%s: S=%d n_gt=%lld n_det=%lld n_off=%lld n_obj=%lld", fn, S,
+                   (long long)n_gt, (long long)n_det, (long long)n_off, (long long)*n_obj);
+    if (S == 0) return TMPNN_OK;
+    TM_REQUIRE(pointers, "%s: null pointer (%s)", fn, pointer_names);
+    TM_REQUIRE(n_off == 0 || offsets, "%s: null offsets", fn);
+    TM_REQUIRE(n_gt == 0 || gt_arrays, "%s: null GT arrays", fn);
+    TM_REQUIRE(n_det == 0 || det_arrays, "%s: null detection arrays or tracks", fn);
+    TM_REQUIRE(aligned16(gt_box) && aligned16(det_box), "%s: boxes must be 16-byte aligned", fn);
+    for (int s = 0; s < S; ++s) {
+        const int64_t* q = seq_host + (size_t)s * 8;
+        TM_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[1] < 0x7fffffff && q[0] + q[1] <= n_gt, "%s: sequence %d: GT rows [%lld, +%lld) of %lld", fn, s,
+                   (long long)q[0], (long long)q[1], (long long)n_gt);
+        TM_REQUIRE(q[2] >= 0 && q[3] >= 0 && q[3] < max_det && q[2] + q[3] <= n_det, "%s: sequence %d: detection rows [%lld, +%lld) of %lld", fn,
+                   s, (long long)q[2], (long long)q[3], (long long)n_det);
+        TM_REQUIRE(q[4] >= 0 && q[5] >= 0 && q[5] < 0x7fffffff && q[4] + q[5] + 1 <= n_off, "%s: sequence %d: offsets [%lld, +%lld + 1) of %lld",
+                   fn, s, (long long)q[4], (long long)q[5], (long long)n_off);
+        TM_REQUIRE(!n_obj || (q[6] >= 0 && q[7] >= 0 && q[7] < max_obj && q[6] + q[7] <= *n_obj), "%s: sequence %d: objects [%lld, +%lld) of %lld",
+                   fn, s, (long long)q[6], (long long)q[7], (long long)(n_obj ? *n_obj : 0));
+    }
+    return TMPNN_OK;
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

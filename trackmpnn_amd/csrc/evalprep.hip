@@ -16,9 +16,10 @@
 // The scores are the same IEEE operations in the same order as the host's (contraction is OFF for this file).  No float atomic,
 // no wait on another workgroup.  Every index is checked against the store's totals before it is used; a failed check, a frame
 // beyond the limit or a solver that gives up sets the sequence's flag word (the first flag stays) and leaves the others alone.
+// The flag bits, the checks, hota_sim and ep_ioa are those of csrc/eval_common.h, shared with csrc/moteval.hip and csrc/hota.hip.
 #pragma clang fp contract(off)
 #include "common.h"
-#include "hota_sim.h"
+#include "eval_common.h"
 #include "wave_lsap.h"
 
 using namespace tmpnn;
@@ -29,41 +30,10 @@ constexpr int EP_MAX = 256;                  // detection rows / GT rows per fra
 constexpr int EP_LDS_SCORE = 1024;           // frames of up to this many pairs keep the solver's scores in LDS (8 KiB a wave)
 constexpr int EP_WAVES = 2;                  // waves of one workgroup
 constexpr int EP_FRAMES = 8;                 // frames of one workgroup (four per wave)
-constexpr double EP_EPS = 2.220446049250313e-16;            // np.finfo(np.float64).eps
 constexpr int NCOUNT = 7;                    // rows_in, other_class, removed_distractor / occluded / small / ignored, kept
 
-enum { FLAG_LIMIT = 1, FLAG_STORE = 4, FLAG_SOLVER = 8 };   // (csrc/moteval.hip, moteval.py)
 enum { GT_OUT = 0, GT_SCORED = 1, GT_HARD = 2, GT_DISTRACTOR = 3, GT_REGION = 4 };
 enum { C_ROWS = 0, C_OTHER = 1, C_DISTRACTOR = 2, C_OCCLUDED = 3, C_SMALL = 4, C_IGNORED = 5, C_KEPT = 6 };
-
-struct EpSeq { int64_t gt_base, n_gt, det_base, n_det, off_base, n_frames; };
-// a sequence's slices of the store; false when one does not lie inside the store's totals: nothing may be indexed then
-__device__ __forceinline__ bool ep_seq(const tmpnn_evalprep_store& st, int s, EpSeq& q) {
-    const int64_t* p = st.seq + (size_t)s * 8;
-    q.gt_base = p[0]; q.n_gt = p[1]; q.det_base = p[2]; q.n_det = p[3]; q.off_base = p[4]; q.n_frames = p[5];
-    return q.gt_base >= 0 && q.n_gt >= 0 && q.gt_base + q.n_gt <= st.n_gt && q.det_base >= 0 && q.n_det >= 0 &&
-           q.det_base + q.n_det <= st.n_det && q.off_base >= 0 && q.n_frames >= 0 && q.off_base + q.n_frames + 1 <= st.n_off &&
-           q.n_gt < 0x7fffffff && q.n_det < 0x7fffffff && q.n_frames < 0x7fffffff;
-}
-
-__device__ __forceinline__ void ep_flag(tmpnn_evalprep_record* rec, int bits, int64_t frame1) {     // the first flag of a sequence stays
-    atomicCAS(reinterpret_cast<unsigned long long*>(&rec->flag), 0ull, (unsigned long long)bits | ((unsigned long long)frame1 << 8));
-}
-
-// intersection over the detection's own area (host: evalprep.evalprep_ioa_host -- the intersection by the operations of
-// hota_sim in their order, the area the float64 product of the float32 width and height), 0 where area > eps is false or the
-// quotient is not finite
-__device__ __forceinline__ double ep_ioa(float4 d, float4 r) {
-    const float wd = d.z - d.x, hd = d.w - d.y, wr = r.z - r.x, hr = r.w - r.y;      // float32
-    const double dtx = d.x, dty = d.y, rtx = r.x, rty = r.y;
-    const double dbx = dtx + (double)wd, dby = dty + (double)hd, rbx = rtx + (double)wr, rby = rty + (double)hr;
-    const double iw = hota_fmax(hota_fmin(dbx, rbx) - hota_fmax(dtx, rtx), 0.0);
-    const double ih = hota_fmax(hota_fmin(dby, rby) - hota_fmax(dty, rty), 0.0);
-    const double inter = iw * ih;
-    const double area = (double)wd * (double)hd;
-    const double q = inter / area;
-    return (area > EP_EPS && hota_finite(q)) ? q : 0.0;
-}
 
 // what a wave holds of one frame: the matching GT rows and the tracker rows, both compacted in row order
 struct EpFrame {
@@ -82,7 +52,7 @@ struct EpCost {
     bool tr;
     __device__ __forceinline__ double pair(int i, int j) const {
         const double s = hota_sim(F->gbox[i], F->tbox[j]);
-        return s < 0.5 - EP_EPS ? 0.0 : s;
+        return s < 0.5 - EVAL_EPS ? 0.0 : s;
     }
     __device__ __forceinline__ double at(int row, int col) const {
         const int i = tr ? col : row, j = tr ? row : col;
@@ -97,6 +67,9 @@ struct EpShared {
 };
 
 __device__ __forceinline__ int ep_count(bool p) { return __popcll(__ballot(p)); }
+__device__ __forceinline__ void ep_flag(tmpnn_evalprep_record* rec, int bits, int64_t frame1) {     // (the record's flag word)
+    eval_flag_first(reinterpret_cast<unsigned long long*>(&rec->flag), bits, frame1);
+}
 
 __global__ __launch_bounds__(64 * EP_WAVES) void k_evalprep(tmpnn_evalprep_store st, const int32_t* __restrict__ tracks,
                                                             int32_t* __restrict__ tracks_out, tmpnn_evalprep_record* __restrict__ out,
@@ -105,8 +78,8 @@ __global__ __launch_bounds__(64 * EP_WAVES) void k_evalprep(tmpnn_evalprep_store
     const int s = blockIdx.x / frame_groups, group = blockIdx.x % frame_groups;      // (the grid is S x frame_groups blocks)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     EpShared& S = s_all[wave];
-    EpSeq q;
-    if (!ep_seq(st, s, q)) {
+    EvalSeq q;
+    if (!eval_seq<false>(st.seq, s, st.n_gt, st.n_det, st.n_off, 0, 0x7fffffff, q)) {
         if (group == 0 && threadIdx.x == 0) ep_flag(&out[s], FLAG_STORE, 0);
         return;
     }
@@ -128,8 +101,8 @@ __global__ __launch_bounds__(64 * EP_WAVES) void k_evalprep(tmpnn_evalprep_store
     for (int r = 0; r < EP_FRAMES / EP_WAVES; ++r) {
         const int64_t f = (int64_t)group * EP_FRAMES + r * EP_WAVES + wave;
         if (f >= q.n_frames) break;
-        const int g0 = gt_off[f], g1 = gt_off[f + 1], d0 = det_off[f], d1 = det_off[f + 1];
-        if (g0 < 0 || g1 < g0 || g1 > q.n_gt || d0 < 0 || d1 < d0 || d1 > n_det) {
+        int g0, g1, d0, d1;
+        if (!eval_frame_rows(gt_off, det_off, f, q, g0, g1, d0, d1)) {
             if (lane == 0) ep_flag(&out[s], FLAG_STORE, f + 1);
             continue;
         }
@@ -149,15 +122,13 @@ __global__ __launch_bounds__(64 * EP_WAVES) void k_evalprep(tmpnn_evalprep_store
                 if (p < 0 || p >= n_det) { bad = true; p = -1; } else { id = trk[p]; cls = det_code[k] == 1; }
             }
             const bool is_trk = id >= 0 && cls;
-            const unsigned long long bal = __ballot(is_trk);
+            const int at = wave_rank(is_trk, lane, nT);              // (< EP_MAX: the frame has at most EP_MAX rows)
             rows_in += ep_count(id >= 0);
             if (is_trk) {
-                const int at = nT + __popcll(bal & ((1ull << lane) - 1ull));                 // (< EP_MAX: the frame has at most EP_MAX rows)
                 S.F.tarr[at] = p; S.F.tbox[at] = det_box[k]; S.F.tmatch[at] = -1;
             } else if (p >= 0) {
                 trk_out[p] = -1;
             }
-            nT += __popcll(bal);
         }
         if (__ballot(bad)) {
             if (lane == 0) ep_flag(&out[s], FLAG_STORE, f + 1);
@@ -170,12 +141,8 @@ __global__ __launch_bounds__(64 * EP_WAVES) void k_evalprep(tmpnn_evalprep_store
             const int k = base + lane;
             const int code = k < g1 ? gt_code[k] : GT_OUT;
             const bool part = code >= GT_SCORED && code <= GT_DISTRACTOR;
-            const unsigned long long bal = __ballot(part);
-            if (part) {
-                const int at = nG + __popcll(bal & ((1ull << lane) - 1ull));
-                S.F.gbox[at] = gt_box[k]; S.F.gcode[at] = (unsigned char)code;
-            }
-            nG += __popcll(bal);
+            const int at = wave_rank(part, lane, nG);
+            if (part) { S.F.gbox[at] = gt_box[k]; S.F.gcode[at] = (unsigned char)code; }
         }
         wave_sync();
         if (nT > 0 && nG > 0) {
@@ -197,7 +164,7 @@ __global__ __launch_bounds__(64 * EP_WAVES) void k_evalprep(tmpnn_evalprep_store
                 const int c = S.L.col4row[row];
                 if (c < 0 || c >= nc) continue;
                 const int i = C.tr ? c : row, j = C.tr ? row : c;
-                if (-C.at(row, c) > 0.0 + EP_EPS) S.F.tmatch[j] = i;
+                if (-C.at(row, c) > 0.0 + EVAL_EPS) S.F.tmatch[j] = i;
             }
             wave_sync();
         }
@@ -216,7 +183,7 @@ __global__ __launch_bounds__(64 * EP_WAVES) void k_evalprep(tmpnn_evalprep_store
                 } else {
                     fate = C_KEPT;
                     for (int k = g0; k < g1; ++k)
-                        if (gt_code[k] == GT_REGION && ep_ioa(b, gt_box[k]) > 0.5 + EP_EPS) fate = C_IGNORED;
+                        if (gt_code[k] == GT_REGION && ep_ioa(b, gt_box[k]) > 0.5 + EVAL_EPS) fate = C_IGNORED;
                 }
                 const int p = S.F.tarr[j];
                 trk_out[p] = fate == C_KEPT ? trk[p] : -1;
@@ -243,26 +210,15 @@ extern "C" int tmpnn_evalprep_max_per_frame(void) { return EP_MAX; }
 extern "C" int tmpnn_evalprep(const tmpnn_evalprep_store* st, const int64_t* seq_host, const int32_t* tracks, int32_t* tracks_out,
                               tmpnn_evalprep_record* out, tmpnn_stream stream) {
     TM_REQUIRE(st != nullptr, "evalprep: store is null");
-    TM_REQUIRE(st->S >= 0 && st->n_gt >= 0 && st->n_det >= 0 && st->n_off >= 0, "evalprep: S=%d n_gt=%lld n_det=%lld n_off=%lld", st->S,
-               (long long)st->n_gt, (long long)st->n_det, (long long)st->n_off);
+    if (const int rc = eval_check_store("evalprep", st->S, st->n_gt, st->n_det, st->n_off, nullptr, seq_host, seq_host && st->seq && out,
+                                        "seq, seq_host or out", st->gt_off && st->det_off, st->gt_code && st->gt_box,
+                                        st->det_code && st->det_box && st->det_perm && tracks && tracks_out, st->gt_box, st->det_box,
+                                        0x7fffffff, EVAL_NO_LIMIT))
+        return rc;
     if (st->S == 0) return TMPNN_OK;
-    TM_REQUIRE(seq_host && st->seq && out, "evalprep: null pointer (seq, seq_host or out)");
-    TM_REQUIRE(st->n_off == 0 || (st->gt_off && st->det_off), "evalprep: null offsets");
-    TM_REQUIRE(st->n_gt == 0 || (st->gt_code && st->gt_box), "evalprep: null GT arrays");
-    TM_REQUIRE(st->n_det == 0 || (st->det_code && st->det_box && st->det_perm && tracks && tracks_out), "evalprep: null detection arrays or tracks");
-    TM_REQUIRE(aligned16(st->gt_box) && aligned16(st->det_box), "evalprep: boxes must be 16-byte aligned");
     TM_REQUIRE(st->height_thr == st->height_thr, "evalprep: the height threshold is NaN");
     int64_t max_frames = 0;
-    for (int s = 0; s < st->S; ++s) {
-        const int64_t* q = seq_host + (size_t)s * 8;
-        TM_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[1] < 0x7fffffff && q[0] + q[1] <= st->n_gt, "evalprep: sequence %d: GT rows [%lld, +%lld) of %lld", s,
-                   (long long)q[0], (long long)q[1], (long long)st->n_gt);
-        TM_REQUIRE(q[2] >= 0 && q[3] >= 0 && q[3] < 0x7fffffff && q[2] + q[3] <= st->n_det, "evalprep: sequence %d: detection rows [%lld, +%lld) of %lld",
-                   s, (long long)q[2], (long long)q[3], (long long)st->n_det);
-        TM_REQUIRE(q[4] >= 0 && q[5] >= 0 && q[5] < 0x7fffffff && q[4] + q[5] + 1 <= st->n_off, "evalprep: sequence %d: offsets [%lld, +%lld + 1) of %lld",
-                   s, (long long)q[4], (long long)q[5], (long long)st->n_off);
-        max_frames = q[5] > max_frames ? q[5] : max_frames;
-    }
+    for (int s = 0; s < st->S; ++s) max_frames = seq_host[(size_t)s * 8 + 5] > max_frames ? seq_host[(size_t)s * 8 + 5] : max_frames;
     const int frame_groups = max_frames > 0 ? ceil_div(max_frames, EP_FRAMES) : 1;
     TM_REQUIRE((int64_t)st->S * frame_groups < 0x7fffffff, "evalprep: %d sequences x %d groups of %d frames pass the grid", st->S, frame_groups, EP_FRAMES);
     hipStream_t hs = as_stream(stream);

@@ -4,8 +4,9 @@
 // (contraction is OFF for this file), and there is no float atomic anywhere.  One clear of the workspace and four launches,
 // whatever the number of sequences:
 //   k_hota_prep    one workgroup per sequence: the tracks in frame-sorted order, the dense index of every kept detection's
-//                  hypothesis id in order of first appearance (the scheme of k_mot_hyp, csrc/moteval.hip: an open-addressing
-//                  table, integer CAS / min, a scan over the first rows), tc[h] = rows per hypothesis, gc[o] = rows per object;
+//                  hypothesis id in order of first appearance (hyp_index, csrc/eval_common.h, as k_mot_hyp of csrc/moteval.hip:
+//                  an open-addressing table, integer CAS / min, a scan over the first rows), tc[h] = rows per hypothesis, gc[o] =
+//                  rows per object;
 //   k_hota_align   pass A, one wave per sequence walks the frames in order: row and column sums of the frame's similarity
 //                  matrix sequentially per lane, then a lane per pair adds sim / (colsum + rowsum - sim) into pm[o][h] (ids
 //                  are unique in a frame: no two lanes meet; across frames the order is the walk's).  It also checks every frame
@@ -22,9 +23,8 @@
 // The similarity is recomputed wherever it is needed (one function, the same inputs: the same bits).  Every index is checked
 // against the store's totals before it is used; a sequence that fails a check is flagged, stops, and leaves the others alone.
 #pragma clang fp contract(off)
-#include "block_scan.h"
 #include "common.h"
-#include "hota_sim.h"
+#include "eval_common.h"
 #include "wave_lsap.h"
 
 using namespace tmpnn;
@@ -40,24 +40,11 @@ constexpr int HM_WAVES = 2;                  // waves of one workgroup of k_hota
 constexpr int HM_FRAMES = 8;                 // frames of one workgroup of k_hota_match (four per wave)
 constexpr int64_t HOTA_MAX_DET = (int64_t)1 << 28;          // (table slots are int32: 4 n_det of them)
 constexpr int64_t HOTA_MAX_PAIR = ((int64_t)1 << 31) / (8 + 4 * HOTA_NA);
-constexpr double HOTA_EPS = 2.220446049250313e-16;          // np.finfo(np.float64).eps
 
-enum { FLAG_LIMIT = 1, FLAG_DUPLICATE = 2, FLAG_STORE = 4, FLAG_SOLVER = 8 };        // (csrc/moteval.hip, moteval.py)
-
-// (the similarity hota_sim and its helpers: csrc/hota_sim.h, shared with csrc/evalprep.hip)
-
-struct HotaSeq { int64_t gt_base, n_gt, det_base, n_det, off_base, n_frames, obj_base, n_obj; };
-// a sequence's slices of the store; false when one does not lie inside the store's totals: nothing may be indexed then
-__device__ __forceinline__ bool hota_seq(const tmpnn_mot_store& st, int s, HotaSeq& q) {
-    const int64_t* p = st.seq + (size_t)s * 8;
-    q.gt_base = p[0]; q.n_gt = p[1]; q.det_base = p[2]; q.n_det = p[3]; q.off_base = p[4]; q.n_frames = p[5]; q.obj_base = p[6]; q.n_obj = p[7];
-    return q.gt_base >= 0 && q.n_gt >= 0 && q.gt_base + q.n_gt <= st.n_gt && q.det_base >= 0 && q.n_det >= 0 &&
-           q.det_base + q.n_det <= st.n_det && q.off_base >= 0 && q.n_frames >= 0 && q.off_base + q.n_frames + 1 <= st.n_off &&
-           q.obj_base >= 0 && q.n_obj >= 0 && q.obj_base + q.n_obj <= st.n_obj && q.n_gt < 0x7fffffff && q.n_det < HOTA_MAX_DET &&
-           q.n_frames < 0x7fffffff;
+// a sequence's slices of the store (eval_seq)
+__device__ __forceinline__ bool hota_seq(const tmpnn_mot_store& st, int s, EvalSeq& q) {
+    return eval_seq(st.seq, s, st.n_gt, st.n_det, st.n_off, st.n_obj, HOTA_MAX_DET, q);
 }
-
-__device__ __forceinline__ int hota_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 struct HotaThr { double v[HOTA_NA]; };       // ALPHAS - EPS, by value in the kernel arguments
 
@@ -79,97 +66,43 @@ struct HotaWs {
     double* part;                            // [3][n_obj * 19]: the association sums of (object, alpha), at obj_base * 19
 };
 
-__device__ __forceinline__ void hota_flag(unsigned long long* flag, int bits, int64_t frame1) {      // the first flag of a sequence stays
-    atomicCAS(flag, 0ull, (unsigned long long)bits | ((unsigned long long)frame1 << 8));
-}
-__device__ __forceinline__ unsigned long long hota_flag_of(const unsigned long long* flag) {
-    return __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __global__ __launch_bounds__(HP_THREADS) void k_hota_prep(tmpnn_mot_store st, const int32_t* __restrict__ tracks, HotaWs W, int64_t n_pair) {
     __shared__ int s_wave[HP_WAVES + 1];
     __shared__ long long s_sum[HP_WAVES];
     __shared__ int s_bad;
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    HotaSeq q;
+    EvalSeq q;
     const bool ok = hota_seq(st, s, q);
-    // the base of the pair matrices: the entries of the sequences before this one (saturating)
-    long long part = 0;
-    for (int s2 = tid; s2 < s; s2 += HP_THREADS) {
-        const int64_t a = st.seq[(size_t)s2 * 8 + 7], b = st.seq[(size_t)s2 * 8 + 3];
-        const long long e = (a < 0 || b < 0 || a > st.n_obj || b > st.n_det) ? n_pair + 1 : a * b;
-        part = (e > n_pair || part + e > n_pair) ? n_pair + 1 : part + e;
-    }
-    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-    if (lane == 0) s_sum[wave] = part;
     if (tid == 0) s_bad = 0;
-    __syncthreads();
-    long long cbase = 0;
-    for (int w = 0; w < HP_WAVES; ++w) cbase += s_sum[w];
+    const long long cbase = pair_base<HP_THREADS>(st.seq, s, st.n_obj, st.n_det, n_pair, s_sum);       // of the pair matrices
     const bool fits = ok && cbase <= n_pair && q.n_obj * q.n_det <= n_pair - cbase;      // (n_obj < 2^31, n_det < 2^28: no overflow)
     int n_hyp = 0;
     long long n_trk = 0;
     if (fits) {                                              // (uniform over the workgroup)
         const int n_det = (int)q.n_det;
-        int cap = 1;
-        while (cap < 2 * n_det) cap <<= 1;                   // < 4 n_det: at most half of the slots are ever taken
-        int32_t* key = W.tab_key + 4 * q.det_base;
-        int32_t* first = W.tab_first + 4 * q.det_base;
-        int32_t* dense = W.tab_dense + 4 * q.det_base;
-        int32_t* slot = W.slot + q.det_base;
-        int32_t* hidx = W.hidx + q.det_base;
-        int32_t* tc = W.tc + q.det_base;
         int32_t* trs = W.trs + q.det_base;
         int32_t* gc = W.gc + q.obj_base;
         const int32_t* perm = st.det_perm + q.det_base;
         const int32_t* trk = tracks + q.det_base;
         const int32_t* gt_id = st.gt_id + q.gt_base;
-        if (n_det > 0)
-            for (int x = tid; x < cap; x += HP_THREADS) { key[x] = -1; first[x] = 0x7fffffff; }
-        for (int k = tid; k < n_det; k += HP_THREADS) tc[k] = 0;
-        for (int64_t o = tid; o < q.n_obj; o += HP_THREADS) gc[o] = 0;
-        __syncthreads();
         bool bad = false;
-        for (int64_t i = tid; i < q.n_gt; i += HP_THREADS) {
-            const int o = gt_id[i];
-            if (o < 0 || o >= q.n_obj) bad = true; else atomicAdd(&gc[o], 1);
-        }
-        for (int k = tid; k < n_det; k += HP_THREADS) {      // (a row belongs to thread k % HP_THREADS in every pass)
+        for (int64_t o = tid; o < q.n_obj; o += HP_THREADS) gc[o] = 0;
+        // the track of a sorted row, on the way the tracks in frame-sorted order and their number
+        auto id_of = [&](int k) {
             const int p = perm[k];
             int id = -1;
             if (p < 0 || p >= n_det) bad = true; else id = trk[p];
             trs[k] = id;
-            int at = -1;
-            if (id >= 0) {
-                ++n_trk;
-                uint32_t mix = (uint32_t)id * 2654435761u;
-                int h = (int)((mix ^ (mix >> 15)) & (uint32_t)(cap - 1));
-                for (int probe = 0; probe < cap && at < 0; ++probe) {
-                    const int old = atomicCAS(&key[h], -1, id);
-                    if (old == -1 || old == id) at = h; else h = (h + 1) & (cap - 1);
-                }
-                if (at >= 0) atomicMin(&first[at], k);
-            }
-            slot[k] = at;
+            n_trk += id >= 0;
+            return id;
+        };
+        hyp_index<HP_THREADS>(n_det, id_of, W.tab_key + 4 * q.det_base, W.tab_first + 4 * q.det_base, W.tab_dense + 4 * q.det_base,
+                              W.slot + q.det_base, W.hidx + q.det_base, W.tc + q.det_base, s_wave, n_hyp);
+        for (int64_t i = tid; i < q.n_gt; i += HP_THREADS) {      // (gc was cleared before the barriers of hyp_index)
+            const int o = gt_id[i];
+            if (o < 0 || o >= q.n_obj) bad = true; else atomicAdd(&gc[o], 1);
         }
         if (bad) s_bad = 1;
-        __syncthreads();
-        for (int base = 0; base < n_det; base += HP_THREADS) {
-            const int k = base + tid;
-            const int at = k < n_det ? slot[k] : -1;
-            const int is_first = at >= 0 && hota_load(&first[at]) == k;
-            int total;
-            const int pre = block_scan<HP_THREADS>(is_first, s_wave, &total);
-            if (is_first) dense[at] = n_hyp + pre;
-            n_hyp += total;
-        }
-        __syncthreads();
-        for (int k = tid; k < n_det; k += HP_THREADS) {
-            const int at = slot[k];
-            const int hi = at >= 0 ? dense[at] : -1;
-            hidx[k] = (hi >= 0 && hi < n_hyp) ? hi : -1;
-            if (hi >= 0 && hi < n_hyp) atomicAdd(&tc[hi], 1);
-        }
     }
     for (int d = 32; d >= 1; d >>= 1) n_trk += __shfl_xor(n_trk, d);
     __syncthreads();                                         // (s_sum was read by every thread before the first barrier inside)
@@ -181,7 +114,7 @@ __global__ __launch_bounds__(HP_THREADS) void k_hota_prep(tmpnn_mot_store st, co
         W.cbase[s] = fits ? cbase : -1;
         W.n_hyp[s] = n_hyp;
         W.n_trk[s] = t;
-        if (!fits || s_bad) hota_flag(&W.flag[s], FLAG_STORE, 0);
+        if (!fits || s_bad) eval_flag_first(&W.flag[s], FLAG_STORE, 0);
     }
 }
 
@@ -193,7 +126,7 @@ struct HotaFrame {
 
 // Loads frame f into F; nO / nH: the rows on both sides.  Returns 0, or the flag bits of the frame (FLAG_STORE: an offset or an
 // id out of range; FLAG_LIMIT: more than HOTA_MAX rows on a side) -- then F is not to be used.  One wave.
-__device__ __forceinline__ int hota_load_frame(const tmpnn_mot_store& st, const HotaSeq& q, const HotaWs& W, int64_t f, int lane,
+__device__ __forceinline__ int hota_load_frame(const tmpnn_mot_store& st, const EvalSeq& q, const HotaWs& W, int64_t f, int lane,
                                                HotaFrame& F, int& nO, int& nH) {
     const int32_t* gt_off = st.gt_off + q.off_base;
     const int32_t* det_off = st.det_off + q.off_base;
@@ -203,21 +136,19 @@ __device__ __forceinline__ int hota_load_frame(const tmpnn_mot_store& st, const 
     const int32_t* trs = W.trs + q.det_base;
     const int32_t* hidx = W.hidx + q.det_base;
     nO = nH = 0;
-    const int g0 = gt_off[f], g1 = gt_off[f + 1], d0 = det_off[f], d1 = det_off[f + 1];
-    if (g0 < 0 || g1 < g0 || g1 > q.n_gt || d0 < 0 || d1 < d0 || d1 > q.n_det) return FLAG_STORE;
+    int g0, g1, d0, d1;
+    if (!eval_frame_rows(gt_off, det_off, f, q, g0, g1, d0, d1)) return FLAG_STORE;
     nO = g1 - g0;
     bool bad = false;
     for (int base = d0; base < d1; base += 64) {
         const int k = base + lane;
         const int id = k < d1 ? trs[k] : -1;
-        const unsigned long long bal = __ballot(id >= 0);
+        const int p = wave_rank(id >= 0, lane, nH);
         if (id >= 0) {
-            const int p = nH + __popcll(bal & ((1ull << lane) - 1ull));
             const int h = hidx[k];
             if (h < 0 || h >= q.n_det) bad = true;
             if (p < HOTA_MAX) { F.hh[p] = h; F.hbox[p] = det_box[k]; }
         }
-        nH += __popcll(bal);
     }
     if (nO > HOTA_MAX || nH > HOTA_MAX) return FLAG_LIMIT;
     for (int i = lane; i < nO; i += 64) {
@@ -234,22 +165,17 @@ __global__ __launch_bounds__(64) void k_hota_align(tmpnn_mot_store st, HotaWs W)
     __shared__ HotaFrame F;
     __shared__ double s_rs[HOTA_MAX], s_cs[HOTA_MAX];
     const int s = blockIdx.x, lane = threadIdx.x;
-    HotaSeq q;
-    if (!hota_seq(st, s, q) || hota_flag_of(&W.flag[s]) != 0) return;
+    EvalSeq q;
+    if (!hota_seq(st, s, q) || eval_load(&W.flag[s]) != 0) return;
     const int64_t cbase = W.cbase[s];
     if (cbase < 0) return;
     double* pm = W.pm + cbase;
     for (int64_t f = 0; f < q.n_frames; ++f) {
         int nO, nH;
         const int bits = hota_load_frame(st, q, W, f, lane, F, nO, nH);
-        if (bits) { if (lane == 0) hota_flag(&W.flag[s], bits, f + 1); return; }
+        if (bits) { if (lane == 0) eval_flag_first(&W.flag[s], bits, f + 1); return; }
         // a hypothesis id twice in the frame: the host definition raises
-        bool dup = false;
-        for (int j = lane; j < nH; j += 64) {
-            const int h = F.hh[j];
-            for (int j2 = 0; j2 < j; ++j2) dup |= F.hh[j2] == h;
-        }
-        if (__ballot(dup)) { if (lane == 0) hota_flag(&W.flag[s], FLAG_DUPLICATE, f + 1); return; }
+        if (wave_has_duplicate(F.hh, nH, lane)) { if (lane == 0) eval_flag_first(&W.flag[s], FLAG_DUPLICATE, f + 1); return; }
         if (nO > 0 && nH > 0) {
             for (int i = lane; i < nO; i += 64) {            // row sums, in ascending column
                 double a = 0.0;
@@ -266,7 +192,7 @@ __global__ __launch_bounds__(64) void k_hota_align(tmpnn_mot_store st, HotaWs W)
                 const int i = x / nH, j = x % nH;
                 const double sim = hota_sim(F.obox[i], F.hbox[j]);
                 const double den = (s_cs[j] + s_rs[i]) - sim;
-                if (den > 0.0 + HOTA_EPS) {
+                if (den > 0.0 + EVAL_EPS) {
                     double* at = pm + (int64_t)F.oid[i] * q.n_det + F.hh[j];
                     *at = *at + sim / den;
                 }
@@ -312,8 +238,8 @@ __global__ __launch_bounds__(64 * HM_WAVES) void k_hota_match(tmpnn_mot_store st
     const int s = blockIdx.x / frame_groups, group = blockIdx.x % frame_groups;      // (the grid is S x frame_groups blocks)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     HotaMatchShared& S = s_all[wave];
-    HotaSeq q;
-    if (!hota_seq(st, s, q) || hota_flag_of(&W.flag[s]) != 0) return;                    // (k_hota_align flagged it)
+    EvalSeq q;
+    if (!hota_seq(st, s, q) || eval_load(&W.flag[s]) != 0) return;                    // (k_hota_align flagged it)
     const int64_t cbase = W.cbase[s];
     if (cbase < 0) return;
     HotaCost C;
@@ -335,7 +261,7 @@ __global__ __launch_bounds__(64 * HM_WAVES) void k_hota_match(tmpnn_mot_store st
         for (int i = lane; i < nO; i += 64) S.omatch[i] = -1;
         wave_sync();
         const int nr = C.tr ? nH : nO, nc = C.tr ? nO : nH;
-        if (!wave_lsap_solve(S.L, C, nr, nc, lane)) { if (lane == 0) hota_flag(&W.flag[s], FLAG_SOLVER, f + 1); return; }
+        if (!wave_lsap_solve(S.L, C, nr, nc, lane)) { if (lane == 0) eval_flag_first(&W.flag[s], FLAG_SOLVER, f + 1); return; }
         wave_sync();
         for (int row = lane; row < nr; row += 64) {
             const int c = S.L.col4row[row];
@@ -365,10 +291,10 @@ __global__ __launch_bounds__(64 * HM_WAVES) void k_hota_match(tmpnn_mot_store st
 
 __global__ __launch_bounds__(HP_THREADS) void k_hota_fold(tmpnn_mot_store st, HotaWs W, tmpnn_hota_record* __restrict__ out) {
     const int s = blockIdx.x, tid = threadIdx.x;
-    HotaSeq q;
+    EvalSeq q;
     const bool ok = hota_seq(st, s, q);
     const int64_t cbase = ok ? W.cbase[s] : -1;
-    const unsigned long long flag = hota_flag_of(&W.flag[s]);
+    const unsigned long long flag = eval_load(&W.flag[s]);
     int n_hyp = ok ? W.n_hyp[s] : 0;
     if (n_hyp < 0 || n_hyp > q.n_det) n_hyp = 0;
     const bool live = ok && cbase >= 0 && flag == 0;
@@ -421,32 +347,29 @@ __global__ __launch_bounds__(HP_THREADS) void k_hota_fold(tmpnn_mot_store st, Ho
     }
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // carves the workspace; *cleared: the bytes from the start that every call clears
 char* hota_carve(char* p, int S, int64_t n_obj, int64_t n_det, int64_t n_off, int64_t n_pair, HotaWs& w, size_t* cleared) {
-    char* const base = p;
-    auto take = [&p](size_t count, size_t size) { char* at = p; p += align16(count * size); return at; };
+    WsCarver c{p};
     const size_t no = (size_t)n_obj, nd = (size_t)n_det, np = (size_t)n_pair;
-    w.pm = reinterpret_cast<double*>(take(np, 8));
-    w.mc = reinterpret_cast<int32_t*>(take(np * HOTA_NA, 4));
-    w.loc = reinterpret_cast<double*>(take((size_t)n_off * HOTA_NA, 8));
-    w.tp = reinterpret_cast<unsigned long long*>(take((size_t)S * HOTA_NA, 8));
-    w.flag = reinterpret_cast<unsigned long long*>(take((size_t)S, 8));
-    *cleared = (size_t)(p - base);
-    w.trs = reinterpret_cast<int32_t*>(take(nd, 4));
-    w.tab_key = reinterpret_cast<int32_t*>(take(4 * nd, 4));
-    w.tab_first = reinterpret_cast<int32_t*>(take(4 * nd, 4));
-    w.tab_dense = reinterpret_cast<int32_t*>(take(4 * nd, 4));
-    w.slot = reinterpret_cast<int32_t*>(take(nd, 4));
-    w.hidx = reinterpret_cast<int32_t*>(take(nd, 4));
-    w.tc = reinterpret_cast<int32_t*>(take(nd, 4));
-    w.gc = reinterpret_cast<int32_t*>(take(no, 4));
-    w.cbase = reinterpret_cast<int64_t*>(take((size_t)S, 8));
-    w.n_hyp = reinterpret_cast<int32_t*>(take((size_t)S, 4));
-    w.n_trk = reinterpret_cast<int64_t*>(take((size_t)S, 8));
-    w.part = reinterpret_cast<double*>(take(3 * no * HOTA_NA, 8));
-    return p;
+    w.pm = c.take<double>(np);
+    w.mc = c.take<int32_t>(np * HOTA_NA);
+    w.loc = c.take<double>((size_t)n_off * HOTA_NA);
+    w.tp = c.take<unsigned long long>((size_t)S * HOTA_NA);
+    w.flag = c.take<unsigned long long>((size_t)S);
+    *cleared = (size_t)(c.p - p);
+    w.trs = c.take<int32_t>(nd);
+    w.tab_key = c.take<int32_t>(4 * nd);
+    w.tab_first = c.take<int32_t>(4 * nd);
+    w.tab_dense = c.take<int32_t>(4 * nd);
+    w.slot = c.take<int32_t>(nd);
+    w.hidx = c.take<int32_t>(nd);
+    w.tc = c.take<int32_t>(nd);
+    w.gc = c.take<int32_t>(no);
+    w.cbase = c.take<int64_t>((size_t)S);
+    w.n_hyp = c.take<int32_t>((size_t)S);
+    w.n_trk = c.take<int64_t>((size_t)S);
+    w.part = c.take<double>(3 * no * HOTA_NA);
+    return c.p;
 }
 
 }  // namespace
@@ -464,14 +387,12 @@ extern "C" size_t tmpnn_hota_ws(int S, int64_t n_obj, int64_t n_det, int64_t n_o
 extern "C" int tmpnn_hota(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, const double* thresholds, void* ws,
                           size_t ws_bytes, tmpnn_hota_record* out, tmpnn_stream stream) {
     TM_REQUIRE(st != nullptr, "hota: store is null");
-    TM_REQUIRE(st->S >= 0 && st->n_gt >= 0 && st->n_det >= 0 && st->n_off >= 0 && st->n_obj >= 0, "hota: S=%d n_gt=%lld n_det=%lld n_off=%lld n_obj=%lld",
-               st->S, (long long)st->n_gt, (long long)st->n_det, (long long)st->n_off, (long long)st->n_obj);
+    if (const int rc = eval_check_store("hota", st->S, st->n_gt, st->n_det, st->n_off, &st->n_obj, seq_host,
+                                        seq_host && st->seq && out && thresholds, "seq, seq_host, thresholds or out",
+                                        st->gt_off && st->det_off, st->gt_id && st->gt_box, st->det_box && st->det_perm && tracks,
+                                        st->gt_box, st->det_box, EVAL_NO_LIMIT, 0x7fffffff))
+        return rc;
     if (st->S == 0) return TMPNN_OK;
-    TM_REQUIRE(seq_host && st->seq && out && thresholds, "hota: null pointer (seq, seq_host, thresholds or out)");
-    TM_REQUIRE(st->n_off == 0 || (st->gt_off && st->det_off), "hota: null offsets");
-    TM_REQUIRE(st->n_gt == 0 || (st->gt_id && st->gt_box), "hota: null GT arrays");
-    TM_REQUIRE(st->n_det == 0 || (st->det_box && st->det_perm && tracks), "hota: null detection arrays or tracks");
-    TM_REQUIRE(aligned16(st->gt_box) && aligned16(st->det_box), "hota: boxes must be 16-byte aligned");
     TM_REQUIRE(st->n_det < HOTA_MAX_DET, "hota: %lld detections (fewer than %lld expected)", (long long)st->n_det, (long long)HOTA_MAX_DET);
     HotaThr thr;
     for (int a = 0; a < HOTA_NA; ++a) {
@@ -481,14 +402,6 @@ extern "C" int tmpnn_hota(const tmpnn_mot_store* st, const int64_t* seq_host, co
     int64_t n_pair = 0, max_frames = 0;
     for (int s = 0; s < st->S; ++s) {
         const int64_t* q = seq_host + (size_t)s * 8;
-        TM_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[1] < 0x7fffffff && q[0] + q[1] <= st->n_gt, "hota: sequence %d: GT rows [%lld, +%lld) of %lld", s,
-                   (long long)q[0], (long long)q[1], (long long)st->n_gt);
-        TM_REQUIRE(q[2] >= 0 && q[3] >= 0 && q[2] + q[3] <= st->n_det, "hota: sequence %d: detection rows [%lld, +%lld) of %lld", s,
-                   (long long)q[2], (long long)q[3], (long long)st->n_det);
-        TM_REQUIRE(q[4] >= 0 && q[5] >= 0 && q[5] < 0x7fffffff && q[4] + q[5] + 1 <= st->n_off, "hota: sequence %d: offsets [%lld, +%lld + 1) of %lld",
-                   s, (long long)q[4], (long long)q[5], (long long)st->n_off);
-        TM_REQUIRE(q[6] >= 0 && q[7] >= 0 && q[7] < 0x7fffffff && q[6] + q[7] <= st->n_obj, "hota: sequence %d: objects [%lld, +%lld) of %lld", s,
-                   (long long)q[6], (long long)q[7], (long long)st->n_obj);
         TM_REQUIRE(q[7] == 0 || q[3] <= HOTA_MAX_PAIR / q[7], "hota: sequence %d: the pair workspace (n_obj x n_det) passes %lld entries", s,
                    (long long)HOTA_MAX_PAIR);
         n_pair += q[7] * q[3];

@@ -246,8 +246,6 @@ __global__ __launch_bounds__(MAP_TILE) void k_map_class(tmpnn_map_store st, cons
     }
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int check_store(const tmpnn_map_store* st, const char* who, bool eval) {
     TM_REQUIRE(st != nullptr, "%s: store is null", who);
     TM_REQUIRE(st->S >= 0 && st->C >= 0 && st->n_gt >= 0 && st->n_det >= 0 && st->n_grp >= 0 && st->n_live >= 0 && st->n_claim >= 0,
@@ -298,14 +296,11 @@ extern "C" int tmpnn_map_eval(const tmpnn_map_store* st, const int32_t* tracks, 
     const size_t need = tmpnn_map_eval_ws(st->n_gt, st->n_det, st->n_live);
     if (need && (ws == nullptr || ws_bytes < need)) return set_error(TMPNN_EWORKSPACE, "map_eval: workspace %zu < %zu bytes", ws_bytes, need);
     TM_REQUIRE(aligned16(ws), "map_eval: workspace must be 16-byte aligned");
-    char* p = static_cast<char*>(ws);
-    uint8_t* mark = reinterpret_cast<uint8_t*>(p);
-    p += align16((size_t)st->n_det);
-    uint8_t* gstat = reinterpret_cast<uint8_t*>(p);
-    p += align16((size_t)st->n_gt);
-    int32_t* ws_tp = reinterpret_cast<int32_t*>(p);
-    p += align16((size_t)st->n_live * 4);
-    double* ws_prec = reinterpret_cast<double*>(p);
+    WsCarver c{static_cast<char*>(ws)};
+    uint8_t* mark = c.take<uint8_t>((size_t)st->n_det);
+    uint8_t* gstat = c.take<uint8_t>((size_t)st->n_gt);
+    int32_t* ws_tp = c.take<int32_t>((size_t)st->n_live);
+    double* ws_prec = c.take<double>((size_t)st->n_live);
     if (st->n_gt > 0) {
         hipLaunchKernelGGL(k_map_mark, dim3(ceil_div(st->n_gt, MM_THREADS)), dim3(MM_THREADS), 0, as_stream(stream), *st, tracks, mark,
                            gstat);

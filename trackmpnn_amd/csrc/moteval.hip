@@ -24,10 +24,11 @@
 // Every loop is bounded by a count read from the store AFTER it was checked against the store's totals: a frame's offsets must be
 // monotone inside the sequence's rows, permutation entries and object ids inside their ranges; a violation, a frame beyond
 // MOT_MAX rows on either side, or a hypothesis id twice in a frame sets a flag bit in the sequence's record and ends the
-// sequence (nothing is read outside the buffers; the other sequences of the launch are not affected).
+// sequence (nothing is read outside the buffers; the other sequences of the launch are not affected).  The flag bits, the
+// checks and the distance mot_dist are those of csrc/eval_common.h, shared with csrc/hota.hip and csrc/evalprep.hip.
 #pragma clang fp contract(off)
-#include "block_scan.h"
 #include "common.h"
+#include "eval_common.h"
 #include "wave_lsap.h"
 
 using namespace tmpnn;
@@ -41,8 +42,6 @@ constexpr int MOT_LDS_OBJ = 1024;            // sequences of up to this many obj
 constexpr size_t MOT_WS_COST = (size_t)MOT_MAX * MOT_MAX;      // doubles per sequence in the workspace
 constexpr int MOT_NEVER = -0x7fffffff - 1;   // last_match of an object that was never matched (t - 1 of no frame: see below)
 
-enum { FLAG_LIMIT = 1, FLAG_DUPLICATE = 2, FLAG_STORE = 4, FLAG_SOLVER = 8 };
-
 struct MotShared {
     LsapShared<MOT_MAX> L;
     double cost[MOT_LDS_COST];
@@ -52,25 +51,6 @@ struct MotShared {
     int m[MOT_LDS_OBJ], last[MOT_LDS_OBJ];
     unsigned char hmask[MOT_MAX];
 };
-
-// np.maximum / np.minimum: the first operand where it is larger (smaller) or NaN
-__device__ __forceinline__ double mot_max(double a, double b) { return (a > b || a != a) ? a : b; }
-__device__ __forceinline__ double mot_min(double a, double b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ bool mot_finite(double x) { return __builtin_fabs(x) < __builtin_huge_val(); }
-
-// 1 - IoU of two x1 y1 x2 y2 boxes, NaN above 0.5 (host: moteval.mot_dist_host, the same operations in the same order)
-__device__ __forceinline__ double mot_dist(float4 o, float4 h) {
-    const float wo = o.z - o.x, ho = o.w - o.y, wh = h.z - h.x, hh = h.w - h.y;      // float32, as metrics.py:37,39
-    const double otx = o.x, oty = o.y, htx = h.x, hty = h.y;
-    const double obx = otx + (double)wo, oby = oty + (double)ho, hbx = htx + (double)wh, hby = hty + (double)hh;
-    const double iw = mot_max(mot_min(obx, hbx) - mot_max(otx, htx), 0.0);
-    const double ih = mot_max(mot_min(oby, hby) - mot_max(oty, hty), 0.0);
-    const double inter = iw * ih;
-    const double uni = ((double)wo * (double)ho + (double)wh * (double)hh) - inter;
-    double d = 1.0 - inter / uni;
-    if (d > 0.5) d = __builtin_nan("");
-    return d;
-}
 
 // The cost the solver sees: entry (row, col) of the problem is D[row * sr + col * sc] unless the object / hypothesis of the
 // pair was matched in step 1 or the distance is not finite -- then L.  (tr: the problem's rows are hypotheses.)
@@ -84,20 +64,13 @@ struct MotCost {
     __device__ __forceinline__ double at(int row, int col) const {
         const int i = tr ? col : row, j = tr ? row : col;
         const double d = D[(size_t)row * sr + (size_t)col * sc];
-        return (omatch[i] >= 0 || hmask[j] || !mot_finite(d)) ? L : d;
+        return (omatch[i] >= 0 || hmask[j] || !box_finite(d)) ? L : d;
     }
 };
 
-struct MotSeq { int64_t gt_base, n_gt, det_base, n_det, off_base, n_frames, obj_base, n_obj; };
-// a sequence's slices of the store; false when one does not lie inside the store's totals: nothing may be indexed then (the host
-// checked its own copy of the table before the launch; this is the table the kernels index by)
-__device__ __forceinline__ bool mot_seq(const tmpnn_mot_store& st, int s, MotSeq& q) {
-    const int64_t* p = st.seq + (size_t)s * 8;
-    q.gt_base = p[0]; q.n_gt = p[1]; q.det_base = p[2]; q.n_det = p[3]; q.off_base = p[4]; q.n_frames = p[5]; q.obj_base = p[6]; q.n_obj = p[7];
-    return q.gt_base >= 0 && q.n_gt >= 0 && q.gt_base + q.n_gt <= st.n_gt && q.det_base >= 0 && q.n_det >= 0 &&
-           q.det_base + q.n_det <= st.n_det && q.off_base >= 0 && q.n_frames >= 0 && q.off_base + q.n_frames + 1 <= st.n_off &&
-           q.obj_base >= 0 && q.n_obj >= 0 && q.obj_base + q.n_obj <= st.n_obj && q.n_gt < 0x7fffffff && q.n_det < 0x7fffffff &&
-           q.n_frames < 0x7fffffff;
+// a sequence's slices of the store (eval_seq), fewer than max_det detections in it
+__device__ __forceinline__ bool mot_seq(const tmpnn_mot_store& st, int s, EvalSeq& q, int64_t max_det = 0x7fffffff) {
+    return eval_seq(st.seq, s, st.n_gt, st.n_det, st.n_off, st.n_obj, max_det, q);
 }
 // IDENT (tmpnn_mot_summary): the walk also keeps, per object, its events (`present`), the tracked ones, the fragmentation
 // state (0 never tracked, 1 last event tracked, 2 missed after tracked) and count -- in LDS up to MOT_LDS_OBJ objects, in
@@ -110,7 +83,7 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
                                                    size_t obj_stride, Rec* __restrict__ out) {
     __shared__ MotShared S;
     const int s = blockIdx.x, lane = threadIdx.x;
-    MotSeq q;
+    EvalSeq q;
     bool ok = mot_seq(st, s, q);
     const int64_t gt_base = q.gt_base, n_gt = q.n_gt, det_base = q.det_base, n_det = q.n_det, off_base = q.off_base,
                   n_frames = q.n_frames, obj_base = q.obj_base, n_obj = q.n_obj;
@@ -153,20 +126,16 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
     }
     const int nF = ok ? (int)n_frames : 0;
     for (int f = 0; f < nF; ++f) {
-        const int g0 = gt_off[f], g1 = gt_off[f + 1], d0 = det_off[f], d1 = det_off[f + 1];
-        if (g0 < 0 || g1 < g0 || g1 > n_gt || d0 < 0 || d1 < d0 || d1 > n_det) { flag = FLAG_STORE | ((int64_t)(f + 1) << 8); break; }
+        int g0, g1, d0, d1;
+        if (!eval_frame_rows(gt_off, det_off, f, q, g0, g1, d0, d1)) { flag = FLAG_STORE | ((int64_t)(f + 1) << 8); break; }
         const int nO = g1 - g0;
         // H: the detections of the frame with a track, in row order (ballot compaction, 64 rows a round)
         int nH = 0;
         for (int base = d0; base < d1; base += 64) {
             const int k = base + lane;
             const int id = k < d1 ? trs[k] : -1;
-            const unsigned long long bal = __ballot(id >= 0);
-            if (id >= 0) {
-                const int p = nH + __popcll(bal & ((1ull << lane) - 1ull));
-                if (p < MOT_MAX) { S.hid[p] = id; S.hbox[p] = det_box[k]; S.hmask[p] = 0; }
-            }
-            nH += __popcll(bal);
+            const int p = wave_rank(id >= 0, lane, nH);
+            if (id >= 0 && p < MOT_MAX) { S.hid[p] = id; S.hbox[p] = det_box[k]; S.hmask[p] = 0; }
         }
         objects += nO;
         predictions += nH;
@@ -180,12 +149,7 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
         if (__ballot(bad)) { flag = FLAG_STORE | ((int64_t)(f + 1) << 8); break; }
         wave_sync();
         // a hypothesis id twice in the frame: the host definition raises
-        bool dup = false;
-        for (int j = lane; j < nH; j += 64) {
-            const int id = S.hid[j];
-            for (int j2 = 0; j2 < j; ++j2) dup |= S.hid[j2] == id;
-        }
-        if (__ballot(dup)) { flag = FLAG_DUPLICATE | ((int64_t)(f + 1) << 8); break; }
+        if (wave_has_duplicate(S.hid, nH, lane)) { flag = FLAG_DUPLICATE | ((int64_t)(f + 1) << 8); break; }
         int nmatch = 0;
         if (nO > 0 && nH > 0) {
             const int t = f;                                  // frames are consecutive: t - 1 is f - 1 (MOT_NEVER is no frame's)
@@ -201,14 +165,14 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
                     const int want = m[o];
                     int j = -1;
                     for (int j2 = 0; j2 < nH; ++j2) if (j < 0 && S.hid[j2] == want) j = j2;
-                    if (j >= 0 && mot_finite(D[i * nH + j])) { S.omatch[i] = j; S.hmask[j] = 1; last[o] = t; }
+                    if (j >= 0 && box_finite(D[i * nH + j])) { S.omatch[i] = j; S.hmask[j] = 1; last[o] = t; }
                 }
             }
             wave_sync();
             // step 2: the largest finite distance that is left, then the assignment over the L-filled matrix
             for (int x = lane; x < nO * nH; x += 64) {
                 const double d = D[x];
-                if (S.omatch[x / nH] < 0 && !S.hmask[x % nH] && mot_finite(d)) mx = d > mx ? d : mx;
+                if (S.omatch[x / nH] < 0 && !S.hmask[x % nH] && box_finite(d)) mx = d > mx ? d : mx;
             }
             const uint64_t mxk = ~wave_min64(~key_f64(mx));
             if (mxk != key_f64(-__builtin_huge_val())) {
@@ -233,7 +197,7 @@ __global__ __launch_bounds__(64) void k_mot_events(tmpnn_mot_store st, const int
                     if (r < nr) {
                         const int c = S.L.col4row[r];
                         const int i = tr ? c : r, j = tr ? r : c;
-                        if (c >= 0 && c < nc && S.omatch[i] < 0 && !S.hmask[j] && mot_finite(D[i * nH + j])) newj[k] = (i << 16) | j;
+                        if (c >= 0 && c < nc && S.omatch[i] < 0 && !S.hmask[j] && box_finite(D[i * nH + j])) newj[k] = (i << 16) | j;
                     }
                 }
                 wave_sync();
@@ -310,7 +274,8 @@ __global__ __launch_bounds__(MD_THREADS) void k_mot_dist(const float4* __restric
 // Identity figures (tmpnn_mot_summary; host definition: trackmpnn_amd.moteval.mot_summary_host).  After the walk, three kernels:
 //   k_mot_hyp    one workgroup per sequence: the dense index of every kept detection's hypothesis id (ids are arbitrary int32
 //                and change with every evaluation), in order of first appearance in the frame-sorted rows -- an open-addressing
-//                table in the workspace (integer CAS on the id, integer min on the first row), a scan over the first rows;
+//                table in the workspace (integer CAS on the id, integer min on the first row), a scan over the first rows
+//                (hyp_index, csrc/eval_common.h, shared with k_hota_prep);
 //   k_mot_pairs  parallel over sequences and frames, a wave per frame: n[o][h] += 1 for every pair of the frame at a finite
 //                mot_dist (the walk's function and predicate; integer atomics: the result does not depend on their order).
 //                No per-frame limit: rows are read where they lie;
@@ -325,8 +290,6 @@ constexpr int MI_FRAMES = 8;                 // frames of one workgroup of k_mot
 constexpr int64_t MI_MAX_PAIR = (int64_t)1 << 40;
 constexpr int64_t MI_MAX_DET = (int64_t)1 << 28;            // (table slots are int32: 4 n_det of them)
 
-__device__ __forceinline__ int mi_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 struct MotIdentWs {
     int32_t *tab_key, *tab_first, *tab_dense;               // [4 n_det]: a sequence's table starts at 4 det_base
     int32_t *slot, *hidx, *hcount;                          // [n_det]: table slot / dense hypothesis index of a sorted row; rows per hypothesis
@@ -340,70 +303,16 @@ __global__ __launch_bounds__(MI_THREADS) void k_mot_hyp(tmpnn_mot_store st, cons
                                                         int64_t n_pair, tmpnn_mot_summary_record* out) {
     __shared__ int s_wave[MI_WAVES + 1];
     __shared__ long long s_sum[MI_WAVES];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    MotSeq q;
-    const bool ok = mot_seq(st, s, q) && q.n_det < MI_MAX_DET && out[s].flag == 0;
-    // the base of the count matrix: the entries of the sequences before this one (saturating: a table the host did not check
-    // cannot overflow the sum)
-    long long part = 0;
-    for (int s2 = tid; s2 < s; s2 += MI_THREADS) {
-        const int64_t a = st.seq[(size_t)s2 * 8 + 7], b = st.seq[(size_t)s2 * 8 + 3];
-        const long long e = (a < 0 || b < 0 || a > st.n_obj || b > st.n_det) ? n_pair + 1 : a * b;
-        part = (e > n_pair || part + e > n_pair) ? n_pair + 1 : part + e;
-    }
-    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-    if (lane == 0) s_sum[wave] = part;
-    __syncthreads();
-    long long cbase = 0;
-    for (int w = 0; w < MI_WAVES; ++w) cbase += s_sum[w];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    EvalSeq q;
+    const bool ok = mot_seq(st, s, q, MI_MAX_DET) && out[s].flag == 0;
+    const long long cbase = pair_base<MI_THREADS>(st.seq, s, st.n_obj, st.n_det, n_pair, s_sum);      // of the count matrix
     const bool fits = ok && cbase <= n_pair && q.n_obj * q.n_det <= n_pair - cbase;      // (n_obj, n_det < 2^31: no overflow)
     int n_hyp = 0;
     if (fits) {                                              // (uniform over the workgroup)
-        const int n_det = (int)q.n_det;
-        int cap = 1;
-        while (cap < 2 * n_det) cap <<= 1;                   // < 4 n_det: at most half of the slots are ever taken
-        int32_t* key = W.tab_key + 4 * q.det_base;
-        int32_t* first = W.tab_first + 4 * q.det_base;
-        int32_t* dense = W.tab_dense + 4 * q.det_base;
-        int32_t* slot = W.slot + q.det_base;
-        int32_t* hidx = W.hidx + q.det_base;
-        int32_t* hcount = W.hcount + q.det_base;
         const int32_t* trs = ws_tracks + q.det_base;
-        if (n_det > 0)
-            for (int x = tid; x < cap; x += MI_THREADS) { key[x] = -1; first[x] = 0x7fffffff; }
-        for (int k = tid; k < n_det; k += MI_THREADS) hcount[k] = 0;
-        __syncthreads();
-        for (int k = tid; k < n_det; k += MI_THREADS) {      // (a row belongs to thread k % MI_THREADS in every pass)
-            const int id = trs[k];
-            int at = -1;
-            if (id >= 0) {
-                uint32_t mix = (uint32_t)id * 2654435761u;
-                int h = (int)((mix ^ (mix >> 15)) & (uint32_t)(cap - 1));
-                for (int probe = 0; probe < cap && at < 0; ++probe) {
-                    const int old = atomicCAS(&key[h], -1, id);
-                    if (old == -1 || old == id) at = h; else h = (h + 1) & (cap - 1);
-                }
-                if (at >= 0) atomicMin(&first[at], k);
-            }
-            slot[k] = at;
-        }
-        __syncthreads();
-        for (int base = 0; base < n_det; base += MI_THREADS) {
-            const int k = base + tid;
-            const int at = k < n_det ? slot[k] : -1;
-            const int is_first = at >= 0 && mi_load(&first[at]) == k;
-            int total;
-            const int pre = block_scan<MI_THREADS>(is_first, s_wave, &total);
-            if (is_first) dense[at] = n_hyp + pre;
-            n_hyp += total;
-        }
-        __syncthreads();
-        for (int k = tid; k < n_det; k += MI_THREADS) {
-            const int at = slot[k];
-            const int hi = at >= 0 ? dense[at] : -1;
-            hidx[k] = (hi >= 0 && hi < n_hyp) ? hi : -1;
-            if (hi >= 0 && hi < n_hyp) atomicAdd(&hcount[hi], 1);
-        }
+        hyp_index<MI_THREADS>((int)q.n_det, [trs](int k) { return trs[k]; }, W.tab_key + 4 * q.det_base, W.tab_first + 4 * q.det_base,
+                              W.tab_dense + 4 * q.det_base, W.slot + q.det_base, W.hidx + q.det_base, W.hcount + q.det_base, s_wave, n_hyp);
     }
     if (tid == 0) {
         W.cbase[s] = fits ? cbase : -1;
@@ -416,7 +325,7 @@ __global__ __launch_bounds__(MI_THREADS) void k_mot_pairs(tmpnn_mot_store st, co
                                                           int frame_groups, const tmpnn_mot_summary_record* __restrict__ out) {
     const int s = blockIdx.x / frame_groups, group = blockIdx.x % frame_groups;      // (the grid is S x frame_groups blocks)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    MotSeq q;
+    EvalSeq q;
     if (!mot_seq(st, s, q) || out[s].flag != 0) return;
     const int64_t cbase = W.cbase[s];
     if (cbase < 0) return;
@@ -431,15 +340,15 @@ __global__ __launch_bounds__(MI_THREADS) void k_mot_pairs(tmpnn_mot_store st, co
     for (int r = 0; r < MI_FRAMES / MI_WAVES; ++r) {
         const int64_t f = (int64_t)group * MI_FRAMES + r * MI_WAVES + wave;
         if (f >= q.n_frames) return;
-        const int g0 = gt_off[f], g1 = gt_off[f + 1], d0 = det_off[f], d1 = det_off[f + 1];
-        if (g0 < 0 || g1 < g0 || g1 > q.n_gt || d0 < 0 || d1 < d0 || d1 > q.n_det) continue;        // (the walk flags it)
+        int g0, g1, d0, d1;
+        if (!eval_frame_rows(gt_off, det_off, f, q, g0, g1, d0, d1)) continue;                     // (the walk flags it)
         const int nD = d1 - d0;
         const int64_t total = (int64_t)(g1 - g0) * nD;
         for (int64_t x = lane; x < total; x += 64) {
             const int i = g0 + (int)(x / nD), k = d0 + (int)(x % nD);
             const int o = gt_id[i], h = trs[k] >= 0 ? hidx[k] : -1;
             if (o < 0 || o >= q.n_obj || h < 0 || h >= q.n_det) continue;
-            if (mot_finite(mot_dist(gt_box[i], det_box[k]))) atomicAdd(&cnt[(int64_t)o * q.n_det + h], 1);
+            if (box_finite(mot_dist(gt_box[i], det_box[k]))) atomicAdd(&cnt[(int64_t)o * q.n_det + h], 1);
         }
     }
 }
@@ -453,7 +362,7 @@ __global__ __launch_bounds__(MI_THREADS) void k_mot_idtp(tmpnn_mot_store st, Mot
     __shared__ MiKey s_key[2][MI_WAVES];
     __shared__ int s_fail;
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    MotSeq q;
+    EvalSeq q;
     const bool ok = mot_seq(st, s, q) && out[s].flag == 0 && W.cbase[s] >= 0;
     const int n_hyp = ok ? (int)out[s].hypotheses : 0;
     if (!ok || n_hyp < 0 || n_hyp > q.n_det) return;         // (idtp stays -1: no identity figures)
@@ -564,7 +473,47 @@ __global__ __launch_bounds__(MI_THREADS) void k_mot_idtp(tmpnn_mot_store st, Mot
     }
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+// the arguments tmpnn_mot_events and tmpnn_mot_summary share: the store, the host copy of its sequence table, the tracks
+int mot_check_args(const char* fn, const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, const void* out) {
+    TM_REQUIRE(st != nullptr, "%s: store is null", fn);
+    return eval_check_store(fn, st->S, st->n_gt, st->n_det, st->n_off, &st->n_obj, seq_host, seq_host && st->seq && out,
+                            "seq, seq_host or out", st->gt_off && st->det_off, st->gt_id && st->gt_box,
+                            st->det_box && st->det_perm && tracks, st->gt_box, st->det_box, 0x7fffffff, EVAL_NO_LIMIT);
+}
+
+struct MotWalkWs { double* cost; int32_t *m, *last, *tracks; };
+char* mot_carve_walk(char* p, int S, int64_t n_obj, int64_t n_det, MotWalkWs& w) {
+    WsCarver c{p};
+    w.cost = c.take<double>((size_t)S * MOT_WS_COST);
+    w.m = c.take<int32_t>((size_t)n_obj);
+    w.last = c.take<int32_t>((size_t)n_obj);
+    w.tracks = c.take<int32_t>((size_t)n_det);
+    return c.p;
+}
+
+// the workspace of tmpnn_mot_summary behind the walk's: per-object state, hypothesis tables, solver state, count matrices
+char* mot_carve_ident(char* p, int S, int64_t n_obj, int64_t n_det, int64_t n_pair, int32_t*& obj, MotIdentWs& w) {
+    WsCarver c{p};
+    const size_t no = (size_t)n_obj, nd = (size_t)n_det, ncol = no + nd;
+    obj = c.take<int32_t>(4 * (align16(no * 4) / 4));
+    w.tab_key = c.take<int32_t>(4 * nd);
+    w.tab_first = c.take<int32_t>(4 * nd);
+    w.tab_dense = c.take<int32_t>(4 * nd);
+    w.slot = c.take<int32_t>(nd);
+    w.hidx = c.take<int32_t>(nd);
+    w.hcount = c.take<int32_t>(nd);
+    w.cbase = c.take<int64_t>((size_t)S);
+    w.u = c.take<long long>(no);
+    w.v = c.take<long long>(ncol);
+    w.spc = c.take<long long>(ncol);
+    w.col4row = c.take<int32_t>(no);
+    w.SR = c.take<int32_t>(no);
+    w.path = c.take<int32_t>(ncol);
+    w.row4col = c.take<int32_t>(ncol);
+    w.done = c.take<int32_t>(ncol);
+    w.cnt = c.take<int32_t>((size_t)n_pair);
+    return c.p;
+}
 
 }  // namespace
 
@@ -574,72 +523,6 @@ extern "C" size_t tmpnn_mot_events_ws(int S, int64_t n_obj, int64_t n_det) {
 }
 
 extern "C" int tmpnn_mot_max_per_frame(void) { return MOT_MAX; }
-
-namespace {
-
-// the arguments tmpnn_mot_events and tmpnn_mot_summary share: the store, the host copy of its sequence table, the tracks
-int mot_check_args(const char* fn, const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, const void* out) {
-    TM_REQUIRE(st != nullptr, "%s: store is null", fn);
-    TM_REQUIRE(st->S >= 0 && st->n_gt >= 0 && st->n_det >= 0 && st->n_off >= 0 && st->n_obj >= 0,
-               "%s: S=%d n_gt=%lld n_det=%lld n_off=%lld n_obj=%lld", fn, st->S, (long long)st->n_gt, (long long)st->n_det,
-               (long long)st->n_off, (long long)st->n_obj);
-    if (st->S == 0) return TMPNN_OK;
-    TM_REQUIRE(seq_host && st->seq && out, "%s: null pointer (seq, seq_host or out)", fn);
-    TM_REQUIRE(st->n_off == 0 || (st->gt_off && st->det_off), "%s: null offsets", fn);
-    TM_REQUIRE(st->n_gt == 0 || (st->gt_id && st->gt_box), "%s: null GT arrays", fn);
-    TM_REQUIRE(st->n_det == 0 || (st->det_box && st->det_perm && tracks), "%s: null detection arrays or tracks", fn);
-    TM_REQUIRE(aligned16(st->gt_box) && aligned16(st->det_box), "%s: boxes must be 16-byte aligned", fn);
-    for (int s = 0; s < st->S; ++s) {
-        const int64_t* q = seq_host + (size_t)s * 8;
-        TM_REQUIRE(q[0] >= 0 && q[1] >= 0 && q[1] < 0x7fffffff && q[0] + q[1] <= st->n_gt, "%s: sequence %d: GT rows [%lld, +%lld) of %lld", fn, s,
-                   (long long)q[0], (long long)q[1], (long long)st->n_gt);
-        TM_REQUIRE(q[2] >= 0 && q[3] >= 0 && q[3] < 0x7fffffff && q[2] + q[3] <= st->n_det, "%s: sequence %d: detection rows [%lld, +%lld) of %lld",
-                   fn, s, (long long)q[2], (long long)q[3], (long long)st->n_det);
-        TM_REQUIRE(q[4] >= 0 && q[5] >= 0 && q[5] < 0x7fffffff && q[4] + q[5] + 1 <= st->n_off, "%s: sequence %d: offsets [%lld, +%lld + 1) of %lld",
-                   fn, s, (long long)q[4], (long long)q[5], (long long)st->n_off);
-        TM_REQUIRE(q[6] >= 0 && q[7] >= 0 && q[6] + q[7] <= st->n_obj, "%s: sequence %d: objects [%lld, +%lld) of %lld", fn, s,
-                   (long long)q[6], (long long)q[7], (long long)st->n_obj);
-    }
-    return TMPNN_OK;
-}
-
-struct MotWalkWs { double* cost; int32_t *m, *last, *tracks; };
-char* mot_carve_walk(char* p, int S, int64_t n_obj, int64_t n_det, MotWalkWs& w) {
-    w.cost = reinterpret_cast<double*>(p);
-    p += (size_t)S * MOT_WS_COST * sizeof(double);
-    w.m = reinterpret_cast<int32_t*>(p);
-    p += align16((size_t)n_obj * 4);
-    w.last = reinterpret_cast<int32_t*>(p);
-    p += align16((size_t)n_obj * 4);
-    w.tracks = reinterpret_cast<int32_t*>(p);
-    return p + align16((size_t)n_det * 4);
-}
-
-// the workspace of tmpnn_mot_summary behind the walk's: per-object state, hypothesis tables, solver state, count matrices
-char* mot_carve_ident(char* p, int S, int64_t n_obj, int64_t n_det, int64_t n_pair, int32_t*& obj, MotIdentWs& w) {
-    auto take = [&p](size_t count, size_t size) { char* at = p; p += align16(count * size); return at; };
-    const size_t no = (size_t)n_obj, nd = (size_t)n_det, ncol = no + nd;
-    obj = reinterpret_cast<int32_t*>(take(4 * (align16(no * 4) / 4), 4));
-    w.tab_key = reinterpret_cast<int32_t*>(take(4 * nd, 4));
-    w.tab_first = reinterpret_cast<int32_t*>(take(4 * nd, 4));
-    w.tab_dense = reinterpret_cast<int32_t*>(take(4 * nd, 4));
-    w.slot = reinterpret_cast<int32_t*>(take(nd, 4));
-    w.hidx = reinterpret_cast<int32_t*>(take(nd, 4));
-    w.hcount = reinterpret_cast<int32_t*>(take(nd, 4));
-    w.cbase = reinterpret_cast<int64_t*>(take((size_t)S, 8));
-    w.u = reinterpret_cast<long long*>(take(no, 8));
-    w.v = reinterpret_cast<long long*>(take(ncol, 8));
-    w.spc = reinterpret_cast<long long*>(take(ncol, 8));
-    w.col4row = reinterpret_cast<int32_t*>(take(no, 4));
-    w.SR = reinterpret_cast<int32_t*>(take(no, 4));
-    w.path = reinterpret_cast<int32_t*>(take(ncol, 4));
-    w.row4col = reinterpret_cast<int32_t*>(take(ncol, 4));
-    w.done = reinterpret_cast<int32_t*>(take(ncol, 4));
-    w.cnt = reinterpret_cast<int32_t*>(take((size_t)n_pair, 4));
-    return p;
-}
-
-}  // namespace
 
 extern "C" int tmpnn_mot_events(const tmpnn_mot_store* st, const int64_t* seq_host, const int32_t* tracks, void* ws, size_t ws_bytes,
                                 tmpnn_mot_record* out, tmpnn_stream stream) {

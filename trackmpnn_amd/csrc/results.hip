@@ -17,8 +17,8 @@
 // Phases that need every row of the phase before are separate launches: nothing waits for another workgroup inside a launch.
 // Every index is checked against the store's totals before it is used; a sequence that fails a check is flagged, and leaves the
 // others alone.
-#include "block_scan.h"
 #include "common.h"
+#include "eval_common.h"
 
 using namespace tmpnn;
 
@@ -33,7 +33,7 @@ constexpr int RS_MAX_SEQ = 65535;                           // gridDim.y
 constexpr int64_t RS_MAX_DET = (int64_t)1 << 28;            // rows of one sequence: its table has at most 2^30 slots
 constexpr unsigned long long RS_DUP_TOP = 1ull << 40;
 
-enum { FLAG_DUPLICATE = 2, FLAG_STORE = 4, FLAG_NEGATIVE = 16 };        // (2 and 4: csrc/moteval.hip, moteval.py)
+enum { FLAG_NEGATIVE = 16 };                                // (beside FLAG_DUPLICATE and FLAG_STORE of csrc/eval_common.h)
 
 struct ResSeq { int64_t tab_base, n_tab, det_base, n_det, off_base, n_frames; };
 
@@ -196,21 +196,18 @@ __global__ __launch_bounds__(RS_THREADS) void k_res_compact(tmpnn_result_store s
     }
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // carves the workspace; *cleared: the bytes from the start that every call clears
 char* res_carve(char* p, int S, int64_t n_det, int64_t n_tab, ResWs& w, size_t* cleared) {
-    char* const base = p;
-    auto take = [&p](size_t count, size_t size) { char* at = p; p += align16(count * size); return at; };
-    w.tab_key = reinterpret_cast<unsigned*>(take((size_t)n_tab, 4));
-    w.tab_cat = reinterpret_cast<int*>(take((size_t)n_tab, 4));
-    w.tab_score = reinterpret_cast<unsigned*>(take((size_t)n_tab, 4));
-    w.tab_rows = reinterpret_cast<int*>(take((size_t)n_tab, 4));
-    w.dup = reinterpret_cast<unsigned long long*>(take((size_t)S, 8));
-    w.bits = reinterpret_cast<unsigned*>(take((size_t)S, 4));
-    *cleared = (size_t)(p - base);
-    w.slot = reinterpret_cast<int*>(take((size_t)n_det, 4));
-    return p;
+    WsCarver c{p};
+    w.tab_key = c.take<unsigned>((size_t)n_tab);
+    w.tab_cat = c.take<int>((size_t)n_tab);
+    w.tab_score = c.take<unsigned>((size_t)n_tab);
+    w.tab_rows = c.take<int>((size_t)n_tab);
+    w.dup = c.take<unsigned long long>((size_t)S);
+    w.bits = c.take<unsigned>((size_t)S);
+    *cleared = (size_t)(c.p - p);
+    w.slot = c.take<int>((size_t)n_det);
+    return c.p;
 }
 
 }  // namespace

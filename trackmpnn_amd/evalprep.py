@@ -51,7 +51,7 @@ import torch
 
 from . import _lib
 from .hota import EPS, hota_sim_host
-from .moteval import FLAG_LIMIT, FLAG_SOLVER, FLAG_STORE, _boxes, _frame_range, _ints, _pack_tracks
+from .moteval import FLAG_LIMIT, FLAG_SOLVER, FLAG_STORE, _boxes, _flag_message, _frame_range, _ints, _pack_tracks
 
 MAX_PER_FRAME = 256            # detection rows / GT rows of one frame, all categories, the device kernel takes (csrc/evalprep.hip EP_MAX)
 LDS_SCORE = 1024               # frames of up to this many pairs keep the solver's scores in LDS (csrc/evalprep.hip)
@@ -414,9 +414,7 @@ class EvalPrep:
         rec = self._out.cpu().numpy()                               # (the one device -> host copy; it waits for the launch)
         bad = [(s, int(rec[s, 7])) for s in range(st.S) if rec[s, 7] != 0 and not self._left_out[s]]
         if bad and check:
-            msg = '; '.join(f'sequence {s}' + (f', frame {st.t0[s] + (f >> 8) - 1}: ' if f >> 8 else ': ')
-                            + ', '.join(txt for bit, txt in _FLAG_TEXT.items() if f & bit) for s, f in bad)
-            raise RuntimeError(f'EvalPrep.read: {msg}')
+            raise RuntimeError(_flag_message('EvalPrep.read', bad, st.t0.__getitem__, _FLAG_TEXT))
         per: List = []
         for s in range(st.S):
             if self._left_out[s]:

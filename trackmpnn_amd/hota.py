@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .moteval import _FLAG_TEXT, MotStore, _boxes, _check_unique, _frame_range, _ints, _pack_tracks
+from .moteval import (_FLAG_TEXT, MotStore, _boxes, _check_unique, _flag_message, _frame_range, _ints, _pack_tracks,
+                      _upload_mot_store)
 
 ALPHAS = np.arange(0.05, 0.99, 0.05)           # the 19 localisation thresholds, as numpy produces them
 EPS = np.finfo(np.float64).eps
@@ -238,10 +239,7 @@ class HotaEvaluator:
                              'with hota_host')
         self._seq_host = np.ascontiguousarray(st.seq)
         self._thr = np.ascontiguousarray(ALPHAS - EPS)
-        up = lambda a: torch.from_numpy(a).to(dev)
-        self._t = {k: up(getattr(st, k)) for k in ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')}
-        self._c = _lib.CMotStore(st.S, 0, st.n_gt, st.n_det, st.n_off, st.n_obj, *[self._t[k].data_ptr() or None for k in
-                            ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')])
+        self._t, self._c = _upload_mot_store(st, dev)
         self._ws = torch.empty(max(self._ws_bytes, 8), dtype=torch.uint8, device=dev)
         self._tracks = torch.empty(max(st.n_det, 1), dtype=torch.int32, device=dev)
         self._out = torch.zeros(max(st.S, 1), RECORD_WORDS, dtype=torch.int64, device=dev)
@@ -261,9 +259,7 @@ class HotaEvaluator:
         fl = rec.view(np.float64)
         bad = [(s, int(rec[s, 23])) for s in range(self.store.S) if rec[s, 23] != 0 and not self._left_out[s]]
         if bad and check:
-            msg = '; '.join(f'sequence {s}' + (f', frame {self.store.t0[s] + (f >> 8) - 1}: ' if f >> 8 else ': ')
-                            + ', '.join(txt for bit, txt in _FLAG_TEXT.items() if f & bit) for s, f in bad)
-            raise RuntimeError(f'HotaEvaluator.read: {msg}')
+            raise RuntimeError(_flag_message('HotaEvaluator.read', bad, self.store.t0.__getitem__, _FLAG_TEXT))
         per: List = []
         for s in range(self.store.S):
             if self._left_out[s]:

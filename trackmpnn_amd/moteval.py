@@ -397,6 +397,20 @@ def _pack_tracks(st: MotStore, tracks: Sequence, buf: torch.Tensor, who: str) ->
     return left_out
 
 
+def _flag_message(who: str, flags, t0_of, texts: Dict[int, str]) -> str:
+    """The text of a read() that met flag words.  flags: (sequence, word) pairs; t0_of(s): the frame at which the frame count in
+    the words of sequence s starts; texts: bit -> text."""
+    return f'{who}: ' + '; '.join(f'sequence {s}' + (f', frame {t0_of(s) + (f >> 8) - 1}: ' if f >> 8 else ': ')
+                                  + ', '.join(txt for bit, txt in texts.items() if f & bit) for s, f in flags)
+
+
+def _upload_mot_store(st: MotStore, dev):
+    """The store on the device: (its arrays as tensors by name, the struct tmpnn_mot_store over them)."""
+    names = ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')
+    t = {k: torch.from_numpy(getattr(st, k)).to(dev) for k in names}
+    return t, _lib.CMotStore(st.S, 0, st.n_gt, st.n_det, st.n_off, st.n_obj, *[t[k].data_ptr() or None for k in names])
+
+
 RECORD_WORDS = 9               # struct tmpnn_mot_record: seven int64 counts, the flag word, dist_sum (double)
 SUMMARY_WORDS = 16             # struct tmpnn_mot_summary_record: the same, then SUMMARY_KEYS, idtp, hypotheses
 
@@ -435,10 +449,7 @@ class MotEvaluator:
                              f'{self._n_pair} entries, more than MAX_PAIR_COUNTS = {MAX_PAIR_COUNTS}: score such a set on the host '
                              'with mot_summary_host')
         self._seq_host = np.ascontiguousarray(st.seq)
-        up = lambda a: torch.from_numpy(a).to(dev)
-        self._t = {k: up(getattr(st, k)) for k in ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')}
-        self._c = _lib.CMotStore(st.S, 0, st.n_gt, st.n_det, st.n_off, st.n_obj, *[self._t[k].data_ptr() or None for k in
-                            ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')])
+        self._t, self._c = _upload_mot_store(st, dev)
         lib = _lib.load()
         self._ws_bytes = int(lib.tmpnn_mot_summary_ws(st.S, st.n_obj, st.n_det, self._n_pair) if self.identity else
                              lib.tmpnn_mot_events_ws(st.S, st.n_obj, st.n_det))
@@ -462,9 +473,7 @@ class MotEvaluator:
         dsum = rec.view(np.float64)[:, 8]
         bad = [(s, int(rec[s, 7])) for s in range(self.store.S) if rec[s, 7] != 0 and not self._left_out[s]]
         if bad and check:
-            msg = '; '.join(f'sequence {s}' + (f', frame {self.store.t0[s] + (f >> 8) - 1}: ' if f >> 8 else ': ')
-                            + ', '.join(txt for bit, txt in _FLAG_TEXT.items() if f & bit) for s, f in bad)
-            raise RuntimeError(f'MotEvaluator.read: {msg}')
+            raise RuntimeError(_flag_message('MotEvaluator.read', bad, self.store.t0.__getitem__, _FLAG_TEXT))
         per = []
         for s in range(self.store.S):
             if self._left_out[s]:

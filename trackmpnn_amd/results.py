@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .moteval import FLAG_DUPLICATE, FLAG_STORE, _boxes, _ints, _pack_tracks
+from .moteval import FLAG_DUPLICATE, FLAG_STORE, _boxes, _flag_message, _ints, _pack_tracks
 
 
 @dataclass(frozen=True)
@@ -379,9 +379,7 @@ class TrackResults:
         filt, order = out[self._rec_ints:self._rec_ints + st.n_det], out[self._rec_ints + st.n_det:]
         bad = [(s, int(rec[s, 4])) for s in range(st.S) if rec[s, 4] != 0 and not self._left_out[s]]
         if bad and check:
-            msg = '; '.join(f'sequence {s}' + (f', frame {st.t_range[s][0] + (f >> 8) - 1}: ' if f >> 8 else ': ')
-                            + ', '.join(txt for bit, txt in _FLAG_TEXT.items() if f & bit) for s, f in bad)
-            raise RuntimeError(f'TrackResults.read: {msg}')
+            raise RuntimeError(_flag_message('TrackResults.read', bad, lambda s: st.t_range[s][0], _FLAG_TEXT))
         per: List = []
         for s in range(st.S):
             if self._left_out[s]:
