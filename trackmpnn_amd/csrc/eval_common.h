@@ -12,7 +12,7 @@
 
 namespace tmpnn {
 
-// the low byte of a sequence's flag word (moteval.py, evalprep.py, results.py); the 1-based frame index sits above it
+// the low byte of a sequence's flag word (Python: trackmpnn_amd/evalstore.py); the 1-based frame index sits above it
 enum { FLAG_LIMIT = 1, FLAG_DUPLICATE = 2, FLAG_STORE = 4, FLAG_SOLVER = 8 };
 constexpr double EVAL_EPS = 2.220446049250313e-16;          // np.finfo(np.float64).eps
 

@@ -42,7 +42,6 @@ The rule, for one frame (evalprep_frame_host):
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -50,8 +49,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from .evalstore import FLAG_LIMIT, FLAG_SOLVER, FLAG_STORE, SeqTable, SequenceEvaluator, _boxes, _frame_range, _ints, frame_sort
 from .hota import EPS, hota_sim_host
-from .moteval import FLAG_LIMIT, FLAG_SOLVER, FLAG_STORE, _boxes, _flag_message, _frame_range, _ints, _pack_tracks
 
 MAX_PER_FRAME = 256            # detection rows / GT rows of one frame, all categories, the device kernel takes (csrc/evalprep.hip EP_MAX)
 LDS_SCORE = 1024               # frames of up to this many pairs keep the solver's scores in LDS (csrc/evalprep.hip)
@@ -316,45 +315,30 @@ class EvalPrepStore:
     """
 
     def __init__(self, sequences: Sequence[Dict], rules: PrepRules):
-        S = len(sequences)
-        self.S, self.rules = S, rules
-        self.seq = np.zeros((S, 8), np.int64)
+        self.S, self.rules = len(sequences), rules
         self.t0: List[int] = []
         self.gt_keep: List[np.ndarray] = []
-        gt_off, det_off, gt_code, det_code, gt_box, det_box, det_perm = [], [], [], [], [], [], []
-        g_base = d_base = f_base = 0
+        tab = SeqTable('EvalPrepStore', self.S)
         for s, q in enumerate(sequences):
             a = _sequence_arrays(q, f'EvalPrepStore: sequence {s}')
             t0, nf = _frame_range(a['det_frame'], a['gt_frame'])
             nd, ng = a['det_frame'].shape[0], a['gt_frame'].shape[0]
-            if nf >= 2 ** 31 - 1 or max(nd, ng) >= 2 ** 31 - 1:
-                raise ValueError(f'EvalPrepStore: sequence {s} is beyond int32')
+            tab.check(s, nf, max(nd, ng))
             code = _gt_codes(a['gt_cat'], a['gt_occ'], a['gt_trunc'], rules)
-            go, do = np.argsort(a['gt_frame'], kind='stable'), np.argsort(a['det_frame'], kind='stable')
-            edges = np.arange(t0, t0 + nf + 1)
-            gt_off.append(np.searchsorted(a['gt_frame'][go], edges, side='left').astype(np.int32))
-            det_off.append(np.searchsorted(a['det_frame'][do], edges, side='left').astype(np.int32))
-            gt_code.append(code[go])
-            det_code.append((a['det_cat'][do] == int(rules.cls)).astype(np.uint8))
-            gt_box.append(a['gt_box'][go])
-            det_box.append(a['det_box'][do])
-            det_perm.append(do.astype(np.int32))
-            self.seq[s, :6] = (g_base, ng, d_base, nd, f_base, nf)
+            go, g_off = frame_sort(a['gt_frame'], t0, nf)
+            do, d_off = frame_sort(a['det_frame'], t0, nf)
+            tab.add(s, ng, nd, nf, gt_off=g_off, det_off=d_off, gt_code=code[go], det_code=a['det_cat'][do] == int(rules.cls),
+                    gt_box=a['gt_box'][go], det_box=a['det_box'][do], det_perm=do)
             self.t0.append(t0)
             self.gt_keep.append(code == GT_SCORED)
-            g_base += ng
-            d_base += nd
-            f_base += nf + 1
-
-        def cat(parts, dtype, tail=()):
-            return np.ascontiguousarray(np.concatenate(parts).astype(dtype)) if parts else np.zeros((0,) + tail, dtype)
-        self.gt_off, self.det_off, self.det_perm = cat(gt_off, np.int32), cat(det_off, np.int32), cat(det_perm, np.int32)
-        self.gt_code, self.det_code = cat(gt_code, np.uint8), cat(det_code, np.uint8)
-        self.gt_box, self.det_box = cat(gt_box, np.float32, (4,)).reshape(-1, 4), cat(det_box, np.float32, (4,)).reshape(-1, 4)
-        self.n_gt, self.n_det, self.n_off = g_base, d_base, f_base
+        self.seq = tab.seq
+        self.gt_off, self.det_off, self.det_perm = (tab.pack(k, np.int32) for k in ('gt_off', 'det_off', 'det_perm'))
+        self.gt_code, self.det_code = tab.pack('gt_code', np.uint8), tab.pack('det_code', np.uint8)
+        self.gt_box, self.det_box = tab.pack('gt_box', np.float32, (4,)), tab.pack('det_box', np.float32, (4,))
+        self.n_gt, self.n_det, self.n_off, _ = tab.totals
 
 
-class EvalPrep:
+class EvalPrep(SequenceEvaluator):
     """The benchmark's preprocessing of S sequences on the device.  sequences: one dict per sequence with det_frame, det_cat,
     det_box, gt_frame, gt_track, gt_cat, gt_box, gt_occ, gt_trunc (the same in every epoch -- only the tracks change); rules: a
     PrepRules (KITTI_CAR, KITTI_PEDESTRIAN).  The store is built on the host and uploaded once.
@@ -375,55 +359,29 @@ class EvalPrep:
     tracks_out and every count equal evalprep_host.  A frame takes at most MAX_PER_FRAME detection rows and as many GT rows, all
     categories (beyond: FLAG_LIMIT for that sequence only; the host definition has no limit)."""
 
+    STEP, FLAG_WORD, FLAG_TEXT = ('apply', 'apply'), 7, _FLAG_TEXT
+
     def __init__(self, sequences: Sequence[Dict], rules: PrepRules = KITTI_CAR, device='cuda:0'):
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError(f'EvalPrep on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a cuda '
-                               'device, or filter on the host with evalprep_host')
-        self.device = dev
+        super().__init__(device, 'filter on the host with evalprep_host')
         self.rules = rules
         self._sequences = list(sequences)
-        self.store = st = EvalPrepStore(sequences, rules)
-        self._seq_host = np.ascontiguousarray(st.seq)
+        st = EvalPrepStore(sequences, rules)
         names = ('seq', 'gt_off', 'det_off', 'gt_code', 'det_code', 'gt_box', 'det_box', 'det_perm')
-        self._t = {k: torch.from_numpy(getattr(st, k)).to(dev) for k in names}
-        self._c = _lib.CEvalPrepStore(st.S, 0, st.n_gt, st.n_det, st.n_off, float(rules.min_height) + EPS,
-                                      *[self._t[k].data_ptr() or None for k in names])
-        self._tracks = torch.empty(max(st.n_det, 1), dtype=torch.int32, device=dev)
-        self._filtered = torch.full((max(st.n_det, 1),), -1, dtype=torch.int32, device=dev)
-        self._out = torch.zeros(max(st.S, 1), RECORD_WORDS, dtype=torch.int64, device=dev)
-        self._left_out = [False] * st.S
-        self._pending = False
+        self._c = _lib.CEvalPrepStore(st.S, 0, st.n_gt, st.n_det, st.n_off, float(rules.min_height) + EPS, *self._attach(st, names))
+        self._filtered = torch.full((max(st.n_det, 1),), -1, dtype=torch.int32, device=self.device)
+        self._out = torch.zeros(max(st.S, 1), RECORD_WORDS, dtype=torch.int64, device=self.device)
 
     def apply(self, tracks: Sequence) -> None:
-        left_out = _pack_tracks(self.store, tracks, self._tracks, 'EvalPrep.apply')
-        _lib.call('tmpnn_evalprep', C.byref(self._c), self._seq_host.ctypes.data, self._tracks.data_ptr(), self._filtered.data_ptr(),
-                  self._out.data_ptr(), _lib.raw_stream(self.device))
-        self._left_out = left_out
-        self._pending = True
+        self._enqueue('tmpnn_evalprep', tracks, self._filtered.data_ptr(), self._out.data_ptr())
 
     def filtered_tracks(self) -> List[torch.Tensor]:
-        if not self._pending:
-            raise RuntimeError('EvalPrep.filtered_tracks: no apply has been enqueued')
-        return [self._filtered[int(b):int(b) + int(n)] for b, n in self.store.seq[:, 2:4]]
+        return self._views(self._filtered)
+
+    def _row(self, s, rec, fl, out) -> Dict:
+        return {k: int(rec[s, i]) for i, k in enumerate(COUNT_KEYS)}
 
     def read(self, check: bool = True):
-        if not self._pending:
-            raise RuntimeError('EvalPrep.read: no apply has been enqueued')
-        st = self.store
-        rec = self._out.cpu().numpy()                               # (the one device -> host copy; it waits for the launch)
-        bad = [(s, int(rec[s, 7])) for s in range(st.S) if rec[s, 7] != 0 and not self._left_out[s]]
-        if bad and check:
-            raise RuntimeError(_flag_message('EvalPrep.read', bad, st.t0.__getitem__, _FLAG_TEXT))
-        per: List = []
-        for s in range(st.S):
-            if self._left_out[s]:
-                per.append(None)
-                continue
-            c = {k: int(rec[s, i]) for i, k in enumerate(COUNT_KEYS)}
-            if not check:
-                c['flag'] = int(rec[s, 7])
-            per.append(c)
+        per = self._read(check)
         return per, prep_overall(per)
 
     def eval_sequences(self) -> List[Dict]:

@@ -19,15 +19,14 @@ what the benchmark scores.  It uses hota_sim_host, so the two stages agree on ev
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Sequence
+from typing import Dict, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
-from .moteval import (_FLAG_TEXT, MotStore, _boxes, _check_unique, _flag_message, _frame_range, _ints, _pack_tracks,
-                      _upload_mot_store)
+from .evalstore import SequenceEvaluator, _boxes, _frame_range, _ints
+from .moteval import _FLAG_TEXT, MotStore, _attach_mot_store, _check_unique
 
 ALPHAS = np.arange(0.05, 0.99, 0.05)           # the 19 localisation thresholds, as numpy produces them
 EPS = np.finfo(np.float64).eps
@@ -205,7 +204,7 @@ def synth_hota_sequence(seed: int, frames: int, objects: int = 8, **kw) -> Dict:
     return q
 
 
-class HotaEvaluator:
+class HotaEvaluator(SequenceEvaluator):
     """HOTA of S sequences on the device.  sequences: the dicts MotEvaluator takes (det_frame, det_box, gt_frame, gt_track,
     gt_box; the same in every epoch); the evaluator builds its own MotStore and uploads it once.  The calling contract is
     MotEvaluator's:
@@ -215,61 +214,39 @@ class HotaEvaluator:
                               the number of sequences, no host wait.
         ev.read()             the one device -> host copy: (per_sequence, overall); per_sequence[i] is the dict of hota_host
                               (None for a sequence left out), overall that of hota_overall.  RuntimeError when a sequence's
-                              flag word is set, with the bits and messages of moteval.py (check=False: no error, every dict
-                              has the sequence's 'flag' word instead).
+                              flag word is set, with the bits of evalstore.py and the messages of moteval.py (check=False:
+                              no error, every dict has the sequence's 'flag' word instead).
 
     Every record field equals hota_host: integers exactly, float64 bit for bit.  A frame takes at most moteval.MAX_PER_FRAME rows on
     either side (beyond: FLAG_LIMIT for that sequence only).  The workspace holds objects x detections entries of PAIR_BYTES per
     sequence: a store beyond MAX_HOTA_PAIRS entries (or a workspace beyond 2 GiB) raises ValueError -- score it with hota_host.
     No class filtering and no DontCare removal here: evalprep.EvalPrep is the benchmark's preprocessing in front of this."""
+    FLAG_WORD, FLAG_TEXT = 23, _FLAG_TEXT
 
     def __init__(self, sequences: Sequence[Dict], device='cuda:0'):
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError(f'HotaEvaluator on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a '
-                               'cuda device, or score on the host with hota_host')
-        self.device = dev
-        self.store = st = MotStore(sequences)
+        super().__init__(device, 'score on the host with hota_host')
+        st = MotStore(sequences)
         self._n_pair = int((st.seq[:, 7] * st.seq[:, 3]).sum())
-        lib = _lib.load()
-        self._ws_bytes = int(lib.tmpnn_hota_ws(st.S, st.n_obj, st.n_det, st.n_off, self._n_pair)) if self._n_pair <= MAX_HOTA_PAIRS else 0
-        if self._n_pair > MAX_HOTA_PAIRS or self._ws_bytes > MAX_WS_BYTES:
+        ws_bytes = int(_lib.load().tmpnn_hota_ws(st.S, st.n_obj, st.n_det, st.n_off, self._n_pair)) if self._n_pair <= MAX_HOTA_PAIRS else 0
+        if self._n_pair > MAX_HOTA_PAIRS or ws_bytes > MAX_WS_BYTES:
             raise ValueError(f'HotaEvaluator: the pair workspace (objects x detections per sequence) has {self._n_pair} entries, more '
                              f'than MAX_HOTA_PAIRS = {MAX_HOTA_PAIRS}, or the workspace passes 2 GiB: score such a set on the host '
                              'with hota_host')
-        self._seq_host = np.ascontiguousarray(st.seq)
         self._thr = np.ascontiguousarray(ALPHAS - EPS)
-        self._t, self._c = _upload_mot_store(st, dev)
-        self._ws = torch.empty(max(self._ws_bytes, 8), dtype=torch.uint8, device=dev)
-        self._tracks = torch.empty(max(st.n_det, 1), dtype=torch.int32, device=dev)
-        self._out = torch.zeros(max(st.S, 1), RECORD_WORDS, dtype=torch.int64, device=dev)
-        self._left_out = [False] * st.S
-        self._pending = False
+        _attach_mot_store(self, st)
+        self._workspace(ws_bytes)
+        self._out = torch.zeros(max(st.S, 1), RECORD_WORDS, dtype=torch.int64, device=self.device)
 
     def evaluate(self, tracks: Sequence) -> None:
-        self._left_out = _pack_tracks(self.store, tracks, self._tracks, 'HotaEvaluator.evaluate')
-        _lib.call('tmpnn_hota', C.byref(self._c), self._seq_host.ctypes.data, self._tracks.data_ptr(), self._thr.ctypes.data,
-                  self._ws.data_ptr(), self._ws_bytes, self._out.data_ptr(), _lib.raw_stream(self.device))
-        self._pending = True
+        self._enqueue('tmpnn_hota', tracks, self._thr.ctypes.data, self._ws.data_ptr(), self._ws_bytes, self._out.data_ptr())
+
+    def _row(self, s, rec, fl, out) -> Dict:
+        r = {'tp': rec[s, :NA].copy()}
+        r.update({k: int(rec[s, NA + i]) for i, k in enumerate(INT_KEYS)})
+        r.update({k: fl[s, 24 + NA * i:24 + NA * (i + 1)].copy() for i, k in enumerate(SUM_KEYS)})
+        return _derived(r)
 
     def read(self, check: bool = True):
-        if not self._pending:
-            raise RuntimeError('HotaEvaluator.read: no evaluation has been enqueued')
-        rec = self._out.cpu().numpy()                               # (the one device -> host copy; it waits for the launches)
-        fl = rec.view(np.float64)
-        bad = [(s, int(rec[s, 23])) for s in range(self.store.S) if rec[s, 23] != 0 and not self._left_out[s]]
-        if bad and check:
-            raise RuntimeError(_flag_message('HotaEvaluator.read', bad, self.store.t0.__getitem__, _FLAG_TEXT))
-        per: List = []
-        for s in range(self.store.S):
-            if self._left_out[s]:
-                per.append(None)
-                continue
-            r = {'tp': rec[s, :NA].copy()}
-            r.update({k: int(rec[s, NA + i]) for i, k in enumerate(INT_KEYS)})
-            r.update({k: fl[s, 24 + NA * i:24 + NA * (i + 1)].copy() for i, k in enumerate(SUM_KEYS)})
-            r = _derived(r)
-            if not check:
-                r['flag'] = int(rec[s, 23])
-            per.append(r)
+        per = self._read(check)
         return per, hota_overall([p for p in per if p is not None])
+

@@ -43,7 +43,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .moteval import _boxes, _ints
+from .evalstore import _boxes, _ints
 
 MAX_PER_FRAME = 256            # detections / GT rows of one frame the device takes (csrc/labeldet.hip LB_MAX)
 WAVE_FRAME = 64                # frames with at most this many rows on either side are labelled by one wave

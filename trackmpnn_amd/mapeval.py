@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .moteval import _boxes, _ints, synth_mot_sequence
+from .evalstore import _boxes, _ints, cat, cuda_device
+from .moteval import synth_mot_sequence
 
 FLAG_STORE = 1
 RECORD_WORDS = 5               # struct tmpnn_map_record: ap (double), annotations, kept, true_positives, flag (int64)
@@ -196,10 +197,6 @@ def synth_map_sequence(seed: int, frames: int, classes: int = 3, ties: bool = Fa
             'gt_frame': gt_frame, 'gt_track': gt_track, 'gt_box': gt_box, 'gt_cat': gt_cat}
 
 
-def _cat(parts, dtype, tail=()):
-    return np.ascontiguousarray(np.concatenate(parts).astype(dtype)) if parts else np.zeros((0,) + tail, dtype)
-
-
 class MapStore:
     """What the evaluator keeps of S sequences (dicts with det_frame, det_cat, det_score, det_box, gt_frame, gt_cat, gt_box;
     categories integers, boxes and scores finite, else ValueError).  GT rows sorted stably by (class, sequence, frame), so that
@@ -226,10 +223,10 @@ class MapStore:
         self.det_base = np.zeros(S + 1, np.int64)
         self.det_base[1:] = np.cumsum([f[0].shape[0] for f in fields])
         self.n_det = int(self.det_base[-1])
-        g_seq = _cat([np.full(f[4].shape[0], s) for s, f in enumerate(fields)], np.int64)
-        g_frame = _cat([f[4] for f in fields], np.int64)
-        g_cls = _cat([[cls_index[int(c)] for c in f[5]] for f in fields], np.int64)
-        g_box = _cat([f[6] for f in fields], np.float32, (4,)).reshape(-1, 4)
+        g_seq = cat([np.full(f[4].shape[0], s) for s, f in enumerate(fields)], np.int64)
+        g_frame = cat([f[4] for f in fields], np.int64)
+        g_cls = cat([[cls_index[int(c)] for c in f[5]] for f in fields], np.int64)
+        g_box = cat([f[6] for f in fields], np.float32, (4,)).reshape(-1, 4)
         self.n_gt = int(g_seq.shape[0])
         if max(self.n_gt, self.n_det) >= 2 ** 31 - 1:
             raise ValueError('MapStore: the store is indexed by int32')
@@ -256,8 +253,8 @@ class MapStore:
                     d_cls[base + i] = c
                     det_grp[base + i] = group.get((s, t, c), -1)
         self.det_grp = det_grp
-        self.det_box = _cat([f[3] for f in fields], np.float32, (4,)).reshape(-1, 4)
-        self.det_score = _cat([f[2] for f in fields], np.float32)
+        self.det_box = cat([f[3] for f in fields], np.float32, (4,)).reshape(-1, 4)
+        self.det_score = cat([f[2] for f in fields], np.float32)
         live = np.where(d_cls >= 0)[0]
         order = live[np.lexsort((live, -self.det_score[live], d_cls[live]))]
         self.order = order.astype(np.int32)
@@ -304,11 +301,7 @@ class MapEvaluator:
     """
 
     def __init__(self, sequences: Sequence[Dict], device='cuda:0'):
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError(f'MapEvaluator on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a '
-                               'cuda device, or score on the host with map_host')
-        self.device = dev
+        self.device = dev = cuda_device(device, 'MapEvaluator', 'score on the host with map_host')
         self.store = st = MapStore(sequences)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         self._t = {k: up(getattr(st, k)) for k in ('gt_box', 'gt_seq', 'cls_gt_off', 'grp_off', 'det_box', 'det_grp', 'cls_off',

@@ -17,40 +17,23 @@ in py-motmetrics >= 1.2 and as metrics.py calls them ("unpi
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
+from .evalstore import (FLAG_DUPLICATE, FLAG_LIMIT, FLAG_SOLVER, FLAG_STORE, SeqTable, SequenceEvaluator, _boxes, _frame_range, _ints,
+                        frame_sort)
 
 MAX_PER_FRAME = 256            # GT rows / kept hypotheses of one frame the device solver takes (csrc/moteval.hip MOT_MAX)
 COUNT_KEYS = ('objects', 'predictions', 'matches', 'switches', 'false_positives', 'misses', 'frames')
 SUMMARY_KEYS = ('unique_objects', 'mostly_tracked', 'partially_tracked', 'mostly_lost', 'fragmentations')
 MAX_PAIR_COUNTS = 2 ** 27      # entries (int32) of the identity count matrices of one store: sum over sequences of n_obj x n_det
-FLAG_LIMIT, FLAG_DUPLICATE, FLAG_STORE, FLAG_SOLVER = 1, 2, 4, 8
 _FLAG_TEXT = {FLAG_LIMIT: f'a frame has more than {MAX_PER_FRAME} GT rows or kept hypotheses',
               FLAG_DUPLICATE: 'a hypothesis id occurs twice in one frame',
               FLAG_STORE: 'the store is inconsistent (an offset, a permutation entry or an object id out of range)',
               FLAG_SOLVER: 'the assignment solver found no augmenting path'}
-
-
-def _boxes(b, what: str) -> np.ndarray:
-    b = np.ascontiguousarray(np.asarray(b, dtype=np.float32)).reshape(-1, 4) if np.size(b) else np.zeros((0, 4), np.float32)
-    return b
-
-
-def _ints(a, what: str, n: Optional[int] = None) -> np.ndarray:
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    a = np.asarray(a)
-    if a.size and not np.issubdtype(a.dtype, np.integer):
-        raise ValueError(f'{what}: integer values expected, got {a.dtype}')
-    a = a.astype(np.int64).reshape(-1)
-    if n is not None and a.shape[0] != n:
-        raise ValueError(f'{what}: {a.shape[0]} entries for {n} rows')
-    return a
 
 
 def mot_dist_host(box_o, box_h) -> np.ndarray:
@@ -97,14 +80,6 @@ def mot_overall(per_sequence: Sequence[Dict]) -> Dict:
             c[k] += int(r[k])
         c['dist_sum'] += float(r['dist_sum'])
     return _derived(c)
-
-
-def _frame_range(det_frame: np.ndarray, gt_frame: np.ndarray):
-    """(first frame, number of frames) of both sides together, every row counted (metrics.py:19-27); (0, 0) without rows."""
-    both = np.concatenate([det_frame, gt_frame])
-    if both.size == 0:
-        return 0, 0
-    return int(both.min()), int(both.max()) - int(both.min()) + 1
 
 
 def _check_unique(ids: np.ndarray, t: int, what: str):
@@ -312,13 +287,11 @@ class MotStore:
     """
 
     def __init__(self, sequences: Sequence[Dict]):
-        S = len(sequences)
-        self.seq = np.zeros((S, 8), np.int64)
+        self.S = len(sequences)
         self.t0: List[int] = []
         self.empty: List[bool] = []
         self.gt_ids: List[np.ndarray] = []                        # dense id -> original id, per sequence
-        gt_off, det_off, gt_id, gt_box, det_box, det_perm = [], [], [], [], [], []
-        g_base = d_base = o_base = f_base = 0
+        tab = SeqTable('MotStore', self.S)
         for s, q in enumerate(sequences):
             det_frame, gt_frame = _ints(q['det_frame'], 'det_frame'), _ints(q['gt_frame'], 'gt_frame')
             gt_track = _ints(q['gt_track'], 'gt_track', gt_frame.shape[0])
@@ -327,95 +300,38 @@ class MotStore:
                 raise ValueError(f'MotStore: sequence {s}: one box per row expected')
             t0, nf = _frame_range(det_frame, gt_frame)
             self.empty.append(det_frame.shape[0] == 0 or gt_frame.shape[0] == 0)
-            if nf >= 2 ** 31 - 1 or max(det_frame.shape[0], gt_frame.shape[0]) >= 2 ** 31 - 1:
-                raise ValueError(f'MotStore: sequence {s} is beyond int32')
-            keep = np.where(gt_track >= 0)[0]
-            go = keep[np.argsort(gt_frame[keep], kind='stable')]
-            do = np.argsort(det_frame, kind='stable')
+            tab.check(s, nf, max(det_frame.shape[0], gt_frame.shape[0]))
+            go, g_off = frame_sort(gt_frame, t0, nf, np.where(gt_track >= 0)[0])
+            do, d_off = frame_sort(det_frame, t0, nf)
             uniq, dense = np.unique(gt_track[go], return_inverse=True)
             if uniq.size and uniq.max() >= 2 ** 31:
                 raise ValueError(f'MotStore: sequence {s}: ids are int32')
-            gf, df = gt_frame[go], det_frame[do]
-            key = gf * (int(uniq.shape[0]) + 1) + dense.reshape(-1)
+            key = gt_frame[go] * (int(uniq.shape[0]) + 1) + dense.reshape(-1)
             if np.unique(key).shape[0] != key.shape[0]:
                 k, cnt = np.unique(key, return_counts=True)
                 raise ValueError(f'MotStore: sequence {s}: a GT id occurs twice in frame {int(k[cnt > 1][0] // (uniq.shape[0] + 1))}')
-            edges = np.arange(t0, t0 + nf + 1)
-            gt_off.append(np.searchsorted(gf, edges, side='left').astype(np.int32))
-            det_off.append(np.searchsorted(df, edges, side='left').astype(np.int32))
-            gt_id.append(dense.reshape(-1).astype(np.int32))
-            gt_box.append(gb[go])
-            det_box.append(db[do])
-            det_perm.append(do.astype(np.int32))
-            self.seq[s] = (g_base, go.shape[0], d_base, do.shape[0], f_base, nf, o_base, uniq.shape[0])
+            tab.add(s, go.shape[0], do.shape[0], nf, uniq.shape[0], gt_off=g_off, det_off=d_off, gt_id=dense.reshape(-1),
+                    gt_box=gb[go], det_box=db[do], det_perm=do)
             self.t0.append(t0)
             self.gt_ids.append(uniq)
-            g_base += go.shape[0]
-            d_base += do.shape[0]
-            f_base += nf + 1
-            o_base += uniq.shape[0]
-
-        def cat(parts, dtype, tail=()):
-            return np.ascontiguousarray(np.concatenate(parts).astype(dtype)) if parts else np.zeros((0,) + tail, dtype)
-        self.S = S
-        self.gt_off, self.det_off = cat(gt_off, np.int32), cat(det_off, np.int32)
-        self.gt_id, self.det_perm = cat(gt_id, np.int32), cat(det_perm, np.int32)
-        self.gt_box, self.det_box = cat(gt_box, np.float32, (4,)).reshape(-1, 4), cat(det_box, np.float32, (4,)).reshape(-1, 4)
-        self.n_gt, self.n_det, self.n_off, self.n_obj = g_base, d_base, f_base, o_base
+        self.seq = tab.seq
+        for k in ('gt_off', 'det_off', 'gt_id', 'det_perm'):
+            setattr(self, k, tab.pack(k, np.int32))
+        self.gt_box, self.det_box = tab.pack('gt_box', np.float32, (4,)), tab.pack('det_box', np.float32, (4,))
+        self.n_gt, self.n_det, self.n_off, self.n_obj = tab.totals
 
 
-def _pack_tracks(st: MotStore, tracks: Sequence, buf: torch.Tensor, who: str) -> List[bool]:
-    """The tracks of an evaluation into `buf` (int32 [n_det] on the device, every sequence at its det_base): host arrays go up in
-    one packed copy at the most (-1 for a sequence given as None), device tensors are copied on the device.  Returns, per
-    sequence, whether it was left out."""
-    if len(tracks) != st.S:
-        raise ValueError(f'{who}: {len(tracks)} track arrays for {st.S} sequences')
-    host = np.full(st.n_det, -1, np.int32)
-    on_device = []
-    left_out = []
-    host_used = False
-    for s, tr in enumerate(tracks):
-        base, n = int(st.seq[s, 2]), int(st.seq[s, 3])
-        left_out.append(tr is None)
-        if tr is None:
-            host_used |= n > 0                                  # (its slice is filled with -1)
-            continue
-        if isinstance(tr, torch.Tensor) and tr.is_cuda:
-            if tr.dtype.is_floating_point or tr.numel() != n:
-                raise ValueError(f'{who}: sequence {s}: an int tensor of {n} tracks expected')
-            on_device.append((base, n, tr))
-        else:
-            a = _ints(tr, f'{who}: sequence {s}: tracks', n)
-            if a.size and (a.max() >= 2 ** 31 or a.min() < -2 ** 31):
-                raise ValueError(f'{who}: sequence {s}: track ids are int32')
-            host[base:base + n] = a
-            host_used |= n > 0
-    if host_used:
-        buf[:st.n_det].copy_(torch.from_numpy(host), non_blocking=True)       # the one packed upload
-    for base, n, tr in on_device:
-        buf[base:base + n].copy_(tr.reshape(-1))
-    return left_out
-
-
-def _flag_message(who: str, flags, t0_of, texts: Dict[int, str]) -> str:
-    """The text of a read() that met flag words.  flags: (sequence, word) pairs; t0_of(s): the frame at which the frame count in
-    the words of sequence s starts; texts: bit -> text."""
-    return f'{who}: ' + '; '.join(f'sequence {s}' + (f', frame {t0_of(s) + (f >> 8) - 1}: ' if f >> 8 else ': ')
-                                  + ', '.join(txt for bit, txt in texts.items() if f & bit) for s, f in flags)
-
-
-def _upload_mot_store(st: MotStore, dev):
-    """The store on the device: (its arrays as tensors by name, the struct tmpnn_mot_store over them)."""
+def _attach_mot_store(ev: SequenceEvaluator, st: MotStore) -> None:
+    """The store on the device for `ev` (MotEvaluator, HotaEvaluator), with the struct tmpnn_mot_store over it."""
     names = ('seq', 'gt_off', 'det_off', 'gt_id', 'gt_box', 'det_box', 'det_perm')
-    t = {k: torch.from_numpy(getattr(st, k)).to(dev) for k in names}
-    return t, _lib.CMotStore(st.S, 0, st.n_gt, st.n_det, st.n_off, st.n_obj, *[t[k].data_ptr() or None for k in names])
+    ev._c = _lib.CMotStore(st.S, 0, st.n_gt, st.n_det, st.n_off, st.n_obj, *ev._attach(st, names))
 
 
 RECORD_WORDS = 9               # struct tmpnn_mot_record: seven int64 counts, the flag word, dist_sum (double)
 SUMMARY_WORDS = 16             # struct tmpnn_mot_summary_record: the same, then SUMMARY_KEYS, idtp, hypotheses
 
 
-class MotEvaluator:
+class MotEvaluator(SequenceEvaluator):
     """The MOT evaluation of S sequences on the device.  sequences: one dict per sequence with det_frame, det_box, gt_frame,
     gt_track, gt_box (host arrays or tensors; they are the same in every epoch -- only the tracks change).  The store is
     built on the host and uploaded once.
@@ -434,59 +350,37 @@ class MotEvaluator:
     identity figures, and then neither has the overall dict).  The count matrices take objects x detections int32 per sequence
     in the workspace: a store beyond MAX_PAIR_COUNTS entries raises ValueError (score it with mot_summary_host).
     """
+    FLAG_WORD, FLAG_TEXT = 7, _FLAG_TEXT
 
     def __init__(self, sequences: Sequence[Dict], device='cuda:0', identity: bool = False):
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError(f'MotEvaluator on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a '
-                               'cuda device, or score on the host with mot_events_host')
-        self.device = dev
+        super().__init__(device, 'score on the host with mot_events_host')
         self.identity = bool(identity)
-        self.store = st = MotStore(sequences)
+        st = MotStore(sequences)
         self._n_pair = int((st.seq[:, 7] * st.seq[:, 3]).sum())
         if self.identity and self._n_pair > MAX_PAIR_COUNTS:
             raise ValueError(f'MotEvaluator(identity=True): the identity count matrices (objects x detections per sequence) have '
                              f'{self._n_pair} entries, more than MAX_PAIR_COUNTS = {MAX_PAIR_COUNTS}: score such a set on the host '
                              'with mot_summary_host')
-        self._seq_host = np.ascontiguousarray(st.seq)
-        self._t, self._c = _upload_mot_store(st, dev)
+        _attach_mot_store(self, st)
         lib = _lib.load()
-        self._ws_bytes = int(lib.tmpnn_mot_summary_ws(st.S, st.n_obj, st.n_det, self._n_pair) if self.identity else
-                             lib.tmpnn_mot_events_ws(st.S, st.n_obj, st.n_det))
-        self._ws = torch.empty(max(self._ws_bytes, 8), dtype=torch.uint8, device=dev)
-        self._tracks = torch.empty(max(st.n_det, 1), dtype=torch.int32, device=dev)
-        self._out = torch.zeros(max(st.S, 1), SUMMARY_WORDS if self.identity else RECORD_WORDS, dtype=torch.int64, device=dev)
-        self._left_out = [False] * st.S
-        self._pending = False
+        self._workspace(lib.tmpnn_mot_summary_ws(st.S, st.n_obj, st.n_det, self._n_pair) if self.identity else
+                        lib.tmpnn_mot_events_ws(st.S, st.n_obj, st.n_det))
+        self._out = torch.zeros(max(st.S, 1), SUMMARY_WORDS if self.identity else RECORD_WORDS, dtype=torch.int64, device=self.device)
 
     def evaluate(self, tracks: Sequence) -> None:
-        left_out = _pack_tracks(self.store, tracks, self._tracks, 'MotEvaluator.evaluate')
-        _lib.call('tmpnn_mot_summary' if self.identity else 'tmpnn_mot_events', C.byref(self._c), self._seq_host.ctypes.data, self._tracks.data_ptr(), self._ws.data_ptr(),
-                  self._ws_bytes, self._out.data_ptr(), _lib.raw_stream(self.device))
-        self._left_out = left_out
-        self._pending = True
+        self._enqueue('tmpnn_mot_summary' if self.identity else 'tmpnn_mot_events', tracks, self._ws.data_ptr(), self._ws_bytes,
+                      self._out.data_ptr())
+
+    def _row(self, s, rec, fl, out) -> Dict:
+        c = {k: int(rec[s, i]) for i, k in enumerate(COUNT_KEYS)}
+        c['dist_sum'] = float(fl[s, 8])
+        if self.identity:
+            c.update({k: int(rec[s, 9 + i]) for i, k in enumerate(SUMMARY_KEYS)})
+            if rec[s, 14] >= 0:                                     # (a flagged sequence has no identity figures)
+                c['idtp'] = int(rec[s, 14])
+        return _derived(c)
 
     def read(self, check: bool = True):
-        if not self._pending:
-            raise RuntimeError('MotEvaluator.read: no evaluation has been enqueued')
-        rec = self._out.cpu().numpy()                               # (the one device -> host copy; it waits for the launch)
-        dsum = rec.view(np.float64)[:, 8]
-        bad = [(s, int(rec[s, 7])) for s in range(self.store.S) if rec[s, 7] != 0 and not self._left_out[s]]
-        if bad and check:
-            raise RuntimeError(_flag_message('MotEvaluator.read', bad, self.store.t0.__getitem__, _FLAG_TEXT))
-        per = []
-        for s in range(self.store.S):
-            if self._left_out[s]:
-                per.append(None)
-                continue
-            c = {k: int(rec[s, i]) for i, k in enumerate(COUNT_KEYS)}
-            c['dist_sum'] = float(dsum[s])
-            if self.identity:
-                c.update({k: int(rec[s, 9 + i]) for i, k in enumerate(SUMMARY_KEYS)})
-                if rec[s, 14] >= 0:                                 # (a flagged sequence has no identity figures)
-                    c['idtp'] = int(rec[s, 14])
-            c = _derived(c)
-            if not check:
-                c['flag'] = int(rec[s, 7])
-            per.append(c)
+        per = self._read(check)
         return per, mot_overall([p for p in per if p is not None])
+

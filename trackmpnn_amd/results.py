@@ -18,7 +18,6 @@ which json.dump raises TypeError for every frame that is not empty, so the refer
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import os
 from dataclasses import dataclass, field
@@ -28,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .moteval import FLAG_DUPLICATE, FLAG_STORE, _boxes, _flag_message, _ints, _pack_tracks
+from .evalstore import FLAG_DUPLICATE, FLAG_STORE, SeqTable, SequenceEvaluator, _boxes, _ints, frame_sort
 
 
 @dataclass(frozen=True)
@@ -44,7 +43,7 @@ KITTI_RESULT_RULES = ResultRules({1: 'Pedestrian', 2: 'Car', 3: 'Cyclist'}, {2: 
 BDD_RESULT_RULES = ResultRules({1: 'pedestrian', 2: 'rider', 3: 'car', 4: 'bus', 5: 'truck', 6: 'train', 7: 'motorcycle', 8: 'bicycle'}, {})
 
 COUNT_KEYS = ('kept_rows', 'kept_tracks', 'removed_rows', 'removed_tracks')
-FLAG_NEGATIVE = 16             # an id below -1 (csrc/results.hip; bits 2 and 4 are moteval's FLAG_DUPLICATE and FLAG_STORE)
+FLAG_NEGATIVE = 16             # an id below -1 (csrc/results.hip; bits 2 and 4 are evalstore's FLAG_DUPLICATE and FLAG_STORE)
 _FLAG_TEXT = {FLAG_DUPLICATE: 'a kept track id occurs twice in one frame',
               FLAG_STORE: 'the store is inconsistent (an offset, a permutation entry, a category or a table size out of range)',
               FLAG_NEGATIVE: 'a track id below -1'}
@@ -270,51 +269,37 @@ class ResultStore:
 
     def __init__(self, sequences: Sequence[Dict], rules: ResultRules):
         _check_rules(rules)
-        S = len(sequences)
-        if S > MAX_SEQUENCES:
-            raise ValueError(f'ResultStore: {S} sequences, at most {MAX_SEQUENCES} in one store')
-        self.S, self.rules = S, rules
-        self.seq = np.zeros((S, 8), np.int64)
+        tab = SeqTable('ResultStore', len(sequences), max_rows=2 ** 28, beyond='is beyond int32 (frames) or 2^28 rows',
+                       max_sequences=MAX_SEQUENCES)
+        self.S, self.rules = len(sequences), rules
         self.arrays: List[Dict] = []
         self.t_range: List = []
-        perm, fidx, off, cat, key = [], [], [], [], []
-        t_base = d_base = f_base = 0
         for s, q in enumerate(sequences):
             a = _sequence_arrays(q, rules, f'ResultStore: sequence {s}')
             frame = a['det_frame']
             n = frame.shape[0]
             t0, t1 = (int(frame.min()), int(frame.max())) if n else (0, -1)
             nf = t1 - t0 + 1
-            if nf >= 2 ** 31 - 1 or n >= 2 ** 28:
-                raise ValueError(f'ResultStore: sequence {s} is beyond int32 (frames) or 2^28 rows')
-            o = np.argsort(frame, kind='stable')
+            tab.check(s, nf, n)
+            o, off = frame_sort(frame, t0, nf)
             n_tab = 0 if n == 0 else max(256, 1 << int(2 * n - 1).bit_length())
-            perm.append(o.astype(np.int32))
-            fidx.append((frame[o] - t0).astype(np.int32))
-            off.append(np.searchsorted(frame[o], np.arange(t0, t0 + nf + 1), side='left').astype(np.int32))
-            cat.append(a['det_cat'].astype(np.int32))
-            key.append(score_keys(a['det_score']))
-            self.seq[s] = (t_base, n_tab, d_base, n, f_base, nf, 0, 0)
+            tab.add(s, n_tab, n, nf, det_perm=o, det_fidx=frame[o] - t0, det_off=off, det_cat=a['det_cat'], det_key=score_keys(a['det_score']))
             self.arrays.append(a)
             self.t_range.append((t0, t1) if n else None)
-            t_base += n_tab
-            d_base += n
-            f_base += nf + 1
-
-        def pack(parts, dtype):
-            return np.ascontiguousarray(np.concatenate(parts).astype(dtype)) if parts else np.zeros(0, dtype)
-        self.det_perm, self.det_fidx, self.det_off = pack(perm, np.int32), pack(fidx, np.int32), pack(off, np.int32)
-        self.det_cat, self.det_key = pack(cat, np.int32), pack(key, np.uint32)
+        self.seq = tab.seq
+        for k in ('det_perm', 'det_fidx', 'det_off', 'det_cat'):
+            setattr(self, k, tab.pack(k, np.int32))
+        self.det_key = tab.pack('det_key', np.uint32)
         self.n_cat = max(list(rules.names) + list(rules.min_track_score) + [0]) + 1
         thr = np.zeros(self.n_cat, np.uint32)
         for c, v in rules.min_track_score.items():
             if not np.isnan(np.float32(v)):                          # (nothing is below NaN: no threshold)
                 thr[int(c)] = score_keys(np.asarray([v], np.float32))[0]
         self.thr_key = thr
-        self.n_det, self.n_off, self.n_tab = d_base, f_base, t_base
+        self.n_tab, self.n_det, self.n_off, _ = tab.totals
 
 
-class TrackResults:
+class TrackResults(SequenceEvaluator):
     """The score filter and the result table of S sequences on the device.  sequences: the evaluators' dicts (det_frame,
     det_cat, det_score float32, det_box; optionally det_alpha, det_dim, det_loc, det_rot; GT keys are ignored) -- what
     DetectionLabeler.eval_sequences() gives; a category outside rules.names raises ValueError.  The store is built on the host
@@ -332,67 +317,41 @@ class TrackResults:
                                through json.dump.  A sequence without detections, or left out, writes no file (infer.py:38-40).
     Everything read() returns equals results_host exactly; two applies of the same tracks give the same bytes."""
 
+    STEP, FLAG_WORD, FLAG_TEXT = ('apply', 'apply'), 4, _FLAG_TEXT
+
     def __init__(self, sequences: Sequence[Dict], rules: ResultRules = KITTI_RESULT_RULES, device='cuda:0'):
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError(f'TrackResults on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a '
-                               'cuda device, or filter on the host with results_host')
-        self.device = dev
+        super().__init__(device, 'filter on the host with results_host')
         self.rules = rules
-        self.store = st = ResultStore(sequences, rules)
-        self._seq_host = np.ascontiguousarray(st.seq)
+        st = ResultStore(sequences, rules)
         names = ('seq', 'det_off', 'det_perm', 'det_fidx', 'det_cat', 'det_key', 'thr_key')
-        self._t = {k: torch.from_numpy(getattr(st, k).view(np.int32) if getattr(st, k).dtype == np.uint32 else getattr(st, k)).to(dev)
-                   for k in names}
-        self._c = _lib.CResultStore(st.S, st.n_cat, st.n_det, st.n_off, st.n_tab, *[self._t[k].data_ptr() or None for k in names])
-        self._ws_bytes = int(_lib.load().tmpnn_results_ws(st.S, st.n_det, st.n_tab))
+        self._c = _lib.CResultStore(st.S, st.n_cat, st.n_det, st.n_off, st.n_tab, *self._attach(st, names))
+        self._workspace(_lib.load().tmpnn_results_ws(st.S, st.n_det, st.n_tab))
         if self._ws_bytes == 0 and st.S:
             raise ValueError(f'TrackResults: a store of {st.S} sequences, {st.n_det} rows is beyond the workspace\'s limits')
-        self._ws = torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, device=dev)
-        self._tracks = torch.empty(max(st.n_det, 1), dtype=torch.int32, device=dev)
         # one buffer for everything read() copies: the records (int64 words as int32 pairs), the filtered ids, the order
         self._rec_ints = 2 * RECORD_WORDS * max(st.S, 1)
-        self._out = torch.zeros(self._rec_ints + 2 * st.n_det, dtype=torch.int32, device=dev)
-        self._left_out = [False] * st.S
-        self._pending = False
+        self._out = torch.zeros(self._rec_ints + 2 * st.n_det, dtype=torch.int32, device=self.device)
 
     def apply(self, tracks: Sequence) -> None:
-        left_out = _pack_tracks(self.store, tracks, self._tracks, 'TrackResults.apply')
         base = self._out.data_ptr()
-        _lib.call('tmpnn_results_apply', C.byref(self._c), self._seq_host.ctypes.data, self._tracks.data_ptr(), self._ws.data_ptr(),
-                  self._ws_bytes, base, base + 4 * self._rec_ints, base + 4 * (self._rec_ints + self.store.n_det),
-                  _lib.raw_stream(self.device))
-        self._left_out = left_out
-        self._pending = True
+        self._enqueue('tmpnn_results_apply', tracks, self._ws.data_ptr(), self._ws_bytes, base, base + 4 * self._rec_ints,
+                      base + 4 * (self._rec_ints + self.store.n_det))
 
     def filtered_tracks(self) -> List[torch.Tensor]:
-        if not self._pending:
-            raise RuntimeError('TrackResults.filtered_tracks: no apply has been enqueued')
-        return [self._out[self._rec_ints + int(b):self._rec_ints + int(b) + int(n)] for b, n in self.store.seq[:, 2:4]]
+        return self._views(self._out, self._rec_ints)
+
+    def _row(self, s, rec, fl, out) -> Dict:
+        st = self.store
+        b, n = self._det[s]
+        ids, order = self._rec_ints + b, self._rec_ints + st.n_det + b          # (its filtered ids, its part of the order)
+        r = {'tracks': out[ids:ids + n].astype(np.int64), 'order': out[order:order + int(rec[s, 0])].copy()}
+        r.update({k: int(rec[s, i]) for i, k in enumerate(COUNT_KEYS)})
+        r['t_range'] = st.t_range[s]
+        return r
 
     def read(self, check: bool = True) -> List:
-        if not self._pending:
-            raise RuntimeError('TrackResults.read: no apply has been enqueued')
-        st = self.store
-        out = self._out.cpu().numpy()                               # (the one device -> host copy; it waits for the launches)
-        rec = out[:self._rec_ints].view(np.int64).reshape(-1, RECORD_WORDS)
-        filt, order = out[self._rec_ints:self._rec_ints + st.n_det], out[self._rec_ints + st.n_det:]
-        bad = [(s, int(rec[s, 4])) for s in range(st.S) if rec[s, 4] != 0 and not self._left_out[s]]
-        if bad and check:
-            raise RuntimeError(_flag_message('TrackResults.read', bad, lambda s: st.t_range[s][0], _FLAG_TEXT))
-        per: List = []
-        for s in range(st.S):
-            if self._left_out[s]:
-                per.append(None)
-                continue
-            b, n = int(st.seq[s, 2]), int(st.seq[s, 3])
-            r = {'tracks': filt[b:b + n].astype(np.int64), 'order': order[b:b + int(rec[s, 0])].copy()}
-            r.update({k: int(rec[s, i]) for i, k in enumerate(COUNT_KEYS)})
-            r['t_range'] = st.t_range[s]
-            if not check:
-                r['flag'] = int(rec[s, 4])
-            per.append(r)
-        return per
+        return self._read(check, lambda out: out[:self._rec_ints].view(np.int64).reshape(-1, RECORD_WORDS),
+                          lambda s: self.store.t_range[s][0])
 
     def _write(self, out_dir: str, ext: str, per: Optional[List]) -> List[Optional[str]]:
         per = self.read() if per is None else per
