@@ -72,7 +72,9 @@ extern "C" {
                                still 13, for the same reason: + struct tmpnn_result_store, struct tmpnn_result_record,
                                    tmpnn_results_apply, tmpnn_results_ws (entry points added, none changed);
                                still 13, for the same reason: + struct tmpnn_evalprep_store, struct tmpnn_evalprep_record,
-                                   tmpnn_evalprep, tmpnn_evalprep_max_per_frame (entry points added, none changed) */
+                                   tmpnn_evalprep, tmpnn_evalprep_max_per_frame (entry points added, none changed);
+                               still 13, for the same reason: + struct tmpnn_att_record, tmpnn_att_hist_count (entry point
+                                   added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1068,6 +1070,41 @@ typedef struct tmpnn_val_record {
 } tmpnn_val_record;
 int tmpnn_val_f1_count(const tmpnn_dgraph* g, const uint8_t* labels, const float* scores, int tp_classifier,
                        tmpnn_val_record* rec, int32_t* log, int log_cap, tmpnn_stream stream);
+
+/* The attention monitor (attention_weights.py:84-105; csrc/atthist.hip): per head, the histograms of the attention weights the
+ * detections give to correct (`tp`) and to incorrect (`fp`) associations, ONE launch per forward and group of up to
+ * TMPNN_ATT_HIST_KMAX heads, enqueued between the model call and tmpnn_track_retire.  g: the graph the model call ran on; labels
+ * [N]: the tracker's row labels of the CURRENT row set; alpha: heads [heads][stride] float32, head k's weights in g's CSR order
+ * (position p of g->inc) at alpha + k * stride, as tmpnn_att_fwd writes them (stride >= 2E: a shorter buffer is no forward).
+ *   selection: what the reference's walk over the dense [N, N] matrices selects -- for every det row and every EDGE column with
+ *     a weight > 0.  A det with incident edges: its alpha at each of them (an alpha of exactly 0 is skipped and counted in
+ *     `zeros`; one above edges[bins] is skipped).  A det without incident edges (rowptr[d] == rowptr[d + 1]) has the uniform
+ *     dense row 1.0f / (float)N: that value once for every edge row of the graph.  The value is `tp` where the edge row's label
+ *     == 1, `fp` for every other label.
+ *   bins: edges [bins + 1] float32 ascending (device memory; numpy.histogram_bin_edges of a float32 array), bins <=
+ *     TMPNN_ATT_HIST_MAX_BINS.  The bin of v is the largest b with edges[b] <= v, the last bin closed: min(int(v * bins),
+ *     bins - 1) stepped down / up against the table, which is numpy.histogram's rule on a uniform range -- a value that sits
+ *     exactly on an edge lands where numpy puts it.
+ *   record: the header below, then int64 counts [K][2][bins] (K = all heads of the model; [k][0] = tp, [k][1] = fp).  The launch
+ *     adds the histograms of heads first_head .. first_head + heads - 1; count_forward != 0 (the first launch of a forward) also
+ *     adds the forward to the header; `zeros` is added by every launch.
+ * E, Dn and the status are read from g->meta on the device: a graph with status != 0 or without rows is no forward and leaves
+ * the record untouched; nothing here waits for the host.  N <= TMPNN_TRACK_MAX_ROWS (checked on the host; N = 0 launches
+ * nothing).  Integer LDS atomics into an int32 [heads][2][bins] histogram, plain int64 adds into the record by one thread per
+ * cell (one workgroup, stream-ordered): exact and repeatable.  The record is device memory the caller zeroes and reads. */
+#define TMPNN_ATT_HIST_KMAX 8       /* heads per launch (= the heads of one tmpnn_att_fwd call) */
+#define TMPNN_ATT_HIST_MAX_BINS 64
+#define TMPNN_ATT_HIST_HEADER 4     /* int64 words in front of the histogram */
+typedef struct tmpnn_att_record {
+    int64_t forwards;          /* forwards counted */
+    int64_t dets;              /* det rows seen, summed over the forwards */
+    int64_t isolated;          /* of them without an incident edge */
+    int64_t zeros;             /* (head, position) pairs skipped because the weight was not > 0 */
+    /* int64_t counts[K][2][bins] follows */
+} tmpnn_att_record;
+int tmpnn_att_hist_count(const tmpnn_dgraph* g, const uint8_t* labels, const float* alpha, int64_t stride, int heads,
+                         int first_head, const float* edges, int bins, tmpnn_att_record* rec, int count_forward,
+                         tmpnn_stream stream);
 
 
 /* ======================================================================================================

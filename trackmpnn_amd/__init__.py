@@ -14,7 +14,7 @@ from .loss import (CELoss, FocalLoss, classification_counts, classification_coun
 from .loops import VisTraining, infer_dataset, train_chunk, train_chunks, train_epoch, validate
 from .results import (BDD_RESULT_RULES, KITTI_RESULT_RULES, ResultRules, TrackResults, bdd_document_host, kitti_lines_host,
                       results_host, synth_result_sequence)
-from .monitor import TrainMonitor, ValMonitor, val_counts_host, val_f1_host
+from .monitor import AttentionMonitor, TrainMonitor, ValMonitor, att_hist_host, val_counts_host, val_f1_host
 from .mapeval import MapEvaluator, MapStore, map_best_host, map_host, synth_map_sequence
 from .hota import HotaEvaluator, hota_host, hota_overall, hota_sim_host
 from .evalprep import (KITTI_CAR, KITTI_PEDESTRIAN, EvalPrep, PrepRules, evalprep_frame_host, evalprep_host, evalprep_ioa_host,
@@ -34,7 +34,7 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'make_chunks', 'DetectionStore', 'ChunkSampler', 'DrawnChunks', 'draw_chunks_host', 'train_epoch', 'AllChunksSkipped',
            'OnlineTracker', 'FeatureSpec', 'online_features_host', 'MotEvaluator', 'MotStore', 'mot_events_host', 'mot_summary_host', 'mot_dist_host',
            'mot_overall', 'HotaEvaluator', 'hota_host', 'hota_overall', 'hota_sim_host', 'validate', 'MapEvaluator', 'MapStore', 'map_host', 'map_best_host', 'synth_map_sequence',
-           'ValMonitor', 'val_counts_host', 'val_f1_host', 'DetectionLabeler', 'LabelRules', 'KITTI_RULES', 'BDD_RULES',
+           'ValMonitor', 'val_counts_host', 'val_f1_host', 'AttentionMonitor', 'att_hist_host', 'DetectionLabeler', 'LabelRules', 'KITTI_RULES', 'BDD_RULES',
            'label_frame_host', 'label_detections_host', 'label_overlaps_host', 'synth_label_sequence', 'VisHead', 'vis_centres_host',
            'vis_pixels_host', 'vis_head_host', 'FramePlan', 'HostDraw', 'FrameStore', 'VisTraining',
            'FramePrep', 'OnlineVis', 'resize_coeffs', 'resize_host', 'prep_host', 'infer_dataset', 'ResultRules',

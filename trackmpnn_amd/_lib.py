@@ -365,6 +365,8 @@ _SIGNATURES = {
                                    c_void_p, c_void_p, _TRP, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
                                    c_void_p, c_void_p, c_void_p]),
     'tmpnn_val_f1_count': (c_int, [_DGP, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    'tmpnn_att_hist_count': (c_int, [_DGP, c_void_p, c_void_p, C.c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                     c_void_p]),
     'tmpnn_wide_supported': (c_int, [c_int, c_int]),
     'tmpnn_wide_prep_bytes': (c_size_t, [c_int, c_int]),
     'tmpnn_wide_prepare': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

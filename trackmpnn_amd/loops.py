@@ -232,18 +232,24 @@ def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier:
 
 def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 5, ret_win_size: int = 0,
                    use_hungarian: bool = False, device='cuda:0', tp_classifier: bool = True,
-                   stages: Optional[Dict[str, float]] = None, monitor=None):
+                   stages: Optional[Dict[str, float]] = None, monitor=None, att_monitor=None):
     """One sequence of infer.py:35-87 (model in eval mode).  Returns (y_out [ND, 2] int64 as the reference keeps it, number
     of forward calls, sum of E over them).
     monitor: a ValMonitor (monitor.py) that counts every forward call as the validation pass does (train.py:207-219, :241-253):
     one more launch behind each model call -- the first call, the calls after a re-initialisation and every update call, a
     timestep without new detections included -- before the decode, on the native driver's timesteps as on the composed ones;
-    no host read, and tracks, call count and edge count are the ones without it."""
+    no host read, and tracks, call count and edge count are the ones without it.
+    att_monitor: a monitor.AttentionMonitor that counts the attention weights of every model call INSIDE the timestep loop --
+    the calls after a re-initialisation included, the first call of the sequence not: the set attention_weights.py:172-174
+    stores -- before the decode.  One launch per call and group of 8 heads, no host read; models with heads run the composed
+    timesteps, and a model without heads raises ValueError at the first counted call.  None: nothing changes."""
     st = _Stages(stages)
     yy = y[0].detach().cpu().numpy().astype('int64')
     y_out = yy.copy()
     y_out[:, 1] = -1
     fast, finfo, h_cap = _fast_greedy(model, use_hungarian, tp_classifier, stages)
+    if att_monitor is not None:
+        fast = None                                            # (every counted call hands its attention to the monitor)
     with torch.no_grad():
         st.start()
         init = TrackGraph.initialize(X, y, 0, 'test', device)
@@ -299,10 +305,12 @@ def infer_sequence(model, X: torch.Tensor, y: torch.Tensor, cur_win_size: int = 
                 feats = tg.update(sc, X, y, t_cur, mode='test', use_hungarian=use_hungarian)
                 n_added = int(feats.shape[0])
             st.stop('graph')
-            scores, logits, h, _ = model.forward_dgraph(feats, h, tg.graph)
+            scores, logits, h, att = model.forward_dgraph(feats, h, tg.graph)
             h_cap = 0
             if monitor is not None:
                 monitor.count(tg, scores, tp_classifier)         # (before the decode deletes rows and flips the row sets)
+            if att_monitor is not None:
+                att_monitor.count(tg, att)
             sc = _pos_score(tg, scores, tp_classifier)
             st.stop('model_fwd')
             ncalls += 1
@@ -348,7 +356,8 @@ def infer_dataset(model, sequences, results, cur_win_size: int = 5, ret_win_size
 
 
 def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: int = 0, use_hungarian: bool = False,
-             tp_classifier: bool = True, map_evaluator=None, monitor=None, hota_evaluator=None, results=None, prep=None) -> Dict:
+             tp_classifier: bool = True, map_evaluator=None, monitor=None, hota_evaluator=None, results=None, prep=None,
+             att_monitor=None) -> Dict:
     """The validation pass of train.py:177-282 up to the MOTA that chooses the checkpoint (train.py:300): the model in eval
     mode for the pass (its mode is restored afterwards), infer_sequence over every sequence, all tracks handed to
     `evaluator.evaluate` and read once.  sequences: one dict per sequence with 'X' [1, ND, F] and 'y' [1, ND, 2] as
@@ -382,7 +391,10 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     returned); the evaluators are then to be built over `prep.eval_sequences()`, the ground truth the benchmark scores.  After
     `results.apply`, if any, the tracks go through `prep.apply` and every evaluator scores `prep.filtered_tracks()` -- the rows
     the KITTI benchmark scores for the class of prep.rules, handed over on the device; the result gains 'prep', the counts of
-    evalprep_host (rows_in, other_class, the four removal counts, kept) summed over the sequences that took part, read last."""
+    evalprep_host (rows_in, other_class, the four removal counts, kept) summed over the sequences that took part, read last.
+    att_monitor: a monitor.AttentionMonitor (or None: nothing more is done and nothing more returned).  It is reset, counts the
+    model calls inside the timestep loop of every sequence that runs (infer_sequence) and is read once, after the evaluators:
+    the result gains 'att_hist', the dict of AttentionMonitor.read()."""
     store = evaluator.store
     if prep is not None and [int(n) for n in prep.store.seq[:, 3]] != [int(n) for n in store.seq[:, 3]]:
         raise ValueError('validate: prep was not built over the sequences of evaluator')
@@ -398,6 +410,8 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     model.eval()
     if monitor is not None:
         monitor.reset()
+    if att_monitor is not None:
+        att_monitor.reset()
     try:
         tracks = []
         for s, q in enumerate(sequences):
@@ -408,7 +422,7 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
                 tracks.append(None)
                 continue
             y_out, ncalls, _ = infer_sequence(model, X, y, cur_win_size, ret_win_size, use_hungarian, evaluator.device,
-                                              tp_classifier, monitor=monitor)
+                                              tp_classifier, monitor=monitor, att_monitor=att_monitor)
             tracks.append(y_out[:, 1] if ncalls > 0 else None)
         if results is not None:
             results.apply(tracks)
@@ -427,6 +441,7 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
         hres = hota_evaluator.read() if hota_evaluator is not None else None
         rres = results.read() if results is not None else None
         pres = prep.read() if prep is not None else None
+        ares = att_monitor.read() if att_monitor is not None else None
     finally:
         model.train(was_training)
     out = dict(overall)
@@ -446,6 +461,8 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
         out['results'] = results_overall(rres)
     if pres is not None:
         out['prep'] = pres[1]
+    if ares is not None:
+        out['att_hist'] = ares
     return out
 
 

@@ -25,6 +25,14 @@ mean (train.py:278).  A `ValMonitor` keeps it in a device record of its own (str
 (`tmpnn_val_f1_count`: targets from the tracker's label rows, counts, the fold) that `infer_sequence(..., monitor=vm)` issues
 behind the model call on either of its paths -- the native driver included -- and `validate(..., monitor=vm)` reads once.
 `val_counts_host` / `val_f1_host` are its definition in numpy (tests/test_val_f1.py pins them against the reference).
+
+The reference's third program, attention_weights.py, produces the paper's attention figure: per head, the distribution of the
+attention weights detections give to correct and to incorrect associations.  It stores every head's dense [N, N] matrix after
+every model call inside the timestep loop and walks N^2 x K entries on the host.  An `AttentionMonitor` keeps the two histograms
+of every head in a device record (struct tmpnn_att_record + int64 [K][2][bins]): one launch per forward and group of up to 8
+heads (`tmpnn_att_hist_count`, csrc/atthist.hip) over the [2E] CSR-ordered `alpha` the attention kernels wrote, issued by
+`infer_sequence(..., att_monitor=am)` behind each of those model calls and read once by `validate(..., att_monitor=am)`;
+`att_hist_host` is its definition in numpy (tests/test_att_hist.py pins it against the reference's dense walk).
 """
 from __future__ import annotations
 
@@ -209,3 +217,167 @@ class ValMonitor:
             raise RuntimeError('ValMonitor.log: built with log_forwards = 0')
         forwards = int(self.record[1].item())
         return self._log[:min(forwards, self.log_cap)].cpu().numpy()
+
+
+ATT_HIST_KMAX = 8            # TMPNN_ATT_HIST_KMAX: heads per counting launch
+ATT_HIST_MAX_BINS = 64       # TMPNN_ATT_HIST_MAX_BINS
+ATT_HIST_HEADER = 4          # TMPNN_ATT_HIST_HEADER: forwards, dets, isolated, zeros (struct tmpnn_att_record)
+
+
+def att_hist_edges(bins: int = 25) -> np.ndarray:
+    """The float32 edge table np.histogram uses for float32 values with `bins` and range (0, 1): [bins + 1]."""
+    return np.histogram_bin_edges(np.zeros(0, np.float32), int(bins), (0.0, 1.0)).astype(np.float32)
+
+
+def att_csr_host(is_edge, src, dst):
+    """(det rows ascending, rowptr [Dn + 1], inc [2E]) of a graph in row form (src / dst [N]: the ROWS of an edge row's earlier /
+    later det): per det its incident edge rows ascending, the sign bit set where the det is the edge's LATER end -- the CSR
+    order of tmpnn_dgraph.inc, i.e. the order of a head's `alpha`."""
+    is_edge = np.asarray(is_edge).reshape(-1) != 0
+    src, dst = np.asarray(src).reshape(-1).astype(np.int64), np.asarray(dst).reshape(-1).astype(np.int64)
+    er = np.flatnonzero(is_edge)
+    dets = np.flatnonzero(~is_edge)
+    end = np.concatenate([src[er], dst[er]])                      # the det of every (edge, side)
+    val = np.concatenate([er, er | 0x80000000])
+    order = np.lexsort((np.concatenate([er, er]), end))
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(np.searchsorted(dets, end), minlength=dets.size))]).astype(np.int64)
+    return dets, rowptr, val[order].astype(np.int64)
+
+
+def att_hist_host(is_edge, labels, alphas, N: Optional[int] = None, bins: int = 25, rowptr=None, inc=None, src=None, dst=None) -> Dict:
+    """The attention histograms of ONE forward call as the reference's head study counts them (attention_weights.py:84-105), in
+    numpy, on the CSR form.
+
+    is_edge [N], labels [N]; the graph either as rowptr [Dn + 1] / inc [2E] (edge row | sign bit, as tmpnn_dgraph) or in row
+    form src / dst [N] (att_csr_host derives the CSR); alphas [K, 2E] float32: head k's weight at CSR position p, i.e. what
+    the det that owns p gives the edge row inc[p]; N: the call's row count (default is_edge.size).
+
+    Selection: the reference looks at every det ROW of a head's dense [N, N] matrix and every EDGE column whose entry is > 0.
+    In eval mode a det with incident edges holds its softmax over them and exact zeros elsewhere, so it contributes its alphas
+    -- one that underflowed to exactly 0 is skipped by the `> 0` test ('zeros' counts them).  A det with NO incident edge
+    holds the uniform value float32(1) / float32(N) in every column (an all-masked softmax): it contributes that value once
+    for every edge row of the graph.  A value is `tp` where the edge row's label == 1 and `fp` for every other label.  Each
+    list is binned with np.histogram(values.astype(np.float32), bins, (0.0, 1.0)): half-open bins, the last one closed.
+
+    Returns counts int64 [K, 2, bins] ([k, 0] = tp, [k, 1] = fp), edges float32 [bins + 1], forwards (1 if the graph has
+    rows), dets, isolated, zeros."""
+    is_edge = np.asarray(is_edge).reshape(-1) != 0
+    lab = np.asarray(labels).reshape(-1)
+    N = int(is_edge.size if N is None else N)
+    if rowptr is None:
+        _, rowptr, inc = att_csr_host(is_edge, src, dst)
+    rowptr, inc = np.asarray(rowptr).reshape(-1).astype(np.int64), np.asarray(inc).reshape(-1).astype(np.int64)
+    a = np.asarray(alphas, dtype=np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    K, P = a.shape[0], int(inc.size)
+    Dn, E = int(rowptr.size) - 1, P // 2
+    if a.shape[1] != P or lab.size != is_edge.size or P != 2 * int(is_edge.sum()) or Dn != int((~is_edge).sum()):
+        raise ValueError(f'att_hist_host: alphas {a.shape}, {P} CSR positions, {lab.size} labels, {is_edge.size} rows')
+    edge_tp = lab[inc & 0x7FFFFFFF] == 1                            # per CSR position: the edge row's label is 1
+    n_iso = int((rowptr[1:] == rowptr[:-1]).sum())
+    edge_lab = lab[is_edge] == 1
+    uniform = np.float32(1.0) / np.float32(max(N, 1))
+    counts = np.zeros((K, 2, int(bins)), np.int64)
+    zeros = 0
+    for k in range(K):
+        live = a[k] > 0
+        zeros += int((~live).sum())
+        for side, sel in ((0, edge_tp), (1, ~edge_tp)):
+            vals = a[k][live & sel]
+            iso = np.full(n_iso * int((edge_lab if side == 0 else ~edge_lab).sum()), uniform, np.float32)
+            counts[k, side] = np.histogram(np.concatenate([vals, iso]).astype(np.float32), int(bins), (0.0, 1.0))[0]
+    return dict(counts=counts, edges=att_hist_edges(bins), forwards=int(E + Dn > 0), dets=Dn, isolated=n_iso, zeros=zeros)
+
+
+class AttentionMonitor:
+    """The head study's histograms in device memory (module docstring).
+
+    record  int64 [4 + K * 2 * bins] device tensor: struct tmpnn_att_record (forwards, dets, isolated, zeros), then the counts
+            [K][2][bins] ([k][0] = tp: the edge's label is 1, [k][1] = fp)
+    edges   float32 [bins + 1] device tensor: np.histogram's edge table for float32 values, bins, range (0, 1)
+    feature_set: which feature group's heads are counted (attention_weights.py:60 stores group 0)."""
+
+    def __init__(self, device='cuda:0', nattheads: int = 0, bins: int = 25, feature_set: int = 0):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError(f'AttentionMonitor on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only '
+                               '(no CPU or torch fallback exists)')
+        if int(nattheads) < 1:
+            raise ValueError(f'AttentionMonitor: nattheads={nattheads}: a model without attention heads has no weights to count')
+        if not 1 <= int(bins) <= ATT_HIST_MAX_BINS:
+            raise ValueError(f'AttentionMonitor: bins={bins} (1 .. {ATT_HIST_MAX_BINS})')
+        if int(feature_set) < 0:
+            raise ValueError(f'AttentionMonitor: feature_set={feature_set}')
+        self.device = dev
+        self.K, self.bins, self.feature_set = int(nattheads), int(bins), int(feature_set)
+        self.edges_host = att_hist_edges(self.bins)
+        self.edges = torch.from_numpy(self.edges_host).to(dev)
+        self.record = torch.zeros(ATT_HIST_HEADER + self.K * 2 * self.bins, dtype=torch.int64, device=dev)
+
+    def reset(self) -> None:
+        """Zero the record.  No host read."""
+        self.record.zero_()
+
+    @staticmethod
+    def _one_buffer(grp: List[torch.Tensor]) -> Optional[Tuple[int, int]]:
+        """(address, stride in floats) where the heads' alphas are rows of ONE buffer (as the attention stage returns them:
+        slices alpha[k, :2E] of a [Kg, max(2E, 1)] tensor), else None."""
+        a0 = grp[0]
+        n = int(a0.numel())
+        if n == 0:                                   # (no edges: an empty tensor has no address; count() hands over zeros)
+            return None
+        if any(a.dtype != torch.float32 or a.dim() != 1 or int(a.numel()) != n or (n > 1 and a.stride(0) != 1) for a in grp):
+            return None
+        if len(grp) == 1:
+            return a0.data_ptr(), max(n, 1)
+        step = grp[1].data_ptr() - a0.data_ptr()
+        if step < 4 * max(n, 1) or step % 4:
+            return None
+        st = a0.untyped_storage().data_ptr()
+        if any(a.untyped_storage().data_ptr() != st or a.data_ptr() - a0.data_ptr() != k * step for k, a in enumerate(grp)):
+            return None
+        return a0.data_ptr(), step // 4
+
+    def count(self, tg, attention) -> None:
+        """The launches of ONE forward: `tg` the tracking.TrackGraph the model call just ran on (BEFORE its decode: the label
+        rows are the current row set's), `attention` the call's fourth output -- per feature group a list of SparseAttention.
+        One launch per group of up to 8 heads (the first one counts the forward).  No host read."""
+        if attention is None or self.feature_set >= len(attention) or attention[self.feature_set] is None:
+            raise ValueError(f'AttentionMonitor.count: the call returned no attention for feature group {self.feature_set} '
+                             f'(a model without heads?); the monitor was built for {self.K} heads')
+        heads = attention[self.feature_set]
+        if len(heads) != self.K:
+            raise ValueError(f'AttentionMonitor.count: {len(heads)} heads handed in, the monitor was built for {self.K}')
+        N = int(tg.N)
+        if N == 0:
+            return
+        alphas = [h.alpha.detach() for h in heads]
+        n = int(alphas[0].numel())
+        st = _lib.raw_stream(self.device)
+        for k0 in range(0, self.K, ATT_HIST_KMAX):
+            grp = alphas[k0:k0 + ATT_HIST_KMAX]
+            one = self._one_buffer(grp)
+            if one is None:
+                if any(int(a.numel()) != n for a in grp):
+                    raise ValueError('AttentionMonitor.count: the heads hold different numbers of weights')
+                buf = torch.zeros((len(grp), max(n, 1)), dtype=torch.float32, device=self.device)
+                if n:
+                    torch.stack([a.reshape(-1).float() for a in grp], out=buf)
+                one = (buf.data_ptr(), max(n, 1))
+            _lib.call('tmpnn_att_hist_count', tg.graph.cref(), tg.rows['labels'].data_ptr(), one[0], one[1], len(grp), k0,
+                      self.edges.data_ptr(), self.bins, self.record.data_ptr(), 1 if k0 == 0 else 0, st)
+
+    def read(self) -> Dict:
+        """The one device -> host copy: 'counts' int64 [K, 2, bins] (tp = 0, fp = 1), 'edges' float32 [bins + 1], 'forwards',
+        and the header's 'dets', 'isolated', 'zeros'."""
+        raw = self.record.cpu().numpy()
+        return dict(counts=raw[ATT_HIST_HEADER:].reshape(self.K, 2, self.bins).copy(), edges=self.edges_host.copy(),
+                    forwards=int(raw[0]), dets=int(raw[1]), isolated=int(raw[2]), zeros=int(raw[3]))
+
+    def normalized(self, result: Optional[Dict] = None) -> np.ndarray:
+        """float64 [K, 2, bins]: every histogram divided by its total, as the figure plots it (attention_weights.py:99-105:
+        weights = 1 / len); a histogram without values is NaN.  result: a dict of read() (default: read now)."""
+        counts = (self.read() if result is None else result)['counts'].astype(np.float64)
+        total = counts.sum(-1, keepdims=True)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.where(total > 0, counts / total, np.nan)
