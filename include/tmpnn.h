@@ -74,7 +74,9 @@ extern "C" {
                                still 13, for the same reason: + struct tmpnn_evalprep_store, struct tmpnn_evalprep_record,
                                    tmpnn_evalprep, tmpnn_evalprep_max_per_frame (entry points added, none changed);
                                still 13, for the same reason: + struct tmpnn_att_record, tmpnn_att_hist_count (entry point
-                                   added, none changed) */
+                                   added, none changed);
+                               still 13, for the same reason: + struct tmpnn_seq_features_args, tmpnn_seq_features (entry
+                                   point added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -743,6 +745,56 @@ typedef struct tmpnn_chunk_vis {
     int32_t* o_track;           /* [n_max] */
 } tmpnn_chunk_vis;
 int tmpnn_chunk_draw_vis(const tmpnn_chunk_draw* d, const tmpnn_chunk_vis* v, tmpnn_stream stream);
+
+/* Whole-sequence features from the same store (csrc/seqfeat.hip; trackmpnn_amd.seqfeat.SequenceFeatures; host definition:
+ * sequence_features_host): the reference's `val` / `test` sample, every detection of a sequence in the store's order, no
+ * transforms.  K listed sequences are packed one behind the other: listed sequence k = seqs[k] owns the packed rows
+ * offsets[k] .. offsets[k + 1], which are the store's rows first[seq_base[s]] .. first[seq_base[s + 1]] in order.  Packed row i
+ * of store row r and frame t = frame[r]:  X[i][0 .. Fs) = stat[r][0] (the plain box), X[i][Fs .. Fs + 2) = table[t mod fr_range]
+ * when F = Fs + 2, y[i] = (t, track[r]); columns F .. ldx of X are not written (the 'vis' group: tmpnn_vis_head_fwd fills them).
+ * With box != NULL the same launch writes the visual head's arguments: o_box = box[r][0], o_im_hw = seq_hw[s], o_map_of =
+ * t mod frames_per_batch (the row's image inside a batch of frames_per_batch frames aligned to its multiples).
+ *   tmpnn_seq_features: ONE launch, a workgroup per 256 packed rows; nothing is computed, every value is selected.  X is stored
+ *     in 4-byte words, a wave 64 consecutive ones: a row of 8, 10, 13, 15, 138 or 143 floats is in general not 16-byte aligned
+ *     and a sequence's packed base falls at any row, so no wider store is used for it; y, o_box and o_im_hw are whole rows of 16,
+ *     16 and 8 bytes.  n_rows = 0 launches nothing.
+ * Every entry the kernel indexes by is checked against the store's totals first: the listed sequence, its frame range, its row
+ * range and that this range has the size the packed offsets give it, the row's frame and that `first` brackets the row at
+ * that frame.  A row that fails is not written and ORs a bit into flag[0] (1: the sequence list or the packed offsets, 2:
+ * seq_base / first, 4: frame): reachable only if the device tables were overwritten, never an out-of-range access. */
+#define TMPNN_SF_FLAG_LIST 1
+#define TMPNN_SF_FLAG_RANGE 2
+#define TMPNN_SF_FLAG_FRAME 4
+typedef struct tmpnn_seq_features_args {
+    int32_t K;                  /* listed sequences, >= 1 */
+    int32_t nseq;               /* sequences of the store */
+    int32_t F;                  /* columns written: Fs, or Fs + 2 with the temporal pair */
+    int32_t Fs;                 /* columns of the static row */
+    int32_t ldx;                /* row stride of X in floats, >= F */
+    int32_t fr_range;           /* rows of table */
+    int32_t frames_per_batch;   /* >= 1 (read with box only) */
+    int32_t reserved;           /* 0 */
+    int64_t ndets;              /* detections of the store */
+    int64_t nframes;            /* frames of the store = seq_base[nseq] */
+    int64_t n_rows;             /* packed rows = offsets[K], < 2^31 */
+    const int32_t* seqs;        /* [K] */
+    const int64_t* offsets;     /* [K + 1] */
+    const int32_t* seq_base;    /* [nseq + 1] */
+    const int32_t* first;       /* [nframes + 1] */
+    const int32_t* frame;       /* [ndets]: frame of every detection within its sequence */
+    const int32_t* track;       /* [ndets] */
+    const float* stat;          /* [ndets][2][Fs] */
+    const float* table;         /* [fr_range][2] (F = Fs + 2) */
+    const float* box;           /* [ndets][2][4], 16-byte aligned; NULL: a store without 'vis' */
+    const float* seq_hw;        /* [nseq][2], 8-byte aligned (with box) */
+    float* X;                   /* [n_rows][ldx] */
+    int64_t* y;                 /* [n_rows][2], 16-byte aligned */
+    float* o_box;               /* [n_rows][4], 16-byte aligned (with box) */
+    float* o_im_hw;             /* [n_rows][2], 8-byte aligned (with box) */
+    int32_t* o_map_of;          /* [n_rows] (with box) */
+    int32_t* flag;              /* [1]: ORed into, never cleared here */
+} tmpnn_seq_features_args;
+int tmpnn_seq_features(const tmpnn_seq_features_args* d, tmpnn_stream stream);
 
 /* The CNN's input for the frames of a draw (csrc/frames.hip; trackmpnn_amd.frames.FrameStore; host definition: frames_host).
  * The store keeps every frame of every sequence, already resized to the CNN's input size H x W, as planar uint8 [3][H][W]; frame

@@ -11,7 +11,9 @@ from .labeling import (BDD_RULES, KITTI_RULES, DetectionLabeler, LabelRules, lab
                        label_overlaps_host, synth_label_sequence)
 from .loss import (CELoss, FocalLoss, classification_counts, classification_counts_windows, create_targets,
                    train_losses_windows)
-from .loops import VisTraining, infer_dataset, train_chunk, train_chunks, train_epoch, validate
+from .loops import (VisInference, VisTraining, infer_dataset, infer_store, train_chunk, train_chunks, train_epoch, validate,
+                    validate_store)
+from .seqfeat import SequenceFeatures, SequenceSample, listed_features_host, sequence_features_host, sequence_vis_host
 from .results import (BDD_RESULT_RULES, KITTI_RESULT_RULES, ResultRules, TrackResults, bdd_document_host, kitti_lines_host,
                       results_host, synth_result_sequence)
 from .monitor import AttentionMonitor, TrainMonitor, ValMonitor, att_hist_host, val_counts_host, val_f1_host
@@ -40,4 +42,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'FramePrep', 'OnlineVis', 'resize_coeffs', 'resize_host', 'prep_host', 'infer_dataset', 'ResultRules',
            'KITTI_RESULT_RULES', 'BDD_RESULT_RULES', 'TrackResults', 'results_host', 'kitti_lines_host', 'bdd_document_host',
            'synth_result_sequence', 'EvalPrep', 'PrepRules', 'KITTI_CAR', 'KITTI_PEDESTRIAN', 'evalprep_frame_host', 'evalprep_host',
-           'evalprep_ioa_host', 'synth_prep_sequence']
+           'evalprep_ioa_host', 'synth_prep_sequence', 'SequenceFeatures', 'SequenceSample', 'sequence_features_host',
+           'sequence_vis_host', 'listed_features_host', 'VisInference', 'validate_store', 'infer_store']

@@ -120,6 +120,14 @@ class CChunkDrawVis(C.Structure):
     _fields_ = [(f, c_void_p) for f in ('box', 'seq_hw', 'slot', 'o_box', 'o_im_hw', 'o_map_of', 'o_track')]
 
 
+class CSeqFeatures(C.Structure):
+    """struct tmpnn_seq_features_args (include/tmpnn.h): the whole-sequence features of listed sequences from the detection store."""
+    _fields_ = ([(f, C.c_int32) for f in ('K', 'nseq', 'F', 'Fs', 'ldx', 'fr_range', 'frames_per_batch', 'reserved')]
+                + [(f, C.c_int64) for f in ('ndets', 'nframes', 'n_rows')]
+                + [(f, c_void_p) for f in ('seqs', 'offsets', 'seq_base', 'first', 'frame', 'track', 'stat', 'table', 'box', 'seq_hw',
+                                           'X', 'y', 'o_box', 'o_im_hw', 'o_map_of', 'flag')])
+
+
 class CFramesGather(C.Structure):
     """struct tmpnn_frames_gather_args (include/tmpnn.h): the CNN's input images of a frame plan from the resident uint8 frames."""
     _fields_ = ([(f, C.c_int32) for f in ('T', 'H', 'W', 'nseq')] + [('nframes', C.c_int64)]
@@ -316,6 +324,7 @@ _SIGNATURES = {
     'tmpnn_chunk_draw_count': (c_int, [_CDP, c_void_p]),
     'tmpnn_chunk_draw_fill': (c_int, [_CDP, c_void_p]),
     'tmpnn_chunk_draw_vis': (c_int, [_CDP, _CVP, c_void_p]),
+    'tmpnn_seq_features': (c_int, [C.POINTER(CSeqFeatures), c_void_p]),
     'tmpnn_frames_gather': (c_int, [_FGP, c_void_p]),
     'tmpnn_frames_resize_ws': (c_size_t, [c_int] * 5),
     'tmpnn_frames_resize': (c_int, [_FRP, c_void_p]),

@@ -13,6 +13,8 @@
     validate        reference/train.py:177-282  the validation pass: infer_sequence over every sequence, then the CLEAR-MOT
                                                 counts of all tracks in one launch (moteval.MotEvaluator) and one host read;
                                                 with a monitor.ValMonitor the F1 of every forward call (train.py:278)
+    validate_store, infer_store                 validate / infer_dataset over a seqfeat.SequenceFeatures: the sequences' features
+                                                made on the device from the DetectionStore (the reference's val / test samples)
 
 Same order of operations, same arguments' meaning and the same results as the reference's drivers (which cannot be imported:
 they parse the command line at import) -- but the graph, the hidden state, the losses' inputs and the tracks stay
@@ -464,6 +466,44 @@ def validate(model, sequences, evaluator, cur_win_size: int = 5, ret_win_size: i
     if ares is not None:
         out['att_hist'] = ares
     return out
+
+
+@dataclass
+class VisInference:
+    """What validate_store / infer_store need for a store with 'vis' features (the counterpart of VisTraining without an
+    optimizer: the embedding net is only evaluated)."""
+    head: Any               # vishead.VisHead: the CNN's input size, down ratio and the 128 'vis' statistics
+    frames: Any             # frames.FrameStore: the resized frames of the store's sequences, in the store's order
+    embed_net: Any          # the embedding CNN: images [T, 3, H, W] -> maps [T, 128, Hm, Wm]
+    frames_per_batch: int = 8
+
+
+def _store_sequences(what: str, sf, vis: Optional[VisInference]) -> list:
+    """The dicts of every sequence of sf's store: sf.build, with 'vis' sf.attach_vis, then sf.check()."""
+    if sf.store.vis and vis is None:
+        raise ValueError(f"{what}: the store holds 'vis' features: pass vis=VisInference(head, frames, embed_net)")
+    if vis is not None and not sf.store.vis:
+        raise ValueError(f"{what}: vis= was given, but the store was built without 'vis' features")
+    sequences = sf.build(frames_per_batch=8 if vis is None else vis.frames_per_batch)
+    if vis is not None:
+        sf.attach_vis(vis.head, vis.frames, vis.embed_net, vis.frames_per_batch)
+    sf.check()                  # (no extra stall: the first thing infer_sequence does is read y on the host)
+    return sequences
+
+
+def validate_store(model, sf, evaluator, vis: Optional[VisInference] = None, **kw) -> Dict:
+    """`validate` over every sequence of a seqfeat.SequenceFeatures: sf.build() (one launch), for a store with 'vis' features
+    sf.attach_vis(vis.head, vis.frames, vis.embed_net, vis.frames_per_batch) -- after every epoch the embedding net has moved
+    and the visual columns are made anew --, then validate(model, sequences, evaluator, **kw).  `evaluator` (and whatever else
+    **kw hands to validate) is built over the store's sequences in the store's order.  A 'vis' store without vis= raises, and
+    vis= without a 'vis' store raises, as train_epoch does."""
+    return validate(model, _store_sequences('validate_store', sf, vis), evaluator, **kw)
+
+
+def infer_store(model, sf, results, vis: Optional[VisInference] = None, **kw) -> list:
+    """`infer_dataset` over every sequence of a seqfeat.SequenceFeatures: the features as validate_store makes them, then
+    infer_dataset(model, sequences, results, **kw)."""
+    return infer_dataset(model, _store_sequences('infer_store', sf, vis), results, **kw)
 
 
 def _fast_greedy(model, use_hungarian: bool, tp_classifier: bool, stages):

@@ -329,6 +329,11 @@ class VisHead:
             raise RuntimeError('VisHead: no call has been made')
         return self._last.logits
 
+    def release(self) -> None:
+        """Forget the last call: its buffers (the maps among them) are kept for last_logits() and record() until the next call
+        or this.  A loop over many batches of maps calls it to hold one batch at a time."""
+        self._last = None
+
     def record(self) -> dict:
         """The counts of the last call (the one device -> host read): per chunk `labelled` (rows with track >= 0), `clamped` (rows
         whose centre lay outside the map) and `rows`; per row `pix` = (map_of * Hm + cy) * Wm + cx, `cy`, `cx` and `clamped`.
