@@ -76,7 +76,10 @@ extern "C" {
                                still 13, for the same reason: + struct tmpnn_att_record, tmpnn_att_hist_count (entry point
                                    added, none changed);
                                still 13, for the same reason: + struct tmpnn_seq_features_args, tmpnn_seq_features (entry
-                                   point added, none changed) */
+                                   point added, none changed);
+                               still 13, for the same reason: + struct tmpnn_embed_loss, tmpnn_embed_loss_ws,
+                                   tmpnn_embed_loss_fwd, tmpnn_embed_loss_bwd, tmpnn_vis_head_scatter, struct
+                                   tmpnn_embed_record, tmpnn_train_embed_fold (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -577,6 +580,16 @@ int tmpnn_cls_counts_win(const tmpnn_graph* g, const tmpnn_loss_windows* w, cons
                          int tp_classifier, int32_t* counts, tmpnn_stream stream);
 int tmpnn_train_record_fold(const int32_t* counts, int C, int W, const float* loss_c, const float* loss_f, int B,
                             tmpnn_train_record* rec, tmpnn_stream stream);
+/* The embedding network's loss of the same chunks (train.py:157-163 logs its epoch mean): ONE launch that adds loss_d[kept[k]],
+ * k < n_kept (kept NULL: loss_d[k]), as fp32 values summed in fp64 in a fixed order, and the number of chunks added, to a record
+ * of its own.  loss_d [n_loss]; an index outside [0, n_loss) is skipped and counted in `skipped`. */
+typedef struct tmpnn_embed_record {
+    double sum_loss_d;   /* over the chunks */
+    int64_t chunks;
+    int64_t skipped;
+} tmpnn_embed_record;
+int tmpnn_train_embed_fold(const float* loss_d, int n_loss, const int64_t* kept, int n_kept, tmpnn_embed_record* rec,
+                           tmpnn_stream stream);
 
 /* The optimizer step (train.py:135 `optimizer_trk.step()` of the `optim.Adam(model.parameters(), lr, weight_decay)` of
  * train.py:329; the learning rate is whatever the StepLR of train.py:330 last set) and the gradient statistics of
@@ -1565,6 +1578,51 @@ int tmpnn_vis_head_fwd(const tmpnn_vis_head* a, tmpnn_stream stream);
 /* After tmpnn_vis_head_fwd on the same stream, with the same struct: a memset of dmaps [T][128][Hm][Wm] and one launch (one wave
  * per detection; a pairwise scan of the saved pixels finds the sharers).  g [B]: the gradient arriving at loss. */
 int tmpnn_vis_head_bwd(const tmpnn_vis_head* a, const float* g, float* dmaps, tmpnn_stream stream);
+/* After tmpnn_vis_head_fwd on the same stream, with the same struct: a memset of dmaps and one launch that adds a gradient handed
+ * in, d_logits [D][128], at the pixels the forward saved (the backward of the gather alone, for a loss computed outside over
+ * `logits`: tmpnn_embed_loss_*).  Rows with a label in a chunk are added; rows that share a pixel are summed in ascending row
+ * order by the lowest of them, which stores once (the ownership scan of tmpnn_vis_head_bwd): no atomics. */
+int tmpnn_vis_head_scatter(const tmpnn_vis_head* a, const float* d_logits, float* dmaps, tmpnn_stream stream);
+
+/* ======================================================================================================
+ * The embedding loss (csrc/embedloss.hip; host definition: trackmpnn_amd.embedloss.embedding_loss_host): the reference's
+ * discriminative pull-push loss over embedding rows (models/loss.py:118-159), per chunk, with its gradient wrt the rows.
+ *   cluster  the rows of chunk b (offsets[b] <= i < offsets[b + 1]) with track[i] >= 0 that share one track id (compared as
+ *            integers); C clusters, n_c rows, mu_c their mean (rows added in ascending order)
+ *   terms    var = (1 / C) sum_c (1 / n_c) sum_{i in c} relu(|x_i - mu_c| - delta_var)^2                      (0 when C = 0)
+ *            dist = (1 / (C (C - 1))) sum_{c != c'} relu(delta_dist - |mu_c - mu_c'|)^2, ordered pairs        (0 when C <= 1)
+ *   loss[b]  var + dist
+ *   d_features[k] = g[b] (u_k - (1 / n_c) sum_{i in c} u_i + v_c / n_c) for a row k of cluster c, 0 for every other row, with
+ *            u_i = 2 relu(d_i - delta_var) (x_i - mu_c) / (d_i C n_c), d_i = |x_i - mu_c|, and
+ *            v_c = -(4 / (C (C - 1))) sum_{c' != c} relu(delta_dist - m) (mu_c - mu_c') / m, m = |mu_c - mu_c'|;
+ *            where a norm is exactly 0 its direction term is 0
+ * No atomics: every sum has one owner and a fixed order, so the results are bitwise reproducible.  No limit on the rows or the
+ * clusters of a chunk (a wave per row scans its chunk's ids 64 at a time).  Chunk boundaries that are not non-decreasing within
+ * [0, D] are clamped and counted, and a row then belongs to the first chunk that holds it: nothing is read or written outside
+ * the arrays, and the caller raises when it reads the counts.
+ * ====================================================================================================== */
+typedef struct tmpnn_embed_loss {
+    int64_t D;                  /* rows, <= 131 072 */
+    int32_t B;                  /* chunks (>= 1) */
+    int32_t W;                  /* columns of a row, 1 .. 1024 */
+    int32_t ld;                 /* row stride of features and of d_features in floats, >= W */
+    float delta_var, delta_dist;
+    int32_t reserved;
+    const float* features;      /* [D][ld] */
+    const int32_t* track;       /* [D], -1: no label */
+    const int32_t* offsets;     /* [B + 1], or NULL with B = 1: one chunk of all rows */
+    void* ws;                   /* tmpnn_embed_loss_ws(D, W) bytes, 16-byte aligned; the forward's results for the backward */
+    size_t ws_bytes;
+    float* loss;                /* [B] */
+    float* terms;               /* [B][2]: var, dist */
+    int32_t* count;             /* [B][4]: labelled rows, clusters, bad boundaries, rows */
+} tmpnn_embed_loss;
+size_t tmpnn_embed_loss_ws(int64_t D, int W);
+/* Four launches (the rows' chunks; leaders and means; distances and leader pairs; one wave per chunk): loss, terms, count. */
+int tmpnn_embed_loss_fwd(const tmpnn_embed_loss* a, tmpnn_stream stream);
+/* After tmpnn_embed_loss_fwd on the same stream, with the same struct: two launches.  g [B]: the gradient arriving at loss;
+ * columns 0 .. W - 1 of every row of d_features [D][ld] are written. */
+int tmpnn_embed_loss_bwd(const tmpnn_embed_loss* a, const float* g, float* d_features, tmpnn_stream stream);
 
 /* ======================================================================================================
  * Wide cells (H = 128 / 256, diff messages; BASELINE.json C5) as LDS-tiled GEMMs on bf16x6 split products

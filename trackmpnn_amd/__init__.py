@@ -27,6 +27,7 @@ from .optim import BucketAdam
 from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
 from .vishead import VisHead, vis_centres_host, vis_head_host, vis_pixels_host
+from .embedloss import EmbeddingLoss, embedding_loss_host
 from .train_batch import AllChunksSkipped, LossWindows, TrainBatch, build_train_batch, build_train_batch_device
 
 __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'create_targets', 'CELoss', 'FocalLoss', 'FrameGraph', 'CallPlan', 'graph_from_adjacency', 'graph_from_edges',
@@ -43,4 +44,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'KITTI_RESULT_RULES', 'BDD_RESULT_RULES', 'TrackResults', 'results_host', 'kitti_lines_host', 'bdd_document_host',
            'synth_result_sequence', 'EvalPrep', 'PrepRules', 'KITTI_CAR', 'KITTI_PEDESTRIAN', 'evalprep_frame_host', 'evalprep_host',
            'evalprep_ioa_host', 'synth_prep_sequence', 'SequenceFeatures', 'SequenceSample', 'sequence_features_host',
-           'sequence_vis_host', 'listed_features_host', 'VisInference', 'validate_store', 'infer_store']
+           'sequence_vis_host', 'listed_features_host', 'VisInference', 'validate_store', 'infer_store', 'EmbeddingLoss',
+           'embedding_loss_host']

@@ -192,6 +192,13 @@ class CVisHead(C.Structure):
                                            'stat', 'nll', 'pix', 'flag', 'chunk_of', 'key', 'loss', 'count')])
 
 
+class CEmbedLoss(C.Structure):
+    """struct tmpnn_embed_loss (include/tmpnn.h): one call of the embedding (pull-push) loss over D rows in B chunks."""
+    _fields_ = ([('D', C.c_int64)] + [(f, C.c_int32) for f in ('B', 'W', 'ld')] + [('delta_var', c_float), ('delta_dist', c_float),
+                ('reserved', C.c_int32)] + [(f, c_void_p) for f in ('features', 'track', 'offsets', 'ws')]
+                + [('ws_bytes', c_size_t)] + [(f, c_void_p) for f in ('loss', 'terms', 'count')])
+
+
 _DGP = C.POINTER(CDGraph)
 _MPP = C.POINTER(CMpParams)
 _TRP = C.POINTER(CTrackRows)
@@ -353,6 +360,11 @@ _SIGNATURES = {
     'tmpnn_label_compact': (c_int, [_LSP, _LOP, c_void_p]),
     'tmpnn_vis_head_fwd': (c_int, [_VHP, c_void_p]),
     'tmpnn_vis_head_bwd': (c_int, [_VHP, c_void_p, c_void_p, c_void_p]),
+    'tmpnn_vis_head_scatter': (c_int, [_VHP, c_void_p, c_void_p, c_void_p]),
+    'tmpnn_embed_loss_ws': (c_size_t, [C.c_int64, c_int]),
+    'tmpnn_embed_loss_fwd': (c_int, [C.POINTER(CEmbedLoss), c_void_p]),
+    'tmpnn_embed_loss_bwd': (c_int, [C.POINTER(CEmbedLoss), c_void_p, c_void_p, c_void_p]),
+    'tmpnn_train_embed_fold': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

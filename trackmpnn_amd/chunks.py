@@ -61,6 +61,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .embedloss import embedding_loss_host
 from .train_batch import TB_MAX_DETS, AllChunksSkipped, _to_device, build_train_batch_device
 from .vishead import VIS_COLS, vis_head_host
 
@@ -280,15 +281,21 @@ class HostDraw:
     track: Optional[np.ndarray] = None      # int32 [ND] = y[:, 1]
     plan: Optional[FramePlan] = None
 
-    def attach_vis(self, maps, mean, std, input_hw, down_ratio) -> np.ndarray:
+    def attach_vis(self, maps, mean, std, input_hw, down_ratio, embed_loss='identity') -> np.ndarray:
         """The host definition of DrawnChunks.attach_vis: vis_head_host on the drawn rows, its rows written into the last 128
-        columns of X (in float32); returns the per-chunk identity loss [B] in the dtype of `maps`."""
+        columns of X (in float32); returns the per-chunk identity loss [B] in the dtype of `maps`.  embed_loss='embedding' (or
+        an object with delta_var / delta_dist, such as an EmbeddingLoss): embedding_loss_host over the gathered logits instead."""
         if self.plan is None:
             raise ValueError("HostDraw.attach_vis: the store was built without 'vis'")
-        _, rows, loss, _ = vis_head_host(maps, self.box, self.map_of, self.im_hw, self.track, self.offsets,
-                                         np.asarray(mean).ravel()[-VIS_COLS:], np.asarray(std).ravel()[-VIS_COLS:], input_hw, down_ratio)
+        logits, rows, loss, _ = vis_head_host(maps, self.box, self.map_of, self.im_hw, self.track, self.offsets,
+                                              np.asarray(mean).ravel()[-VIS_COLS:], np.asarray(std).ravel()[-VIS_COLS:], input_hw, down_ratio)
         self.X[:, self.X.shape[1] - VIS_COLS:] = rows
-        return loss
+        if isinstance(embed_loss, str) and embed_loss == 'identity':
+            return loss
+        if isinstance(embed_loss, str) and embed_loss != 'embedding':
+            raise ValueError(f"HostDraw.attach_vis: embed_loss={embed_loss!r}; 'identity', 'embedding' or an EmbeddingLoss expected")
+        deltas = (0.5, 10.0) if isinstance(embed_loss, str) else (embed_loss.delta_var, embed_loss.delta_dist)
+        return embedding_loss_host(logits, self.track, self.offsets, *deltas)[0]
 
 
 @dataclass
@@ -313,17 +320,18 @@ class DrawnChunks:
     track: Optional[torch.Tensor] = None    # int32 [n_max] = y[:, 1]
     plan: Optional[FramePlan] = None
 
-    def attach_vis(self, head, maps, loss: bool = True):
+    def attach_vis(self, head, maps, loss: bool = True, embed_loss='identity'):
         """The visual head on the draw: maps [T, 128, Hm, Wm] = the CNN's answer to the images of `plan` (FrameStore.gather).  The
         standardised softmax rows go into the last 128 columns of X; with `loss` the per-chunk identity loss [B] is returned,
-        differentiable wrt `maps` (VisHead.forward), otherwise None (VisHead.rows).  No wait for the device."""
+        differentiable wrt `maps` (VisHead.forward), otherwise None (VisHead.rows).  embed_loss: which loss that is --
+        'identity', 'embedding' or an EmbeddingLoss (VisHead.forward's `loss`).  No wait for the device."""
         if self.plan is None:
             raise ValueError("DrawnChunks.attach_vis: the store was built without 'vis'")
         col = int(self.X.shape[1]) - VIS_COLS
         if not loss:
             head.rows(maps, self.box, self.map_of, self.im_hw, out=self.X, col=col)
             return None
-        return head.forward(maps, self.box, self.map_of, self.im_hw, self.track, self.offsets, out=self.X, col=col)[1]
+        return head.forward(maps, self.box, self.map_of, self.im_hw, self.track, self.offsets, out=self.X, col=col, loss=embed_loss)[1]
 
     def batch(self):
         """The TrainBatch of the drawn chunks (build_train_batch_device; its two host reads are the only waits).  The maximum of

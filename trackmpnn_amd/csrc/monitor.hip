@@ -167,6 +167,29 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_train_record_fold(const int32_
     }
 }
 
+__global__ __launch_bounds__(FOLD_THREADS) void k_train_embed_fold(const float* __restrict__ loss_d, int n_loss,
+                                                                   const int64_t* __restrict__ kept, int n_kept,
+                                                                   tmpnn_embed_record* __restrict__ rec) {
+    __shared__ double s_d[FOLD_THREADS];
+    __shared__ long long s_n[FOLD_THREADS];
+    double sd = 0.0;
+    long long n = 0, skipped = 0;
+    for (long k = threadIdx.x; k < n_kept; k += FOLD_THREADS) {            // a thread takes its chunks in ascending order
+        const long long b = kept ? (long long)kept[k] : (long long)k;
+        if (b < 0 || b >= n_loss) { ++skipped; continue; }
+        sd += (double)loss_d[b];
+        ++n;
+    }
+    sd = fold_tree(sd, s_d);
+    n = fold_tree(n, s_n);
+    skipped = fold_tree(skipped, s_n);
+    if (threadIdx.x == 0) {
+        rec->sum_loss_d += sd;
+        rec->chunks += n;
+        rec->skipped += skipped;
+    }
+}
+
 }  // namespace tmpnn
 
 using namespace tmpnn;
@@ -213,6 +236,16 @@ int tmpnn_train_record_fold(const int32_t* counts, int C, int W, const float* lo
     hipLaunchKernelGGL(k_train_record_fold, dim3(1), dim3(FOLD_THREADS), 0, as_stream(stream), counts, C, W, loss_c, loss_f, B,
                        rec);
     return check_launch("train_record_fold");
+}
+
+int tmpnn_train_embed_fold(const float* loss_d, int n_loss, const int64_t* kept, int n_kept, tmpnn_embed_record* rec,
+                           tmpnn_stream stream) {
+    TM_REQUIRE(rec != nullptr, "train_embed_fold: record is null");
+    TM_REQUIRE(n_loss >= 0 && n_kept >= 0, "train_embed_fold: n_loss=%d n_kept=%d", n_loss, n_kept);
+    TM_REQUIRE(n_loss == 0 || loss_d, "train_embed_fold: loss_d is null");
+    if (n_kept == 0) return TMPNN_OK;
+    hipLaunchKernelGGL(k_train_embed_fold, dim3(1), dim3(FOLD_THREADS), 0, as_stream(stream), loss_d, n_loss, kept, n_kept, rec);
+    return check_launch("train_embed_fold");
 }
 
 }  // extern "C"

@@ -178,6 +178,36 @@ __global__ __launch_bounds__(VH_THREADS) void k_vis_bwd(tmpnn_vis_head a, const 
     dst[(int64_t)(lane + 64) * plane] = acc1;
 }
 
+// the ownership scan of k_vis_bwd for a gradient that is handed in: the owner of a pixel adds d_logits of its sharers in ascending
+// row order and stores once (tmpnn_vis_head_scatter)
+__global__ __launch_bounds__(VH_THREADS) void k_vis_scatter(tmpnn_vis_head a, const float* __restrict__ dl, float* __restrict__ dmaps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * VH_WAVES + (threadIdx.x >> 6);     // (wave-uniform)
+    if (i >= a.D) return;
+    const int my = a.key[i];
+    const int64_t plane = (int64_t)a.Hm * a.Wm;
+    if (my < 0 || (int64_t)my >= (int64_t)a.T * plane) return;                  // no label, or in no chunk: nothing to add
+    for (int64_t j0 = 0; j0 < i; j0 += 64) {                                    // a lower row on this pixel owns it
+        const int64_t j = j0 + lane;
+        if (__ballot(j < i && a.key[j] == my)) return;
+    }
+    float acc0 = 0.0f, acc1 = 0.0f;
+    for (int64_t j0 = i & ~(int64_t)63; j0 < a.D; j0 += 64) {
+        const int64_t j = j0 + lane;
+        unsigned long long hits = __ballot(j >= i && j < a.D && a.key[j] == my);
+        while (hits) {                                                          // ascending rows
+            const int64_t r = j0 + (__ffsll((long long)hits) - 1);
+            hits &= hits - 1;
+            acc0 += dl[r * VH_C + lane];
+            acc1 += dl[r * VH_C + lane + 64];
+        }
+    }
+    const int64_t m = my / plane, inmap = my % plane;
+    float* dst = dmaps + m * VH_C * plane + inmap;
+    dst[(int64_t)lane * plane] = acc0;
+    dst[(int64_t)(lane + 64) * plane] = acc1;
+}
+
 int check_args(const tmpnn_vis_head* a, const char* who) {
     TM_REQUIRE(a != nullptr, "%s: the call struct is null", who);
     TM_REQUIRE(a->T >= 1 && a->Hm >= 1 && a->Wm >= 1 && (int64_t)a->T * a->Hm * a->Wm < 0x7fffffffLL, "%s: maps of %d x %d x %d pixels "
@@ -217,6 +247,20 @@ extern "C" int tmpnn_vis_head_bwd(const tmpnn_vis_head* a, const float* g, float
     if (a->D > 0 && a->track != nullptr) {
         hipLaunchKernelGGL(k_vis_bwd, dim3((unsigned)ceil_div(a->D, VH_WAVES)), dim3(VH_THREADS), 0, as_stream(stream), *a, g, dmaps);
         if (int rc = check_launch("vis_head_bwd (scatter)")) return rc;
+    }
+    return TMPNN_OK;
+}
+
+extern "C" int tmpnn_vis_head_scatter(const tmpnn_vis_head* a, const float* d_logits, float* dmaps, tmpnn_stream stream) {
+    if (int rc = check_args(a, "vis_head_scatter")) return rc;
+    TM_REQUIRE(dmaps != nullptr && (a->D == 0 || d_logits != nullptr), "vis_head_scatter: d_logits or dmaps is null");
+    const size_t bytes = sizeof(float) * (size_t)a->T * VH_C * (size_t)a->Hm * (size_t)a->Wm;
+    hipError_t e = hipMemsetAsync(dmaps, 0, bytes, as_stream(stream));
+    if (e != hipSuccess) return set_error(TMPNN_ELAUNCH, "vis_head_scatter (memset): %s", hipGetErrorString(e));
+    if (a->D > 0 && a->track != nullptr) {
+        hipLaunchKernelGGL(k_vis_scatter, dim3((unsigned)ceil_div(a->D, VH_WAVES)), dim3(VH_THREADS), 0, as_stream(stream), *a, d_logits,
+                           dmaps);
+        if (int rc = check_launch("vis_head_scatter")) return rc;
     }
     return TMPNN_OK;
 }

@@ -180,6 +180,7 @@ class VisTraining:
     frames: Any             # frames.FrameStore: the resized frames of the store's sequences, in the store's order
     embed_net: Any          # the embedding CNN: images [T, 3, H, W] -> maps [T, 128, Hm, Wm]
     embed_opt: Any          # its optimizer (zero_grad / step next to the tracker's)
+    embed_loss: Any = 'identity'    # loss_d: 'identity' (FairMOTLoss), 'embedding' or an embedloss.EmbeddingLoss (its deltas)
 
 
 def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier: bool = True, monitor=None, scheduler=None,
@@ -196,8 +197,10 @@ def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier:
     skipped runs no CNN), images = vis.frames.gather(drawn.plan), maps = vis.embed_net(images), loss_d =
     drawn.attach_vis(vis.head, maps) (the rows into the last 128 columns of X, detached as the reference's features.detach()),
     both optimizers' zero_grad, train_chunks, loss_d[batch.kept].sum().backward() (the identity loss of the chunks the batch
-    kept: the reference `continue`s past a skipped chunk before its backward, train.py:56-67), both optimizers' step.  loss_d
-    is not handed to the monitor."""
+    kept: the reference `continue`s past a skipped chunk before its backward, train.py:56-67), both optimizers' step.
+    vis.embed_loss chooses loss_d: the identity loss (the default) or the reference's EmbeddingLoss over the gathered logits.
+    The monitor takes the kept chunks' loss_d in one launch (TrainMonitor.fold_embed: 'avg_loss_d' and 'avg_loss_total', the
+    reference's "Average embedding loss for epoch" and its total, train.py:157-171)."""
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError(f'train_epoch: batch_size={batch_size}')
@@ -218,12 +221,15 @@ def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier:
         except AllChunksSkipped:
             continue
         if vis is not None:
-            loss_d = drawn.attach_vis(vis.head, vis.embed_net(vis.frames.gather(drawn.plan)))
+            loss_d = drawn.attach_vis(vis.head, vis.embed_net(vis.frames.gather(drawn.plan)), embed_loss=vis.embed_loss)
             vis.embed_opt.zero_grad()
         opt.zero_grad()
         train_chunks(model, batch, drawn.features(batch), tp_classifier, monitor=monitor)
         if vis is not None:
-            loss_d.index_select(0, _to_device(batch.kept, loss_d.device)).sum().backward()
+            kept = _to_device(batch.kept, loss_d.device)
+            if monitor is not None:
+                monitor.fold_embed(loss_d, kept)
+            loss_d.index_select(0, kept).sum().backward()
             vis.embed_opt.step()
         opt.step()
         steps += 1

@@ -17,6 +17,10 @@ the record with one launch.  The host waits for the device in `read()` only:
     stats = m.read()                                       # avg_f1, avg_loss_c, avg_loss_f, avg_loss, forwards, chunks
     m.reset()
 
+With visual features the reference also logs the embedding network's loss ("Average embedding loss for epoch", train.py:157-163):
+`train_epoch(vis=..., monitor=m)` hands the kept chunks' `loss_d` to `m.fold_embed` (one launch, a record of its own: struct
+tmpnn_embed_record), and `read()` then also carries `avg_loss_d` and `avg_loss_total`.
+
 Every (call, chunk) pair of a batch in which the chunk has rows is one forward, so a batched epoch averages over the same
 forwards as the reference's chunk-by-chunk loop.  Under `trackmpnn_amd.dist` each rank's monitor covers its own shard.
 
@@ -62,10 +66,30 @@ class TrainMonitor:
         self.device = dev
         self.record = torch.zeros(len(_FIELDS), dtype=torch.int64, device=dev)
         self.last_counts: Optional[torch.Tensor] = None
+        self.embed_record: Optional[torch.Tensor] = None      # int64 [3]: struct tmpnn_embed_record, made by the first fold_embed
 
     def reset(self) -> None:
         """Zero the record (an epoch boundary).  No host read."""
         self.record.zero_()
+        self.embed_record = None
+
+    def fold_embed(self, loss_d: torch.Tensor, kept: Optional[torch.Tensor] = None) -> None:
+        """One launch: the embedding network's loss of the chunks `kept` (int64 indices on the device into loss_d [n]; None: every
+        chunk) into a record of its own: an fp64 sum in a fixed order and the number of chunks.  `read()` then also gives
+        'avg_loss_d' and 'avg_loss_total' (train.py:157-163).  No host read."""
+        ld = loss_d.detach().reshape(-1)
+        ld = ld if (ld.dtype == torch.float32 and ld.is_contiguous()) else ld.float().contiguous()
+        if ld.device != self.record.device:
+            raise ValueError(f'TrainMonitor.fold_embed: loss_d on {ld.device}, the monitor on {self.record.device}')
+        if kept is not None:
+            if kept.device != ld.device or kept.dtype != torch.int64:
+                raise ValueError('TrainMonitor.fold_embed: kept must be an int64 tensor on the device of loss_d')
+            kept = kept.reshape(-1).contiguous()
+        if self.embed_record is None:
+            self.embed_record = torch.zeros(3, dtype=torch.int64, device=self.record.device)
+        n_kept = int(ld.numel() if kept is None else kept.numel())
+        _lib.call('tmpnn_train_embed_fold', ld.data_ptr() if ld.numel() else None, int(ld.numel()), _lib.ptr(kept) if n_kept else None,
+                  n_kept, self.embed_record.data_ptr(), _lib.raw_stream(self.device))
 
     def new_counts(self, C: int, W: int, zero: bool) -> torch.Tensor:
         """int32 [C, 4, W] for the counts of a step (zero: rows no call will write must read as `no forward`)."""
@@ -94,16 +118,30 @@ class TrainMonitor:
 
     def read(self) -> Dict[str, float]:
         """The one device -> host copy: what train.py:157-171 logs, and the two divisors.  A mean over nothing (no forward /
-        no chunk since the last reset) is NaN, as the reference's np.mean of an empty list."""
-        raw = self.record.cpu().numpy()
+        no chunk since the last reset) is NaN, as the reference's np.mean of an empty list.  If fold_embed ran since the last
+        reset(), also 'avg_loss_d' = the mean of loss_d over the chunks it took and 'avg_loss_total' = the mean of
+        loss_d + loss_c + loss_f over the chunks = avg_loss_d + avg_loss (both folds take the kept chunks of every step); the
+        copy then carries both records."""
+        if self.embed_record is None:
+            raw = self.record.cpu().numpy()
+        else:
+            both = torch.cat([self.record, self.embed_record]).cpu().numpy()
+            raw, eraw = both[:len(_FIELDS)], both[len(_FIELDS):]
         f = raw.view(np.float64)
         forwards, chunks = int(raw[1]), int(raw[5])
         nan = float('nan')
-        return dict(avg_f1=float(f[0]) / forwards if forwards else nan,
-                    avg_loss_c=float(f[2]) / chunks if chunks else nan,
-                    avg_loss_f=float(f[3]) / chunks if chunks else nan,
-                    avg_loss=float(f[4]) / chunks if chunks else nan,
-                    forwards=forwards, chunks=chunks)
+        out = dict(avg_f1=float(f[0]) / forwards if forwards else nan,
+                   avg_loss_c=float(f[2]) / chunks if chunks else nan,
+                   avg_loss_f=float(f[3]) / chunks if chunks else nan,
+                   avg_loss=float(f[4]) / chunks if chunks else nan,
+                   forwards=forwards, chunks=chunks)
+        if self.embed_record is not None:
+            if int(eraw[2]):
+                raise RuntimeError(f'TrainMonitor.read: fold_embed was handed {int(eraw[2])} chunk indices outside loss_d')
+            n_d = int(eraw[1])
+            out['avg_loss_d'] = float(eraw.view(np.float64)[0]) / n_d if n_d else nan
+            out['avg_loss_total'] = out['avg_loss_d'] + out['avg_loss']
+        return out
 
 
 _VAL_FIELDS = ('sum_f1', 'forwards', 'tp', 'fp', 'fn', 'rows')                            # struct tmpnn_val_record

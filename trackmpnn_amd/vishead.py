@@ -6,7 +6,8 @@ the identity loss over the same rows (reference dataset/kitti_mot.py:391-412, 55
     vis_head_host       logits, standardised softmax rows, per-chunk identity loss and its gradient wrt the maps, in numpy, in the
                         dtype of `maps` (float64: the yardstick of the device tests)
     VisHead             the same on the device (tmpnn_vis_head_fwd, tmpnn_vis_head_bwd; csrc/vishead.hip): `rows()` for inference,
-                        `forward()` a torch.autograd.Function whose backward hands d(loss)/d(maps) to the user's CNN, `record()`
+                        `forward()` a torch.autograd.Function whose backward hands d(loss)/d(maps) to the user's CNN, `record()`;
+                        `forward(loss='embedding')` puts the reference's EmbeddingLoss (embedloss.py) in the identity loss's place
 
 The rule.  A detection with box x1 y1 x2 y2 in an image of im_h x im_w pixels that the CNN sees resized to input_h x input_w and
 answers with a map of 1 / down_ratio that size reads the pixel
@@ -200,6 +201,30 @@ class _VisFn(torch.autograd.Function):
         return dmaps, None, None, None, None, None, None, None
 
 
+class _VisEmbedFn(torch.autograd.Function):
+    """VisHead.forward(loss='embedding'): the forward launches write rows, logits and pixels, the embedding loss
+    (embedloss.EmbeddingLoss) runs over the saved logits; backward: its gradient wrt the logits, then tmpnn_vis_head_scatter."""
+
+    @staticmethod
+    def forward(ctx, maps, head, crit, box, map_of, im_hw, track, offsets, dest):
+        call = head._launch(maps, box, map_of, im_hw, track, offsets, dest[0], dest[1])
+        ecall = crit._launch(call.logits, call.keep[4], call.keep[5])           # (the head's own device track and offsets)
+        ctx.call, ctx.ecall, ctx.head, ctx.crit = call, ecall, head, crit
+        if dest[0] is not None:
+            return ecall.loss
+        ctx.mark_non_differentiable(call.rows)
+        return call.rows, ecall.loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        call, head = ctx.call, ctx.head
+        d_logits = ctx.crit._backward(ctx.ecall, grads[-1]).contiguous()
+        dmaps = torch.empty(call.maps_shape, dtype=torch.float32, device=head.device)
+        _lib.call('tmpnn_vis_head_scatter', C.byref(call.c), d_logits.data_ptr(), dmaps.data_ptr(), _lib.raw_stream(head.device))
+        return dmaps, None, None, None, None, None, None, None, None
+
+
 class VisHead:
     """The visual head on the device (module docstring).
 
@@ -313,15 +338,42 @@ class VisHead:
         with torch.no_grad():
             return self._launch(maps, box, map_of, im_hw, None, None, out, col).rows
 
-    def forward(self, maps, box, map_of, im_hw, track, offsets, out: Optional[torch.Tensor] = None, col: int = 0):
+    def forward(self, maps, box, map_of, im_hw, track, offsets, out: Optional[torch.Tensor] = None, col: int = 0, loss='identity'):
         """(rows [D, 128], loss [B]): the feature columns (detached, as the reference's features.detach()) and the identity loss
         of every chunk, differentiable wrt `maps`.  With `out` [D, F] the rows are written into its columns col .. col + 127 as
-        rows() writes them, and `out` itself is returned in their place."""
+        rows() writes them, and `out` itself is returned in their place.
+
+        loss: 'identity' (FairMOTLoss, the default), 'embedding' (the reference's EmbeddingLoss over the gathered logits with its
+        default deltas; module docstring of trackmpnn_amd.embedloss) or an embedloss.EmbeddingLoss instance for other deltas.
+        `embed_record()` then gives the embedding loss's counts of the call."""
         if track is None or offsets is None:
             raise ValueError('VisHead.forward: track and offsets are needed (rows() is the call without a loss)')
+        if not (isinstance(loss, str) and loss == 'identity'):
+            crit = self._embedding(loss)
+            got = _VisEmbedFn.apply(maps, self, crit, box, map_of, im_hw, track, offsets, (out, col if out is not None else 0))
+            self._last_embed = crit
+            return (out, got) if out is not None else got
         if out is None:
             return _VisFn.apply(maps, self, box, map_of, im_hw, track, offsets, (None, 0))
         return out, _VisFn.apply(maps, self, box, map_of, im_hw, track, offsets, (out, col))
+
+    def _embedding(self, loss):
+        """The EmbeddingLoss behind forward(loss=...): the instance handed in, or one with the reference's deltas for 'embedding'."""
+        from .embedloss import EmbeddingLoss
+        if isinstance(loss, EmbeddingLoss):
+            return loss
+        if isinstance(loss, str) and loss == 'embedding':
+            if getattr(self, '_embed_default', None) is None:
+                self._embed_default = EmbeddingLoss()
+            return self._embed_default
+        raise ValueError(f"VisHead.forward: loss={loss!r}; 'identity', 'embedding' or an EmbeddingLoss expected")
+
+    def embed_record(self) -> dict:
+        """EmbeddingLoss.record() of the last forward(loss='embedding') (one host read)."""
+        crit = getattr(self, '_last_embed', None)
+        if crit is None:
+            raise RuntimeError("VisHead.embed_record: no forward(loss='embedding') has been made")
+        return crit.record()
 
     def last_logits(self) -> torch.Tensor:
         """The gathered logits [D, 128] of the last call (a view of its buffer)."""
