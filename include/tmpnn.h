@@ -79,7 +79,9 @@ extern "C" {
                                    point added, none changed);
                                still 13, for the same reason: + struct tmpnn_embed_loss, tmpnn_embed_loss_ws,
                                    tmpnn_embed_loss_fwd, tmpnn_embed_loss_bwd, tmpnn_vis_head_scatter, struct
-                                   tmpnn_embed_record, tmpnn_train_embed_fold (entry points added, none changed) */
+                                   tmpnn_embed_record, tmpnn_train_embed_fold (entry points added, none changed);
+                               still 13, for the same reason: + tmpnn_espnet_arena_floats, tmpnn_espnet_ws_bytes,
+                                   tmpnn_espnet_fwd (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1682,6 +1684,40 @@ int tmpnn_wide_gru_bwd_diff_fused(const void* prep, const tmpnn_graph* g, const 
                                   float* d_h, int ld_dh, float* dW_ih, float* dW_hh, float* db_ih, float* db_hh, void* ws,
                                   size_t ws_bytes, const float* add_msg, int ld_add, tmpnn_stream stream,
                                   tmpnn_stream aux_stream, tmpnn_event ev_fork, tmpnn_event ev_join);
+
+/* ======================================================================================================
+ * The embedding CNN (csrc/espnet.hip; host definition: trackmpnn_amd.espnet.espnet_host): the reference's ESPNetv2
+ * segmentation net EESPNet_Seg(classes = C, s = 1) (models/espv2) in eval mode.  images [T][3][H][W] float32 ->
+ * out [T][C][H][W] float32, both contiguous NCHW; H and W positive multiples of 16.  Every BatchNorm uses its running
+ * statistics, folded by the caller into a per-channel scale and shift; both Dropout2d are the identity.  No atomics: results
+ * are bitwise reproducible, and image i of a batch gives the same bits for every T.
+ *
+ * The weight arena is one array of float32.  It is a sequence of segments, each padded with zeros to a multiple of 4 floats,
+ * in this order (a "norm" is scale [c] | shift [c]; slopes are the per-channel PReLU weights):
+ *   level1      W [32][3][3][3] | scale [32] | shift [32] | slope [32]
+ *   DOWN(level2_0: 32 -> 64)  DOWN(level3_0: 64 -> 128)  3 x EESP(level3: 128 -> 128)
+ *   DOWN(level4_0: 128 -> 256)  7 x EESP(level4: 256 -> 256)
+ *   PW(proj_L4_C: 256 -> 128)   EESP(pspMod.0: 256 -> 128)
+ *   4 x W [128][9] (pspMod.1.stages)   PW(pspMod.1.project: 640 -> 128)
+ *   PW(project_l3: 128 -> C; the norm and slopes of act_l3)   PW(project_l2: 64 + C -> C)   PW(project_l1: 32 + C -> C)
+ * with
+ *   PW(cin -> cout, groups g)   Wt [cin / g][cout] (the conv weight [cout][cin / g] transposed) | scale [cout] | shift [cout] |
+ *                               slope [cout]; without a norm scale = 1, shift = 0; without an activation slope = 1
+ *   EESP(nin -> nout), n = nout / 4
+ *                               PW(proj_1x1: nin -> n, g = 4) | W [4][n][9] (spp_dw.0 .. 3) | scale [nout] | shift [nout] |
+ *                               slope [nout] (br_after_cat) | PW(conv_1x1_exp: nout -> nout, g = 4; slopes: module_act, or
+ *                               in a DOWN the block's act from channel nin on)
+ *   DOWN(nin -> nout)           W [3][3][3][3] | scale [3] | shift [3] | slope [3] (inp_reinf.0) | Wt [3][nout] | scale [nout] |
+ *                               shift [nout] (inp_reinf.1) | slope [nin] (act, channels below nin) | EESP(eesp: nin -> nout - nin)
+ * tmpnn_espnet_arena_floats(C) is the length of that array (0: C outside 1 .. 1024); tmpnn_espnet_ws_bytes the workspace of one
+ * call (0: a shape tmpnn_espnet_fwd refuses).  tmpnn_espnet_fwd validates on the host before any launch (null pointers, H or W
+ * not a multiple of 16, T outside 1 .. 65535, max(C, 160) H W >= 2^31, pointers not 16-byte aligned: TMPNN_EINVAL; a short
+ * workspace: TMPNN_EWORKSPACE), then enqueues 70 launches on `stream`, whatever T is; nothing is allocated, copied or waited for.
+ * ====================================================================================================== */
+size_t tmpnn_espnet_arena_floats(int C);
+size_t tmpnn_espnet_ws_bytes(int T, int H, int W, int C);
+int tmpnn_espnet_fwd(const float* arena, int C, const float* images, int T, int H, int W, void* ws, size_t ws_bytes, float* out,
+                     tmpnn_stream stream);
 
 /* ---- comparison builds only (-DTMPNN_KEEP_VARIANTS; tools/build_variant.sh) ------------------------------------------------
  * Superseded forms kept for A/B runs: the two-kernel backward of the wide cells (the shipped path takes both W_ih products on

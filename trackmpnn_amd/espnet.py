@@ -1,0 +1,388 @@
+"""The embedding CNN: the reference's default `--embed-arch espv2`, EESPNet_Seg(classes=C, s=1) (models/espv2), in eval mode.
+
+    espnet_spec(C)          every tensor name of the net's state_dict() with its shape: the DEFINITION of what loads
+    espnet_host(sd, images) the eval forward over a state dict with torch ops, written from the architecture (float64: the
+                            yardstick of the device tests; on a device tensor torch runs it through MIOpen: the timing baseline)
+    fold_bn                 a BatchNorm's running statistics as a per-channel scale and shift, float64 then rounded once
+    pack_arena(sd, C)       the float32 weight arena of the device (layout: include/tmpnn.h, struct-free: one array)
+    EspEmbedNet             the same forward on the device (tmpnn_espnet_fwd; csrc/espnet.hip): `net(images) -> maps`, drops in
+                            wherever an `embed_net` is taken (OnlineVis, VisInference, SequenceFeatures.attach_vis)
+
+The net.  Encoder (widths 32 / 64 / 128 / 256 at 1/2, 1/4, 1/8, 1/16 of the input):
+    level1      3x3 stride-2 conv 3 -> 32, BN, PReLU
+    level2_0    DownSampler 32 -> 64;  level3_0  DownSampler 64 -> 128, then 3 EESP(128);  level4_0  DownSampler 128 -> 256, then
+                7 EESP(256)
+    DownSampler(nin, nout)(x, image) = PReLU(cat[avg_pool3x3 s2 p1 (x), EESP_s2(x)] + inp_reinf(image pooled to that size));
+                the pool counts its padding (every window / 9); inp_reinf = 3x3 conv 3 -> 3, BN, PReLU, 1x1 conv 3 -> nout, BN; its
+                stride-2 EESP returns before the residual and the PReLU
+    EESP(nin, nout, stride, r_lim): grouped 1x1 conv (groups 4) nin -> n = nout / 4, BN, PReLU; four depthwise 3x3 convs of dilation
+                d_k (padding d_k, the block's stride) fused as out_k = conv_k + out_{k-1} for every k >= 1; concat, BN, PReLU;
+                grouped 1x1 conv nout -> nout (groups 4), BN; + input where the shapes agree; PReLU.  The dilations are
+                ((s - 1) / 2 for s in sorted(3 + 2 i if 3 + 2 i <= r_lim else 3 for i in 0..3)): 1 2 3 4 for r_lim >= 9 (level2_0,
+                level3_0, level3, level4_0), 1 1 2 3 for r_lim = 7 (level4, pspMod)
+Decoder: proj_L4_C (1x1 256 -> 128, BN, PReLU), bilinear x2, pspMod = EESP(256 -> 128) over cat[out_l3, up] then the PSP module (four
+times: pool the previous level 3x3 s2 p1, depthwise 3x3, bilinear back to the level-3 size; concat 5 x 128; 1x1 640 -> 128, BN,
+PReLU), project_l3 (1x1 128 -> C), act_l3 (BN, PReLU), x2, project_l2 (1x1 64 + C -> C, BN, PReLU over cat[out_l2, up]), x2,
+project_l1 (1x1 32 + C -> C, nothing else, over cat[out_l1, up]), x2.  Every bilinear is align_corners=True.  Every BatchNorm uses
+its running statistics and both Dropout2d are the identity.
+
+Out of scope: training the CNN (backward, batch statistics, Dropout2d: train it in torch and hand the state dict over), the
+reference's other backbone (dla34 / DCNv2), s != 1, ImageNet classification checkpoints (they hold level5 and a classifier).
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+BN_EPS = 1e-5
+_BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')
+_PSP = 128
+
+
+def _dilations(r_lim: int) -> Tuple[int, ...]:
+    sizes = sorted(3 + 2 * i if 3 + 2 * i <= r_lim else 3 for i in range(4))
+    return tuple((s - 1) // 2 for s in sizes)
+
+
+# ---- the state dict ----------------------------------------------------------------------------------------------------------
+def _spec_bn(spec, p, c):
+    for k in _BN_KEYS:
+        spec[f'{p}.{k}'] = (c,)
+
+
+def _spec_cbr(spec, p, cin, cout, k, groups=1, bn=True, act=True):
+    spec[f'{p}.conv.weight'] = (cout, cin // groups, k, k)
+    if bn:
+        _spec_bn(spec, f'{p}.bn', cout)
+    if act:
+        spec[f'{p}.act.weight'] = (cout,)
+
+
+def _spec_eesp(spec, p, nin, nout):
+    n = nout // 4
+    _spec_cbr(spec, f'{p}.proj_1x1', nin, n, 1, groups=4)
+    for i in range(4):
+        spec[f'{p}.spp_dw.{i}.conv.weight'] = (n, 1, 3, 3)
+    _spec_cbr(spec, f'{p}.conv_1x1_exp', nout, nout, 1, groups=4, act=False)
+    _spec_bn(spec, f'{p}.br_after_cat.bn', nout)
+    spec[f'{p}.br_after_cat.act.weight'] = (nout,)
+    spec[f'{p}.module_act.weight'] = (nout,)
+
+
+def _spec_down(spec, p, nin, nout):
+    _spec_eesp(spec, f'{p}.eesp', nin, nout - nin)
+    _spec_cbr(spec, f'{p}.inp_reinf.0', 3, 3, 3)
+    _spec_cbr(spec, f'{p}.inp_reinf.1', 3, nout, 1, act=False)
+    spec[f'{p}.act.weight'] = (nout,)
+
+
+def espnet_spec(C: int) -> 'OrderedDict[str, Tuple[int, ...]]':
+    """name -> shape of every tensor EESPNet_Seg(classes=C, s=1).state_dict() holds, the BatchNorms' num_batches_tracked
+    (shape (), accepted and ignored) left out."""
+    C = int(C)
+    if C < 1 or C > 1024:
+        raise ValueError(f'espnet: C={C} (1 .. 1024 expected)')
+    s: 'OrderedDict[str, Tuple[int, ...]]' = OrderedDict()
+    _spec_cbr(s, 'net.level1', 3, 32, 3)
+    _spec_down(s, 'net.level2_0', 32, 64)
+    _spec_down(s, 'net.level3_0', 64, 128)
+    for i in range(3):
+        _spec_eesp(s, f'net.level3.{i}', 128, 128)
+    _spec_down(s, 'net.level4_0', 128, 256)
+    for i in range(7):
+        _spec_eesp(s, f'net.level4.{i}', 256, 256)
+    _spec_cbr(s, 'proj_L4_C', 256, _PSP, 1)
+    _spec_eesp(s, 'pspMod.0', 2 * _PSP, _PSP)
+    for i in range(4):
+        s[f'pspMod.1.stages.{i}.conv.weight'] = (_PSP, 1, 3, 3)
+    _spec_cbr(s, 'pspMod.1.project', 5 * _PSP, _PSP, 1)
+    s['project_l3.1.conv.weight'] = (C, _PSP, 1, 1)
+    _spec_bn(s, 'act_l3.bn', C)
+    s['act_l3.act.weight'] = (C,)
+    _spec_cbr(s, 'project_l2', 64 + C, C, 1)
+    s['project_l1.1.conv.weight'] = (C, 32 + C, 1, 1)
+    return s
+
+
+def check_state_dict(sd) -> int:
+    """C of a state dict that is exactly EESPNet_Seg(classes=C, s=1).state_dict(); ValueError naming the first key that is
+    missing, unexpected or of the wrong shape."""
+    if not hasattr(sd, 'keys'):
+        raise ValueError('espnet: a state dict (name -> tensor) expected')
+    keys = list(sd.keys())
+    if keys and all(str(k).startswith('module.') for k in keys):
+        raise ValueError("espnet: every key starts with 'module.': this is the state dict of a DataParallel wrapper; save "
+                         "model.module.state_dict(), or strip the prefix, and load that")
+    k3 = 'project_l3.1.conv.weight'
+    if k3 not in sd:
+        raise ValueError(f'espnet: missing key {k3}')
+    w3 = sd[k3]
+    if w3.dim() != 4 or tuple(w3.shape[1:]) != (_PSP, 1, 1):
+        raise ValueError(f'espnet: {k3} of shape {tuple(w3.shape)}; (C, {_PSP}, 1, 1) expected')
+    spec = espnet_spec(int(w3.shape[0]))
+    for k, shp in spec.items():
+        if k not in sd:
+            raise ValueError(f'espnet: missing key {k}')
+        if tuple(sd[k].shape) != shp:
+            raise ValueError(f'espnet: {k} of shape {tuple(sd[k].shape)}; {shp} expected')
+    for k in keys:
+        if k in spec:
+            continue
+        if str(k).endswith('.num_batches_tracked') and str(k)[:-len('num_batches_tracked')] + 'weight' in spec:
+            continue
+        raise ValueError(f'espnet: unexpected key {k}')
+    return int(w3.shape[0])
+
+
+# ---- the host definition -----------------------------------------------------------------------------------------------------
+def espnet_host(sd, images, dtype=torch.float64, taps: bool = False):
+    """maps [T, C, H, W] in `dtype` on the device of `images`: the eval forward (module docstring) over the state dict `sd` with
+    torch ops.  images [T, 3, H, W], H and W positive multiples of 16.  taps=True: (maps, {'out_l1' .. 'out_l4': the encoder
+    outputs, 'merge_l3', 'merge_l2', 'merge_l1': the decoder merges before each upsampling})."""
+    check_state_dict(sd)
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError('espnet_host: images [T, 3, H, W] expected')
+    _check_hw(int(images.shape[2]), int(images.shape[3]))
+    dev = images.device
+    x = images.detach().to(dtype)
+
+    def g(k):
+        return sd[k].detach().to(device=dev, dtype=dtype)
+
+    def bn(v, p):
+        return F.batch_norm(v, g(p + '.running_mean'), g(p + '.running_var'), g(p + '.weight'), g(p + '.bias'), False, 0.0, BN_EPS)
+
+    def conv(v, p, stride=1, pad=0, dil=1, groups=1):
+        return F.conv2d(v, g(p + '.conv.weight'), None, stride, pad, dil, groups)
+
+    def pool(v):
+        return F.avg_pool2d(v, kernel_size=3, stride=2, padding=1)
+
+    def up(v, size=None):
+        if size is None:
+            size = (2 * v.shape[2], 2 * v.shape[3])
+        return F.interpolate(v, size=size, mode='bilinear', align_corners=True)
+
+    def cbr(v, p, **kw):
+        return F.prelu(bn(conv(v, p, **kw), p + '.bn'), g(p + '.act.weight'))
+
+    def eesp(v, p, stride, r_lim, down):
+        r = cbr(v, p + '.proj_1x1', groups=4)
+        outs = []
+        for k, d in enumerate(_dilations(r_lim)):
+            o = F.conv2d(r, g(f'{p}.spp_dw.{k}.conv.weight'), None, stride, d, d, r.shape[1])
+            outs.append(o if k == 0 else o + outs[k - 1])
+        cat = torch.cat(outs, 1)
+        cat = F.prelu(bn(cat, p + '.br_after_cat.bn'), g(p + '.br_after_cat.act.weight'))
+        e = bn(conv(cat, p + '.conv_1x1_exp', groups=4), p + '.conv_1x1_exp.bn')
+        if down:
+            return e
+        if e.shape == v.shape:
+            e = e + v
+        return F.prelu(e, g(p + '.module_act.weight'))
+
+    def down(v, p, r_lim, image):
+        o = torch.cat([pool(v), eesp(v, p + '.eesp', 2, r_lim, True)], 1)
+        r = cbr(image, p + '.inp_reinf.0', pad=1)
+        r = bn(conv(r, p + '.inp_reinf.1'), p + '.inp_reinf.1.bn')
+        return F.prelu(o + r, g(p + '.act.weight'))
+
+    img2 = pool(x)
+    img4 = pool(img2)
+    img8 = pool(img4)
+    img16 = pool(img8)
+    out_l1 = cbr(x, 'net.level1', stride=2, pad=1)
+    out_l2 = down(out_l1, 'net.level2_0', 13, img4)
+    out_l3 = down(out_l2, 'net.level3_0', 11, img8)
+    for i in range(3):
+        out_l3 = eesp(out_l3, f'net.level3.{i}', 1, 9, False)
+    out_l4 = down(out_l3, 'net.level4_0', 9, img16)
+    for i in range(7):
+        out_l4 = eesp(out_l4, f'net.level4.{i}', 1, 7, False)
+
+    p4 = cbr(out_l4, 'proj_L4_C')
+    feats = eesp(torch.cat([out_l3, up(p4)], 1), 'pspMod.0', 1, 7, False)
+    hw = (feats.shape[2], feats.shape[3])
+    stages, lvl = [feats], feats
+    for k in range(4):
+        lvl = pool(lvl)
+        stages.append(up(F.conv2d(lvl, g(f'pspMod.1.stages.{k}.conv.weight'), None, 1, 1, 1, _PSP), hw))
+    merge_l3 = cbr(torch.cat(stages, 1), 'pspMod.1.project')
+    m3 = F.prelu(bn(conv(merge_l3, 'project_l3.1'), 'act_l3.bn'), g('act_l3.act.weight'))
+    merge_l2 = cbr(torch.cat([out_l2, up(m3)], 1), 'project_l2')
+    merge_l1 = conv(torch.cat([out_l1, up(merge_l2)], 1), 'project_l1.1')
+    out = up(merge_l1)
+    if taps:
+        return out, {'out_l1': out_l1, 'out_l2': out_l2, 'out_l3': out_l3, 'out_l4': out_l4, 'merge_l3': merge_l3,
+                     'merge_l2': merge_l2, 'merge_l1': merge_l1}
+    return out
+
+
+def _check_hw(H: int, W: int) -> None:
+    if H <= 0 or W <= 0 or H % 16 or W % 16:
+        raise ValueError(f'espnet: images of {H} x {W}; H and W must be positive multiples of 16 (the decoder concatenates maps '
+                         'of 1/2, 1/4 and 1/8 of the input with upsampled ones)')
+
+
+# ---- the device's weights ----------------------------------------------------------------------------------------------------
+def fold_bn(weight, bias, running_mean, running_var, eps: float = BN_EPS) -> Tuple[np.ndarray, np.ndarray]:
+    """(scale, shift) float32 with BN(x) = x scale + shift for the running statistics: computed in float64, rounded once."""
+    w, b, m, v = (np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, np.float64)
+                  for t in (weight, bias, running_mean, running_var))
+    scale = w / np.sqrt(v + eps)
+    return scale.astype(np.float32), (b - m * scale).astype(np.float32)
+
+
+def pack_arena(sd, C: Optional[int] = None) -> np.ndarray:
+    """The float32 weight arena tmpnn_espnet_fwd reads (the segment order is documented in include/tmpnn.h)."""
+    c = check_state_dict(sd)
+    if C is not None and int(C) != c:
+        raise ValueError(f'espnet: the state dict has C={c}, not {C}')
+    C = c
+    segs = []
+
+    def a(k):
+        return sd[k].detach().cpu().numpy().astype(np.float32)
+
+    def seg(x):
+        x = np.ascontiguousarray(x, np.float32).ravel()
+        pad = (-x.size) % 4
+        segs.append(np.concatenate([x, np.zeros(pad, np.float32)]) if pad else x)
+
+    def norm(p, c):
+        if p is None:
+            seg(np.ones(c, np.float32)), seg(np.zeros(c, np.float32))
+        else:
+            s, t = fold_bn(*(sd[f'{p}.{k}'] for k in _BN_KEYS))
+            seg(s), seg(t)
+
+    def pw(conv, bn, slope):
+        w = a(conv + '.weight')[:, :, 0, 0]                      # [cout][cin / groups]
+        seg(w.T)
+        norm(bn, w.shape[0])
+        seg(np.ones(w.shape[0], np.float32) if slope is None else slope)
+
+    def eesp(p, exp_slope):
+        pw(p + '.proj_1x1.conv', p + '.proj_1x1.bn', a(p + '.proj_1x1.act.weight'))
+        seg(np.stack([a(f'{p}.spp_dw.{k}.conv.weight').reshape(-1, 9) for k in range(4)]))
+        norm(p + '.br_after_cat.bn', 0)
+        seg(a(p + '.br_after_cat.act.weight'))
+        pw(p + '.conv_1x1_exp.conv', p + '.conv_1x1_exp.bn', exp_slope)
+
+    def down(p, nin):
+        seg(a(p + '.inp_reinf.0.conv.weight'))
+        norm(p + '.inp_reinf.0.bn', 3)
+        seg(a(p + '.inp_reinf.0.act.weight'))
+        seg(a(p + '.inp_reinf.1.conv.weight')[:, :, 0, 0].T)
+        norm(p + '.inp_reinf.1.bn', 0)
+        act = a(p + '.act.weight')
+        seg(act[:nin])
+        eesp(p + '.eesp', act[nin:])
+
+    seg(a('net.level1.conv.weight'))
+    norm('net.level1.bn', 32)
+    seg(a('net.level1.act.weight'))
+    down('net.level2_0', 32)
+    down('net.level3_0', 64)
+    for i in range(3):
+        eesp(f'net.level3.{i}', a(f'net.level3.{i}.module_act.weight'))
+    down('net.level4_0', 128)
+    for i in range(7):
+        eesp(f'net.level4.{i}', a(f'net.level4.{i}.module_act.weight'))
+    pw('proj_L4_C.conv', 'proj_L4_C.bn', a('proj_L4_C.act.weight'))
+    eesp('pspMod.0', a('pspMod.0.module_act.weight'))
+    for i in range(4):
+        seg(a(f'pspMod.1.stages.{i}.conv.weight'))
+    pw('pspMod.1.project.conv', 'pspMod.1.project.bn', a('pspMod.1.project.act.weight'))
+    pw('project_l3.1.conv', 'act_l3.bn', a('act_l3.act.weight'))
+    pw('project_l2.conv', 'project_l2.bn', a('project_l2.act.weight'))
+    pw('project_l1.1.conv', None, None)
+    arena = np.concatenate(segs)
+    want = int(_lib.fn('tmpnn_espnet_arena_floats')(C))
+    if arena.size != want:
+        raise RuntimeError(f'espnet: packed {arena.size} floats, the library expects {want} for C={C}')
+    return arena
+
+
+class EspEmbedNet:
+    """EESPNet_Seg(classes=C, s=1) in eval mode on the device (module docstring).
+
+        net = EspEmbedNet.from_state_dict(sd)           sd: the torch module's state_dict() (a vis-net_*.pth snapshot)
+        maps = net(images, out=None)                    images [T, 3, H, W] float32 contiguous on the device, H and W multiples
+                                                        of 16 -> maps [T, C, H, W] float32 contiguous NCHW (what VisHead reads)
+
+    No autograd graph is built.  The workspace of a (T, H, W) is allocated at its first call and reused; a call then allocates
+    nothing but its result (nothing at all with `out`), waits for nothing and reads nothing back; every launch goes on the
+    current stream and their number (70) does not depend on T.  Results are bitwise reproducible, and image i of a batch gives
+    the same bits for every T.  The net is an eval-mode network: `training` is False, eval() and train(False) return it,
+    train(True) raises."""
+
+    training = False
+
+    def __init__(self, sd, device='cuda:0'):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError(f'EspEmbedNet on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a cuda '
+                               'device')
+        self.C = check_state_dict(sd)
+        self._sd = OrderedDict(sd.items())
+        arena = pack_arena(sd, self.C)
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        self.device = dev
+        self._arena = torch.from_numpy(arena).to(dev)
+        self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+        self._fwd = _lib.fn('tmpnn_espnet_fwd')
+
+    @classmethod
+    def from_state_dict(cls, sd, device='cuda:0') -> 'EspEmbedNet':
+        return cls(sd, device)
+
+    def state_dict(self):
+        """The tensors `from_state_dict` was given, under their names."""
+        return OrderedDict(self._sd.items())
+
+    def eval(self) -> 'EspEmbedNet':
+        return self
+
+    def train(self, mode: bool = True) -> 'EspEmbedNet':
+        if mode:
+            raise NotImplementedError('eval-mode network: train the CNN in torch')
+        return self
+
+    def __call__(self, images, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if not isinstance(images, torch.Tensor) or images.device.type != 'cuda':
+            raise RuntimeError('EspEmbedNet: images on the host: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path)')
+        if images.device != self.device or images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+            raise ValueError(f'EspEmbedNet: images [T, 3, H, W] float32 on {self.device} expected, got {tuple(images.shape)} '
+                             f'{images.dtype} on {images.device}')
+        T, _, H, W = (int(v) for v in images.shape)
+        _check_hw(H, W)
+        if not images.is_contiguous():
+            raise ValueError('EspEmbedNet: images must be contiguous')
+        if T < 1:
+            raise ValueError('EspEmbedNet: an empty batch')
+        ws = self._ws.get((T, H, W))
+        if ws is None:
+            nbytes = int(_lib.fn('tmpnn_espnet_ws_bytes')(T, H, W, self.C))
+            if nbytes == 0:
+                raise ValueError(f'EspEmbedNet: a batch of {T} x {H} x {W} with C={self.C} is too large for one call (T <= 65535, '
+                                 'max(C, 160) H W < 2^31)')
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws[(T, H, W)] = ws
+        if out is None:
+            out = torch.empty((T, self.C, H, W), dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32
+              or tuple(out.shape) != (T, self.C, H, W) or not out.is_contiguous()):
+            raise ValueError(f'EspEmbedNet: out [{T}, {self.C}, {H}, {W}] float32 contiguous on {self.device} expected')
+        rc = self._fwd(self._arena.data_ptr(), self.C, images.data_ptr(), T, H, W, ws.data_ptr(), ws.numel(), out.data_ptr(),
+                       _lib.raw_stream(self.device))
+        if rc != 0:
+            raise RuntimeError(f'tmpnn_espnet_fwd failed (code {rc}): {_lib.last_error()}')
+        return out
