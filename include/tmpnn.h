@@ -81,7 +81,10 @@ extern "C" {
                                    tmpnn_embed_loss_fwd, tmpnn_embed_loss_bwd, tmpnn_vis_head_scatter, struct
                                    tmpnn_embed_record, tmpnn_train_embed_fold (entry points added, none changed);
                                still 13, for the same reason: + tmpnn_espnet_arena_floats, tmpnn_espnet_ws_bytes,
-                                   tmpnn_espnet_fwd (entry points added, none changed) */
+                                   tmpnn_espnet_fwd (entry points added, none changed);
+                               still 13, for the same reason: + tmpnn_espnet_centres_ws_bytes, tmpnn_espnet_trunk,
+                                   tmpnn_espnet_centres, tmpnn_vis_head_pixels, tmpnn_vis_head_rows_from_logits (entry points
+                                   added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1585,6 +1588,13 @@ int tmpnn_vis_head_bwd(const tmpnn_vis_head* a, const float* g, float* dmaps, tm
  * `logits`: tmpnn_embed_loss_*).  Rows with a label in a chunk are added; rows that share a pixel are summed in ascending row
  * order by the lowest of them, which stores once (the ownership scan of tmpnn_vis_head_bwd): no atomics. */
 int tmpnn_vis_head_scatter(const tmpnn_vis_head* a, const float* d_logits, float* dmaps, tmpnn_stream stream);
+/* The head behind a CNN that answers per pixel (tmpnn_espnet_centres), for inference: `maps` may be NULL, track and offsets are
+ * NULL and B = 1.  tmpnn_vis_head_pixels (one launch) writes pix and flag of every row by the centre rule above;
+ * tmpnn_vis_head_rows_from_logits (one launch, one wave per row and one for the counts) then reads `logits` [D][128] -- filled
+ * by the caller for the pixels in pix -- and writes everything else tmpnn_vis_head_fwd writes, by the same arithmetic: rows
+ * from equal logits are equal bit for bit. */
+int tmpnn_vis_head_pixels(const tmpnn_vis_head* a, tmpnn_stream stream);
+int tmpnn_vis_head_rows_from_logits(const tmpnn_vis_head* a, tmpnn_stream stream);
 
 /* ======================================================================================================
  * The embedding loss (csrc/embedloss.hip; host definition: trackmpnn_amd.embedloss.embedding_loss_host): the reference's
@@ -1718,6 +1728,22 @@ size_t tmpnn_espnet_arena_floats(int C);
 size_t tmpnn_espnet_ws_bytes(int T, int H, int W, int C);
 int tmpnn_espnet_fwd(const float* arena, int C, const float* images, int T, int H, int W, void* ws, size_t ws_bytes, float* out,
                      tmpnn_stream stream);
+/* The same net answered at single pixels.  Everything behind the C-channel map at 1/8 size is pointwise convs and x2 resizes, so
+ * one output pixel needs 2 x 2 pixels of the last merge, 3 x 3 of the one before and the taps of those at 1/8 size.
+ *   tmpnn_espnet_centres_ws_bytes   the workspace without the four maps of the dense tail (0: a shape that is refused); the
+ *                                   arrays of the trunk lie where they lie in the workspace of tmpnn_espnet_fwd
+ *   tmpnn_espnet_trunk              the first 65 launches of tmpnn_espnet_fwd (the same host code), which leave the encoder
+ *                                   outputs at 1/2 and 1/4 size and that 1/8 map in the workspace; the same checks
+ *   tmpnn_espnet_centres            after the trunk on the same stream, with the same workspace: one launch, one workgroup per
+ *                                   entry of pix [D] (pix = (t H + y) W + x, T H W < 2^31), logits [D][C] = what
+ *                                   tmpnn_espnet_fwd leaves at out[t][.][y][x], bit for bit; flags [D] = 1 where pix lay
+ *                                   outside [0, T H W) and was clamped into it, else 0.  1 <= C <= 256 (TMPNN_EINVAL names
+ *                                   the dense call for wider nets); D = 0 launches nothing; no atomics. */
+size_t tmpnn_espnet_centres_ws_bytes(int T, int H, int W, int C);
+int tmpnn_espnet_trunk(const float* arena, int C, const float* images, int T, int H, int W, void* ws, size_t ws_bytes,
+                       tmpnn_stream stream);
+int tmpnn_espnet_centres(const float* arena, int C, int T, int H, int W, const void* ws, size_t ws_bytes, const int32_t* pix, int D,
+                         float* logits, int32_t* flags, tmpnn_stream stream);
 
 /* ---- comparison builds only (-DTMPNN_KEEP_VARIANTS; tools/build_variant.sh) ------------------------------------------------
  * Superseded forms kept for A/B runs: the two-kernel backward of the wide cells (the shipped path takes both W_ih products on

@@ -361,6 +361,8 @@ _SIGNATURES = {
     'tmpnn_vis_head_fwd': (c_int, [_VHP, c_void_p]),
     'tmpnn_vis_head_bwd': (c_int, [_VHP, c_void_p, c_void_p, c_void_p]),
     'tmpnn_vis_head_scatter': (c_int, [_VHP, c_void_p, c_void_p, c_void_p]),
+    'tmpnn_vis_head_pixels': (c_int, [_VHP, c_void_p]),
+    'tmpnn_vis_head_rows_from_logits': (c_int, [_VHP, c_void_p]),
     'tmpnn_embed_loss_ws': (c_size_t, [C.c_int64, c_int]),
     'tmpnn_embed_loss_fwd': (c_int, [C.POINTER(CEmbedLoss), c_void_p]),
     'tmpnn_embed_loss_bwd': (c_int, [C.POINTER(CEmbedLoss), c_void_p, c_void_p, c_void_p]),
@@ -368,6 +370,10 @@ _SIGNATURES = {
     'tmpnn_espnet_arena_floats': (c_size_t, [c_int]),
     'tmpnn_espnet_ws_bytes': (c_size_t, [c_int] * 4),
     'tmpnn_espnet_fwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'tmpnn_espnet_centres_ws_bytes': (c_size_t, [c_int] * 4),
+    'tmpnn_espnet_trunk': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'tmpnn_espnet_centres': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

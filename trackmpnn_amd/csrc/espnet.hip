@@ -1,5 +1,6 @@
 // The embedding CNN on the device: the reference's ESPNetv2 segmentation net EESPNet_Seg(classes = C, s = 1) in eval mode
-// (tmpnn_espnet_arena_floats, tmpnn_espnet_ws_bytes, tmpnn_espnet_fwd; include/tmpnn.h; host definition:
+// (tmpnn_espnet_arena_floats, tmpnn_espnet_ws_bytes, tmpnn_espnet_fwd, and for single pixels tmpnn_espnet_centres_ws_bytes,
+// tmpnn_espnet_trunk, tmpnn_espnet_centres; include/tmpnn.h; host definition:
 // trackmpnn_amd.espnet.espnet_host).  float32 NCHW throughout; every BatchNorm arrives folded into a per-channel scale and
 // shift, every PReLU as per-channel slopes (a layer without an activation carries slopes of 1, without a norm scale 1 shift 0).
 //
@@ -27,6 +28,7 @@
 //                 weight is remainder / (out - 1) rounded once; an axis of one input or output pixel reads index 0.
 // k_esp_psp_up    one PSP stage behind its pooled map: depthwise 3x3 (no norm) evaluated at the four bilinear corners and
 //                 blended into the stage's slot of the 5 x 128 channel buffer the PSP projection reads.
+// k_esp_centres   the decoder tail behind the 1/8-size map at single pixels, a workgroup per pixel (described at the kernel).
 //
 // No atomics: every output element has one owner thread and every sum a fixed order that depends on the shapes alone, never
 // on T (an image is grid z), so results are bitwise reproducible and image i of a batch equals the same image alone.
@@ -51,6 +53,24 @@ constexpr int ESP_REINF_CO = 32;             // output channels a thread of k_es
 constexpr int ESP_UP_ROWS = 4;               // output rows a thread of k_esp_bilinear writes
 
 __device__ __forceinline__ float prelu(float v, float a) { return v > 0.0f ? v : a * v; }
+
+// The forms of the decoder tail's arithmetic, written out so that the dense kernels and k_esp_centres round alike (this file is
+// compiled with contraction on, and which product of (1 - l) p + l q the compiler fuses is its choice per site).
+// esp_norm      the epilogue of a pointwise conv: one fused multiply-add.
+// esp_lerp_fma  fma(1 - l, p, l q): the vertical blend of an x2 resize, and its row blend in columns 0 .. 2 of every four.
+// esp_lerp_sep  (1 - l) p + l q with both products rounded: the row blend in column 3 of every four.  That split is what the
+//               library has computed since the resize kernel took four columns a thread; the maps keep those bits.
+__device__ __forceinline__ float esp_norm(float acc, float scale, float shift) { return fmaf(acc, scale, shift); }
+__device__ __forceinline__ float esp_lerp_fma(float l, float p, float q) { return fmaf(1.0f - l, p, l * q); }
+__device__ __forceinline__ float esp_lerp_sep(float l, float p, float q) {
+#pragma clang fp contract(off)
+    const float a = (1.0f - l) * p, b = l * q;
+    return a + b;
+}
+// the row blend of output column x of an x2 resize (k_esp_bilinear<4>: a thread's columns are x0 .. x0 + 3, x0 a multiple of 4)
+__device__ __forceinline__ float esp_lerp_col(int x, float l, float p, float q) {
+    return (x & 3) == 3 ? esp_lerp_sep(l, p, q) : esp_lerp_fma(l, p, q);
+}
 
 template <bool ACT>
 __global__ __launch_bounds__(ESP_THREADS) void k_esp_pool(const float* __restrict__ in, size_t in_bs, int h, int w, float* out,
@@ -187,7 +207,7 @@ __global__ __launch_bounds__(ESP_THREADS) void k_esp_pw(const float* __restrict_
     for (int j = 0; j < CO_T; ++j) {
         if (j < nco) {
             const int co = co0 + j;
-            float v = acc[j] * scale[co] + shift[co];
+            float v = esp_norm(acc[j], scale[co], shift[co]);
             if (res) v += res[t * res_bs + (size_t)co * P + pix];
             out[t * out_bs + (size_t)co * P + pix] = prelu(v, slope[co]);
         }
@@ -264,7 +284,7 @@ __device__ __forceinline__ void esp_blend_row(const float* __restrict__ row, int
 #pragma unroll
         for (int i = 0; i < 4; ++i) p[i] = row[min(xa[0] + i, wi - 1)];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) h[j] = (1.0f - lx[j]) * esp_sel4(p, xa[j] - xa[0]) + lx[j] * esp_sel4(p, xb[j] - xa[0]);
+        for (int j = 0; j < 4; ++j) h[j] = esp_lerp_col(j, lx[j], esp_sel4(p, xa[j] - xa[0]), esp_sel4(p, xb[j] - xa[0]));
     } else {
 #pragma unroll
         for (int j = 0; j < VEC; ++j) h[j] = (1.0f - lx[j]) * row[xa[j]] + lx[j] * row[xb[j]];
@@ -308,7 +328,13 @@ __global__ __launch_bounds__(ESP_THREADS) void k_esp_bilinear(const float* __res
         }
         float v[VEC];
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) v[j] = (1.0f - ly) * ha[j] + ly * (y1 == ra ? ha[j] : hb[j]);
+        for (int j = 0; j < VEC; ++j) {
+            const float lo = y1 == ra ? ha[j] : hb[j];
+            if constexpr (VEC == 4)
+                v[j] = esp_lerp_fma(ly, ha[j], lo);
+            else
+                v[j] = (1.0f - ly) * ha[j] + ly * lo;
+        }
         float* o = out + (size_t)blockIdx.z * out_bs + ((size_t)c * ho + y) * wo + x0;
         if constexpr (VEC == 4)
             *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
@@ -345,6 +371,134 @@ __global__ __launch_bounds__(ESP_THREADS) void k_esp_psp_up(const float* __restr
     const float top = (1.0f - lx) * esp_dw3(p, hp, wp, y0, xa, w9) + lx * esp_dw3(p, hp, wp, y0, xb, w9);
     const float bot = (1.0f - lx) * esp_dw3(p, hp, wp, y1, xa, w9) + lx * esp_dw3(p, hp, wp, y1, xb, w9);
     out[(size_t)blockIdx.z * out_bs + (size_t)c * h * w + idx] = (1.0f - ly) * top + ly * bot;
+}
+
+// ---- the decoder tail at single pixels (tmpnn_espnet_centres) ---------------------------------------------------------------
+// Everything behind m3 is pointwise convs and x2 resizes, so output pixel (y, x) needs m1 at <= 2 x 2 pixels, m2 at <= 3 x 3 and
+// m3 at the taps of those.  One workgroup per requested pixel:
+//   1  xs [64 + C][12]  cat[out_l2, up(m3)] at the 3 x 3 pixels of level 2 from (by, bx) on (9 of a row of 12 floats: a lane reads
+//                       its k's nine values as three 16-byte words), the upper half blended from m3
+//   2  ms [9][C]        project_l2 at those pixels
+//   3  xs [32 + C][4]   cat[out_l1, up(m2)] at the 2 x 2 pixels of level 1, the upper half blended from ms
+//   4  m1s [4][C]       project_l1 at those pixels
+//   5  logits[d][c]     the final blend
+// Every sum is the chain of k_esp_pw (acc = 0, fmaf over k ascending, source a then b) and every epilogue and blend the helper
+// the dense kernels use, with the column of the dense resize that would have written the pixel, so the values equal the dense
+// map's bit for bit.  A conv gives lane c output channel c and all staged pixels: the pixels are independent accumulators, the
+// weight row wt[k][.] one coalesced load, and the loop holds no branch, so eight weight loads are in flight.
+// LDS: 320 x 12 + 9 x 256 floats = 24 576 bytes for every C (stages 3 and 4 reuse the first array).
+constexpr int ESPC_MAX_C = 256;              // channels a workgroup of ESP_THREADS lanes serves
+constexpr int ESPC_N2 = 9, ESPC_S2 = 12;     // pixels staged at level 2 and the floats of their row in xs
+constexpr int ESPC_N1 = 4;                   // pixels staged at level 1
+constexpr int ESPC_XS = (64 + ESPC_MAX_C) * ESPC_S2;
+constexpr int ESPC_M1 = (32 + ESPC_MAX_C) * ESPC_N1;          // m1s starts here, behind the staged input of stage 4
+static_assert(ESPC_M1 + ESPC_N1 * ESPC_MAX_C <= ESPC_XS && ESPC_MAX_C <= ESP_THREADS, "stage 4 fits the first array; a lane a channel");
+
+struct EspTail {
+    const float *l1, *l2, *m3;                                 // [T][32][h2][w2], [T][64][h4][w4], [T][C][h8][w8]
+    const float *w2, *scale2, *shift2, *slope2;                // project_l2: wt [64 + C][C]
+    const float *w1, *scale1, *shift1, *slope1;                // project_l1: wt [32 + C][C]
+};
+
+// out[p][c] = prelu(norm(sum_k xs[k][p] wt[k][c])) for the NP pixels staged in xs ([cin][NS]); out is [NP][C]; lane c < C
+template <int NP, int NS>
+__device__ __forceinline__ void espc_conv(const float* xs, int cin, int C, int c, const float* __restrict__ wt,
+                                          const float* __restrict__ scale, const float* __restrict__ shift,
+                                          const float* __restrict__ slope, float* out) {
+    float acc[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) acc[j] = 0.0f;
+#pragma unroll 8
+    for (int k = 0; k < cin; ++k) {
+        const float w = wt[(size_t)k * C + c];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) acc[j] = fmaf(xs[k * NS + j], w, acc[j]);
+    }
+    const float sc = scale[c], sh = shift[c], sl = slope[c];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) out[j * C + c] = prelu(esp_norm(acc[j], sc, sh), sl);
+}
+
+// the value of an x2 resize (hi x wi -> 2 hi x 2 wi) at output (y, x), as k_esp_bilinear<4> forms it; src(yy, xx) reads the source
+template <class Src>
+__device__ __forceinline__ float espc_up(int y, int x, int hi, int wi, Src src) {
+    int y0, y1, x0, x1;
+    float ly, lx;
+    esp_axis(y, hi, 2 * hi, y0, y1, ly);
+    esp_axis(x, wi, 2 * wi, x0, x1, lx);
+    const float top = esp_lerp_col(x, lx, src(y0, x0), src(y0, x1));
+    const float bot = esp_lerp_col(x, lx, src(y1, x0), src(y1, x1));
+    return esp_lerp_fma(ly, top, bot);
+}
+
+__global__ __launch_bounds__(ESP_THREADS) void k_esp_centres(EspTail a, int C, int T, int H, int W, const int32_t* __restrict__ pix,
+                                                             float* __restrict__ logits, int32_t* __restrict__ flags) {
+    __shared__ __align__(16) float xs[ESPC_XS];
+    __shared__ __align__(16) float ms[ESPC_N2 * ESPC_MAX_C];
+    const int d = blockIdx.x, tid = threadIdx.x;
+    const int h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, h8 = H / 8, w8 = W / 8;
+    const int plane = H * W;                                                // (T H W < 2^31: the host check)
+    int px = pix[d];
+    const bool bad = px < 0 || px >= T * plane;
+    px = px < 0 ? 0 : (px >= T * plane ? T * plane - 1 : px);
+    if (tid == 0) flags[d] = bad ? 1 : 0;
+    const int t = px / plane, rem = px - t * plane, y = rem / W, x = rem - y * W;
+    // level 1: the 2 x 2 pixels (ya0 | ya1, xa0 | xa1) of m1 under (y, x); level 2: the 3 x 3 pixels of m2 from (by, bx) on under those
+    int ya0, ya1, xa0, xa1, by, bx, unused;
+    float lya, lxa, lam;
+    esp_axis(y, h2, H, ya0, ya1, lya);
+    esp_axis(x, w2, W, xa0, xa1, lxa);
+    esp_axis(ya0, h4, h2, by, unused, lam);
+    esp_axis(xa0, w4, w2, bx, unused, lam);
+
+    // 1: cat[out_l2, up(m3)] at level-2 pixel (min(by + r, h4 - 1), min(bx + q, w4 - 1)), p = 3 r + q
+    {
+        const float* l2 = a.l2 + (size_t)t * 64 * h4 * w4;
+        const float* m3 = a.m3 + (size_t)t * C * h8 * w8;
+#pragma unroll 3
+        for (int i = tid; i < 64 * ESPC_N2; i += ESP_THREADS) {
+            const int k = i / ESPC_N2, p = i - k * ESPC_N2, r = p / 3, q = p - 3 * r;
+            xs[k * ESPC_S2 + p] = l2[((size_t)k * h4 + min(by + r, h4 - 1)) * w4 + min(bx + q, w4 - 1)];
+        }
+#pragma unroll 2
+        for (int i = tid; i < C * ESPC_N2; i += ESP_THREADS) {
+            const int c = i / ESPC_N2, p = i - c * ESPC_N2, r = p / 3, q = p - 3 * r;
+            const float* src = m3 + (size_t)c * h8 * w8;
+            xs[(64 + c) * ESPC_S2 + p] =
+                espc_up(min(by + r, h4 - 1), min(bx + q, w4 - 1), h8, w8, [&](int yy, int xx) { return src[yy * w8 + xx]; });
+        }
+    }
+    __syncthreads();
+    // 2: project_l2
+    if (tid < C) espc_conv<ESPC_N2, ESPC_S2>(xs, 64 + C, C, tid, a.w2, a.scale2, a.shift2, a.slope2, ms);
+    __syncthreads();
+    // 3: cat[out_l1, up(m2)] at level-1 pixel (ya0 or ya1, xa0 or xa1), p = 2 r + q; the taps of m2 lie in the staged 3 x 3
+    {
+        const float* l1 = a.l1 + (size_t)t * 32 * h2 * w2;
+        for (int i = tid; i < 32 * ESPC_N1; i += ESP_THREADS) {
+            const int k = i / ESPC_N1, p = i - k * ESPC_N1;
+            xs[i] = l1[((size_t)k * h2 + ((p >> 1) ? ya1 : ya0)) * w2 + ((p & 1) ? xa1 : xa0)];
+        }
+        for (int i = tid; i < C * ESPC_N1; i += ESP_THREADS) {
+            const int c = i / ESPC_N1, p = i - c * ESPC_N1;
+            const float* src = ms + c;
+            xs[32 * ESPC_N1 + i] = espc_up((p >> 1) ? ya1 : ya0, (p & 1) ? xa1 : xa0, h4, w4, [&](int yy, int xx) {
+                const int ry = min(max(yy - by, 0), 2), rx = min(max(xx - bx, 0), 2);      // (0 .. 2 by construction; never outside ms)
+                return src[(ry * 3 + rx) * C];
+            });
+        }
+    }
+    __syncthreads();
+    // 4: project_l1 (no norm, no activation: scale 1, shift 0, slopes 1 in the arena, applied as the dense kernel applies them)
+    float* m1s = xs + ESPC_M1;
+    if (tid < C) espc_conv<ESPC_N1, ESPC_N1>(xs, 32 + C, C, tid, a.w1, a.scale1, a.shift1, a.slope1, m1s);
+    __syncthreads();
+    // 5: the final x2 resize at (y, x)
+    if (tid < C) {
+        const float top = esp_lerp_col(x, lxa, m1s[tid], m1s[C + tid]);
+        const float bot = esp_lerp_col(x, lxa, m1s[2 * C + tid], m1s[3 * C + tid]);
+        logits[(size_t)d * C + tid] = esp_lerp_fma(lya, top, bot);
+    }
 }
 
 // ---- the weight arena (include/tmpnn.h documents the order; trackmpnn_amd/espnet.py packs it) -------------------------------
@@ -418,7 +572,9 @@ struct Ws {
     float *img2, *img4, *img8, *img16, *l1, *l2, *l3a, *l3b, *l4a, *l4b, *red, *cat, *p4, *up4, *psp, *pool_a, *pool_b, *pspo, *m3,
         *up3, *m2, *up2, *m1;
 };
-size_t walk_ws(void* base, int T, int H, int W, int C, Ws& s) {
+// tail = false: without the four maps of the dense decoder tail (up3, m2, up2, m1), which are carved last, so the trunk's arrays lie
+// at the same offsets in both layouts
+size_t walk_ws(void* base, int T, int H, int W, int C, Ws& s, bool tail = true) {
     WsCarver cv{reinterpret_cast<char*>(base)};
     const size_t t = (size_t)T, P2 = (size_t)(H / 2) * (W / 2), P4 = P2 / 4, P8 = P4 / 4, P16 = P8 / 4;
     const size_t Pp = (size_t)((H / 8 + 1) / 2) * ((W / 8 + 1) / 2);
@@ -433,8 +589,12 @@ size_t walk_ws(void* base, int T, int H, int W, int C, Ws& s) {
     s.psp = cv.take<float>(t * 5 * ESP_PSP * P8);
     s.pool_a = cv.take<float>(t * ESP_PSP * Pp), s.pool_b = cv.take<float>(t * ESP_PSP * Pp);
     s.pspo = cv.take<float>(t * ESP_PSP * P8);
-    s.m3 = cv.take<float>(t * C * P8), s.up3 = cv.take<float>(t * C * P4), s.m2 = cv.take<float>(t * C * P4);
-    s.up2 = cv.take<float>(t * C * P2), s.m1 = cv.take<float>(t * C * P2);
+    s.m3 = cv.take<float>(t * C * P8);
+    s.up3 = s.m2 = s.up2 = s.m1 = nullptr;
+    if (tail) {
+        s.up3 = cv.take<float>(t * C * P4), s.m2 = cv.take<float>(t * C * P4);
+        s.up2 = cv.take<float>(t * C * P2), s.m1 = cv.take<float>(t * C * P2);
+    }
     return (size_t)(cv.p - reinterpret_cast<char*>(base));
 }
 
@@ -547,34 +707,19 @@ bool shape_ok(int T, int H, int W, int C) {
            (int64_t)std::max(C, 160) * H * W < ((int64_t)1 << 31);
 }
 
-}  // namespace
-
-extern "C" size_t tmpnn_espnet_arena_floats(int C) {
-    if (C < 1 || C > ESP_MAX_C) return 0;
-    Net n;
-    return walk_arena(nullptr, C, n);
-}
-
-extern "C" size_t tmpnn_espnet_ws_bytes(int T, int H, int W, int C) {
-    if (!shape_ok(T, H, W, C)) return 0;
-    Ws s;
-    return walk_ws(nullptr, T, H, W, C, s);
-}
-
-extern "C" int tmpnn_espnet_fwd(const float* arena, int C, const float* images, int T, int H, int W, void* ws, size_t ws_bytes, float* out,
-                                tmpnn_stream stream) {
-    TM_REQUIRE(arena != nullptr && images != nullptr && ws != nullptr && out != nullptr, "espnet_fwd: null pointer (arena, images, ws, out)");
-    TM_REQUIRE(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "espnet_fwd: H=%d W=%d (positive multiples of 16)", H, W);
-    TM_REQUIRE(shape_ok(T, H, W, C), "espnet_fwd: T=%d C=%d H=%d W=%d (1 <= T <= %d, 1 <= C <= %d, max(C, 160) H W < 2^31)", T, C, H, W,
+// the host checks every entry point shares; `who` names the caller in the message
+int check_call(const char* who, const void* arena, const void* images, const void* ws, const void* out, int T, int H, int W, int C) {
+    TM_REQUIRE(arena != nullptr && images != nullptr && ws != nullptr && out != nullptr, "%s: null pointer (arena, images, ws, out)", who);
+    TM_REQUIRE(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "%s: H=%d W=%d (positive multiples of 16)", who, H, W);
+    TM_REQUIRE(shape_ok(T, H, W, C), "%s: T=%d C=%d H=%d W=%d (1 <= T <= %d, 1 <= C <= %d, max(C, 160) H W < 2^31)", who, T, C, H, W,
                ESP_MAX_T, ESP_MAX_C);
-    TM_REQUIRE(aligned16(arena) && aligned16(images) && aligned16(ws) && aligned16(out), "espnet_fwd: pointers must be 16-byte aligned");
-    Net n;
-    walk_arena(arena, C, n);
-    Ws s;
-    const size_t need = walk_ws(ws, T, H, W, C, s);
-    if (ws_bytes < need) return set_error(TMPNN_EWORKSPACE, "espnet_fwd: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    TM_REQUIRE(aligned16(arena) && aligned16(images) && aligned16(ws) && aligned16(out), "%s: pointers must be 16-byte aligned", who);
+    return TMPNN_OK;
+}
 
-    Run r{as_stream(stream), T, 0};
+// The trunk: every launch of the forward up to and including m3 (65), shared by tmpnn_espnet_fwd and tmpnn_espnet_trunk.
+int run_trunk(const Net& n, const Ws& s, const float* images, int T, int H, int W, int C, hipStream_t st) {
+    Run r{st, T, 0};
     const int h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, h8 = H / 8, w8 = W / 8, h16 = H / 16, w16 = W / 16;
     const size_t P2 = (size_t)h2 * w2, P4 = (size_t)h4 * w4, P8 = (size_t)h8 * w8, P16 = (size_t)h16 * w16;
     // the image pyramid every DownSampler's reinforcement reads (the reference pools the full image again in each of them)
@@ -625,10 +770,78 @@ extern "C" int tmpnn_espnet_fwd(const float* arena, int C, const float* images, 
     }
     run_pw(r, n.psp_proj, s.psp, psp_bs, 5 * ESP_PSP, nullptr, 0, (int)P8, nullptr, 0, s.pspo, ESP_PSP * P8);
     run_pw(r, n.proj3, s.pspo, ESP_PSP * P8, ESP_PSP, nullptr, 0, (int)P8, nullptr, 0, s.m3, C * P8);
+    return r.rc;
+}
+
+}  // namespace
+
+extern "C" size_t tmpnn_espnet_arena_floats(int C) {
+    if (C < 1 || C > ESP_MAX_C) return 0;
+    Net n;
+    return walk_arena(nullptr, C, n);
+}
+
+extern "C" size_t tmpnn_espnet_ws_bytes(int T, int H, int W, int C) {
+    if (!shape_ok(T, H, W, C)) return 0;
+    Ws s;
+    return walk_ws(nullptr, T, H, W, C, s);
+}
+
+extern "C" size_t tmpnn_espnet_centres_ws_bytes(int T, int H, int W, int C) {
+    if (!shape_ok(T, H, W, C)) return 0;
+    Ws s;
+    return walk_ws(nullptr, T, H, W, C, s, false);
+}
+
+extern "C" int tmpnn_espnet_fwd(const float* arena, int C, const float* images, int T, int H, int W, void* ws, size_t ws_bytes, float* out,
+                                tmpnn_stream stream) {
+    if (int rc = check_call("espnet_fwd", arena, images, ws, out, T, H, W, C)) return rc;
+    Net n;
+    walk_arena(arena, C, n);
+    Ws s;
+    const size_t need = walk_ws(ws, T, H, W, C, s);
+    if (ws_bytes < need) return set_error(TMPNN_EWORKSPACE, "espnet_fwd: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    if (int rc = run_trunk(n, s, images, T, H, W, C, as_stream(stream))) return rc;
+    Run r{as_stream(stream), T, 0};
+    const int h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, h8 = H / 8, w8 = W / 8;
+    const size_t P2 = (size_t)h2 * w2, P4 = (size_t)h4 * w4, P8 = (size_t)h8 * w8;
     run_bilinear(r, s.m3, C * P8, C, h8, w8, s.up3, C * P4, h4, w4);
     run_pw(r, n.proj2, s.l2, 64 * P4, 64, s.up3, C * P4, (int)P4, nullptr, 0, s.m2, C * P4);
     run_bilinear(r, s.m2, C * P4, C, h4, w4, s.up2, C * P2, h2, w2);
     run_pw(r, n.proj1, s.l1, 32 * P2, 32, s.up2, C * P2, (int)P2, nullptr, 0, s.m1, C * P2);
     run_bilinear(r, s.m1, C * P2, C, h2, w2, out, (size_t)C * H * W, H, W);
     return r.rc;
+}
+
+extern "C" int tmpnn_espnet_trunk(const float* arena, int C, const float* images, int T, int H, int W, void* ws, size_t ws_bytes,
+                                  tmpnn_stream stream) {
+    if (int rc = check_call("espnet_trunk", arena, images, ws, ws, T, H, W, C)) return rc;
+    Net n;
+    walk_arena(arena, C, n);
+    Ws s;
+    const size_t need = walk_ws(ws, T, H, W, C, s, false);
+    if (ws_bytes < need) return set_error(TMPNN_EWORKSPACE, "espnet_trunk: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    return run_trunk(n, s, images, T, H, W, C, as_stream(stream));
+}
+
+extern "C" int tmpnn_espnet_centres(const float* arena, int C, int T, int H, int W, const void* ws, size_t ws_bytes, const int32_t* pix,
+                                    int D, float* logits, int32_t* flags, tmpnn_stream stream) {
+    TM_REQUIRE(D >= 0, "espnet_centres: D=%d", D);
+    TM_REQUIRE(arena != nullptr && ws != nullptr && (D == 0 || (pix != nullptr && logits != nullptr && flags != nullptr)),
+               "espnet_centres: null pointer (arena, ws, pix, logits, flags)");
+    TM_REQUIRE(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "espnet_centres: H=%d W=%d (positive multiples of 16)", H, W);
+    TM_REQUIRE(shape_ok(T, H, W, C) && (int64_t)T * H * W < ((int64_t)1 << 31), "espnet_centres: T=%d C=%d H=%d W=%d (a shape "
+               "tmpnn_espnet_trunk takes, T H W < 2^31)", T, C, H, W);
+    TM_REQUIRE(C <= ESPC_MAX_C, "espnet_centres: C=%d (1 .. %d; wider nets take the dense call, tmpnn_espnet_fwd)", C, ESPC_MAX_C);
+    TM_REQUIRE(aligned16(arena) && aligned16(ws), "espnet_centres: arena and ws must be 16-byte aligned");
+    Net n;
+    walk_arena(arena, C, n);
+    Ws s;
+    const size_t need = walk_ws(const_cast<void*>(ws), T, H, W, C, s, false);
+    if (ws_bytes < need) return set_error(TMPNN_EWORKSPACE, "espnet_centres: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    if (D == 0) return TMPNN_OK;
+    const EspTail a{s.l1, s.l2, s.m3, n.proj2.wt, n.proj2.scale, n.proj2.shift, n.proj2.slope,
+                    n.proj1.wt, n.proj1.scale, n.proj1.shift, n.proj1.slope};
+    k_esp_centres<<<dim3((unsigned)D), ESP_THREADS, 0, as_stream(stream)>>>(a, C, T, H, W, pix, logits, flags);
+    return check_launch("espnet_centres");
 }

@@ -1,4 +1,5 @@
-// The visual head on the device (tmpnn_vis_head_fwd, tmpnn_vis_head_bwd; include/tmpnn.h; host definition:
+// The visual head on the device (tmpnn_vis_head_fwd, tmpnn_vis_head_bwd, tmpnn_vis_head_pixels, tmpnn_vis_head_rows_from_logits;
+// include/tmpnn.h; host definition:
 // trackmpnn_amd.vishead.vis_head_host).  The reference reads the embedding CNN's map at every box centre in a Python loop with one
 // indexing kernel per detection (dataset/kitti_mot.py:391-412), then torch.cat, F.softmax and the standardisation (:558-566), and
 // for training a np.vectorize label map and nn.CrossEntropyLoss (models/loss.py:162-181).
@@ -7,6 +8,10 @@
 //               logits, the wave's maximum and sum of exponentials by xor butterflies (every lane ends with the same bits), the
 //               standardised softmax row into the caller's rows at its own stride and column, the contiguous logits, and per row
 //               the (maximum, sum) pair, the negative log-likelihood of its label, the pixel and the flags.
+// k_vis_pixels, k_vis_rows_logits   the same head behind a CNN that answers per pixel (tmpnn_espnet_centres): the pixels and flags
+//               alone, a thread per row; then, over logits the caller gathered at them, the rows by k_vis_fwd's own code (vh_row)
+//               and, in one more workgroup, the one chunk's counts by k_vis_reduce's (vh_chunk).  They live here because this file
+//               is built with contraction off: the centre rule and the softmax stay the arithmetic of k_vis_fwd.
 // k_vis_reduce  one wave per chunk: lanes walk the chunk's rows in strides of 64 and a butterfly adds the 64 partial sums, so the
 //               order of the additions depends on the chunk's bounds alone.  loss[b], the counts, and per row its chunk and its
 //               scatter key (the pixel of a labelled row, -1 otherwise).
@@ -61,30 +66,29 @@ __device__ __forceinline__ int wave_sum(int v) {
     return v;
 }
 
-__global__ __launch_bounds__(VH_THREADS) void k_vis_fwd(tmpnn_vis_head a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t d = (int64_t)blockIdx.x * VH_WAVES + (threadIdx.x >> 6);     // (wave-uniform)
-    if (d >= a.D) return;
+// the pixel row d reads: the centre rule, the clamps and the flags (k_vis_fwd and k_vis_pixels)
+__device__ __forceinline__ int32_t vh_pixel(const tmpnn_vis_head& a, int64_t d, int& m, int64_t& inmap, int& fl) {
     const float x1 = a.box[4 * d], y1 = a.box[4 * d + 1], x2 = a.box[4 * d + 2], y2 = a.box[4 * d + 3];
     const float im_h = a.im_hw ? a.im_hw[2 * d] : a.im_h, im_w = a.im_hw ? a.im_hw[2 * d + 1] : a.im_w;
     bool clamped = false;
     const int cx = vh_centre(x1, x2, a.input_w, im_w, a.down_ratio, a.Wm, clamped);
     const int cy = vh_centre(y1, y2, a.input_h, im_h, a.down_ratio, a.Hm, clamped);
-    int m = a.map_of[d];
-    int fl = clamped ? VH_CLAMPED : 0;
+    m = a.map_of[d];
+    fl = clamped ? VH_CLAMPED : 0;
     if (m < 0 || m >= a.T) { m = 0; fl |= VH_BADMAP; }
-    const int64_t plane = (int64_t)a.Hm * a.Wm;
-    const int64_t inmap = (int64_t)cy * a.Wm + cx;                              // < plane
-    const float* src = a.maps + (int64_t)m * VH_C * plane + inmap;
-    const float v0 = src[(int64_t)lane * plane], v1 = src[(int64_t)(lane + 64) * plane];
+    inmap = (int64_t)cy * a.Wm + cx;                                            // < plane
+    return (int32_t)((int64_t)m * a.Hm * a.Wm + inmap);
+}
+
+// a wave's row from its two logits a lane (k_vis_fwd and k_vis_rows_logits): maximum, exponentials, sum, the standardised
+// softmax into the caller's rows, the (maximum, sum) pair and the row's negative log-likelihood
+__device__ __forceinline__ void vh_row(const tmpnn_vis_head& a, int64_t d, int lane, float v0, float v1) {
     const float mx = wave_max(fmaxf(v0, v1));
     const float e0 = expf(v0 - mx), e1 = expf(v1 - mx);
     const float s = wave_sum(e0 + e1);
     float* row = a.rows + d * (int64_t)a.ld_rows + a.col;
     row[lane] = (e0 / s - a.mean[lane]) / a.std[lane];
     row[lane + 64] = (e1 / s - a.mean[lane + 64]) / a.std[lane + 64];
-    a.logits[d * VH_C + lane] = v0;
-    a.logits[d * VH_C + lane + 64] = v1;
     const int tr = a.track ? a.track[d] : -1;
     float nll = 0.0f;
     if (tr >= 0) {                                                              // (wave-uniform)
@@ -96,17 +100,41 @@ __global__ __launch_bounds__(VH_THREADS) void k_vis_fwd(tmpnn_vis_head a) {
         a.stat[2 * d] = mx;
         a.stat[2 * d + 1] = s;
         a.nll[d] = nll;
-        a.pix[d] = (int32_t)((int64_t)m * plane + inmap);
+    }
+}
+
+__global__ __launch_bounds__(VH_THREADS) void k_vis_fwd(tmpnn_vis_head a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t d = (int64_t)blockIdx.x * VH_WAVES + (threadIdx.x >> 6);     // (wave-uniform)
+    if (d >= a.D) return;
+    int m, fl;
+    int64_t inmap;
+    const int32_t px = vh_pixel(a, d, m, inmap, fl);
+    const int64_t plane = (int64_t)a.Hm * a.Wm;
+    const float* src = a.maps + (int64_t)m * VH_C * plane + inmap;
+    const float v0 = src[(int64_t)lane * plane], v1 = src[(int64_t)(lane + 64) * plane];
+    vh_row(a, d, lane, v0, v1);
+    a.logits[d * VH_C + lane] = v0;
+    a.logits[d * VH_C + lane + 64] = v1;
+    if (lane == 0) {
+        a.pix[d] = px;
         a.flag[d] = fl;
         a.chunk_of[d] = -1;
         a.key[d] = -1;
     }
 }
 
-__global__ __launch_bounds__(VH_THREADS) void k_vis_reduce(tmpnn_vis_head a) {
-    const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * VH_WAVES + (threadIdx.x >> 6);
-    if (b >= a.B) return;
+// the pixel and the flags of every row alone, a thread per row (tmpnn_vis_head_pixels): what a per-centre CNN is asked for
+__global__ __launch_bounds__(VH_THREADS) void k_vis_pixels(tmpnn_vis_head a) {
+    const int64_t d = (int64_t)blockIdx.x * VH_THREADS + threadIdx.x;
+    if (d >= a.D) return;
+    int m, fl;
+    int64_t inmap;
+    a.pix[d] = vh_pixel(a, d, m, inmap, fl);
+    a.flag[d] = fl;
+}
+
+__device__ __forceinline__ void vh_chunk(const tmpnn_vis_head& a, int b, int lane) {
     int64_t lo = 0, hi = a.D;
     int bad = 0;
     if (a.offsets) {
@@ -140,6 +168,28 @@ __global__ __launch_bounds__(VH_THREADS) void k_vis_reduce(tmpnn_vis_head a) {
         a.count[4 * b + 2] = n_bad + bad;
         a.count[4 * b + 3] = (int32_t)(hi - lo);
     }
+}
+
+__global__ __launch_bounds__(VH_THREADS) void k_vis_reduce(tmpnn_vis_head a) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * VH_WAVES + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    vh_chunk(a, b, lane);
+}
+
+// Rows from logits that are already gathered (tmpnn_vis_head_rows_from_logits; inference: no track, one chunk): a wave per row
+// runs vh_row over a.logits; the first wave of one more workgroup is the chunk's k_vis_reduce -- it reads the flags of the
+// launch before (k_vis_pixels) and no nll, and writes chunk_of and key, which the row waves leave alone.
+__global__ __launch_bounds__(VH_THREADS) void k_vis_rows_logits(tmpnn_vis_head a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row_blocks = (a.D + VH_WAVES - 1) / VH_WAVES;
+    if ((int64_t)blockIdx.x >= row_blocks) {
+        if ((threadIdx.x >> 6) == 0) vh_chunk(a, 0, lane);
+        return;
+    }
+    const int64_t d = (int64_t)blockIdx.x * VH_WAVES + (threadIdx.x >> 6);     // (wave-uniform)
+    if (d >= a.D) return;
+    vh_row(a, d, lane, a.logits[d * VH_C + lane], a.logits[d * VH_C + lane + 64]);
 }
 
 __global__ __launch_bounds__(VH_THREADS) void k_vis_bwd(tmpnn_vis_head a, const float* __restrict__ g, float* __restrict__ dmaps) {
@@ -208,7 +258,7 @@ __global__ __launch_bounds__(VH_THREADS) void k_vis_scatter(tmpnn_vis_head a, co
     dst[(int64_t)(lane + 64) * plane] = acc1;
 }
 
-int check_args(const tmpnn_vis_head* a, const char* who) {
+int check_args(const tmpnn_vis_head* a, const char* who, bool need_maps = true) {
     TM_REQUIRE(a != nullptr, "%s: the call struct is null", who);
     TM_REQUIRE(a->T >= 1 && a->Hm >= 1 && a->Wm >= 1 && (int64_t)a->T * a->Hm * a->Wm < 0x7fffffffLL, "%s: maps of %d x %d x %d pixels "
                "(T * Hm * Wm must fit in int32)", who, a->T, a->Hm, a->Wm);
@@ -219,7 +269,7 @@ int check_args(const tmpnn_vis_head* a, const char* who) {
     TM_REQUIRE(a->im_hw != nullptr || (a->im_h > 0.0f && a->im_h <= 3.0e38f && a->im_w > 0.0f && a->im_w <= 3.0e38f),
                "%s: im_hw is null and im_h, im_w are not finite and positive", who);
     TM_REQUIRE(a->col >= 0 && a->ld_rows >= VH_C && a->col <= a->ld_rows - VH_C, "%s: col=%d ld_rows=%d", who, a->col, a->ld_rows);
-    TM_REQUIRE(a->maps && a->mean && a->std && a->loss && a->count, "%s: null maps, mean, std, loss or count", who);
+    TM_REQUIRE((a->maps || !need_maps) && a->mean && a->std && a->loss && a->count, "%s: null maps, mean, std, loss or count", who);
     TM_REQUIRE(a->offsets != nullptr || a->B == 1, "%s: offsets is null with B=%d", who, a->B);
     TM_REQUIRE(a->D == 0 || (a->box && a->map_of && a->rows && a->logits && a->stat && a->nll && a->pix && a->flag && a->chunk_of && a->key),
                "%s: null per-detection arrays", who);
@@ -263,4 +313,19 @@ extern "C" int tmpnn_vis_head_scatter(const tmpnn_vis_head* a, const float* d_lo
         if (int rc = check_launch("vis_head_scatter")) return rc;
     }
     return TMPNN_OK;
+}
+
+extern "C" int tmpnn_vis_head_pixels(const tmpnn_vis_head* a, tmpnn_stream stream) {
+    if (int rc = check_args(a, "vis_head_pixels", false)) return rc;
+    if (a->D == 0) return TMPNN_OK;
+    hipLaunchKernelGGL(k_vis_pixels, dim3((unsigned)ceil_div(a->D, VH_THREADS)), dim3(VH_THREADS), 0, as_stream(stream), *a);
+    return check_launch("vis_head_pixels");
+}
+
+extern "C" int tmpnn_vis_head_rows_from_logits(const tmpnn_vis_head* a, tmpnn_stream stream) {
+    if (int rc = check_args(a, "vis_head_rows_from_logits", false)) return rc;
+    TM_REQUIRE(a->track == nullptr && a->offsets == nullptr && a->B == 1, "vis_head_rows_from_logits: inference only (track and offsets "
+               "NULL, B = 1); a loss takes tmpnn_vis_head_fwd over the dense maps");
+    hipLaunchKernelGGL(k_vis_rows_logits, dim3((unsigned)ceil_div(a->D, VH_WAVES) + 1), dim3(VH_THREADS), 0, as_stream(stream), *a);
+    return check_launch("vis_head_rows_from_logits");
 }

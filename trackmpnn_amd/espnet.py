@@ -7,6 +7,18 @@
     pack_arena(sd, C)       the float32 weight arena of the device (layout: include/tmpnn.h, struct-free: one array)
     EspEmbedNet             the same forward on the device (tmpnn_espnet_fwd; csrc/espnet.hip): `net(images) -> maps`, drops in
                             wherever an `embed_net` is taken (OnlineVis, VisInference, SequenceFeatures.attach_vis)
+    espnet_centres_host(sd, images, pix)    espnet_host(...)[t, :, cy, cx] for pix = (t H + cy) W + cx: the DEFINITION of
+                            what the net answers at single pixels
+    EspCentres              `net.centres(images)`: the net run up to its C-channel map at 1/8 size (tmpnn_espnet_trunk), and
+                            `.logits_at(pix)` the rest of the decoder at the pixels asked for (tmpnn_espnet_centres), equal bit
+                            for bit to the dense map there
+
+The sparse path.  VisHead reads one pixel per detection, and everything behind the 1/8-size map is pointwise convs and x2 bilinear
+steps: one output pixel depends on 2 x 2 pixels of merge_l1, 3 x 3 of merge_l2 and their taps at 1/8 size.  So for inference
+`EspEmbedNet.from_state_dict(sd, device, centres=True)` makes `net(images)` return an EspCentres in the map's place, which
+VisHead.rows takes as it takes the map; the dense tail's five launches, their four workspace maps (2 C (P4 + P2) floats an image)
+and the [T, C, H, W] result are not made.  Training through VisHead.forward keeps the dense map (its backward hands d(maps) to a
+torch CNN).
 
 The net.  Encoder (widths 32 / 64 / 128 / 256 at 1/2, 1/4, 1/8, 1/16 of the input):
     level1      3x3 stride-2 conv 3 -> 32, BN, PReLU
@@ -43,6 +55,7 @@ from . import _lib
 BN_EPS = 1e-5
 _BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')
 _PSP = 128
+MAX_CENTRES_C = 256            # channels the per-centre tail serves (csrc/espnet.hip ESPC_MAX_C)
 
 
 def _dilations(r_lim: int) -> Tuple[int, ...]:
@@ -224,6 +237,19 @@ def espnet_host(sd, images, dtype=torch.float64, taps: bool = False):
     return out
 
 
+def espnet_centres_host(sd, images, pix, dtype=torch.float64):
+    """logits [D, C] in `dtype`: espnet_host(sd, images, dtype)[t, :, cy, cx] for every pix = (t H + cy) W + cx in [0, T H W).
+    The definition of EspCentres.logits_at."""
+    out = espnet_host(sd, images, dtype)
+    T, _, H, W = (int(v) for v in out.shape)
+    px = torch.as_tensor(np.asarray(pix.detach().cpu().numpy() if isinstance(pix, torch.Tensor) else pix, dtype=np.int64).ravel())
+    if px.numel() and (int(px.min()) < 0 or int(px.max()) >= T * H * W):
+        raise ValueError(f'espnet_centres_host: a pix outside [0, {T * H * W})')
+    px = px.to(out.device)
+    t, rem = px // (H * W), px % (H * W)
+    return out[t, :, rem // W, rem % W]
+
+
 def _check_hw(H: int, W: int) -> None:
     if H <= 0 or W <= 0 or H % 16 or W % 16:
         raise ValueError(f'espnet: images of {H} x {W}; H and W must be positive multiples of 16 (the decoder concatenates maps '
@@ -320,12 +346,17 @@ class EspEmbedNet:
     No autograd graph is built.  The workspace of a (T, H, W) is allocated at its first call and reused; a call then allocates
     nothing but its result (nothing at all with `out`), waits for nothing and reads nothing back; every launch goes on the
     current stream and their number (70) does not depend on T.  Results are bitwise reproducible, and image i of a batch gives
-    the same bits for every T.  The net is an eval-mode network: `training` is False, eval() and train(False) return it,
+    the same bits for every T.
+
+        h = net.centres(images)                         the trunk alone (65 launches); h.logits_at(pix) -> ([D, C], flags [D])
+        net = EspEmbedNet.from_state_dict(sd, dev, centres=True)       net(images) returns that handle (inference behind VisHead)
+  The net is an eval-mode network: `training` is False, eval() and train(False) return it,
     train(True) raises."""
 
     training = False
+    _sparse = False              # centres=True: __call__ returns centres(images)
 
-    def __init__(self, sd, device='cuda:0'):
+    def __init__(self, sd, device='cuda:0', centres: bool = False):
         dev = torch.device(device)
         if dev.type != 'cuda':
             raise RuntimeError(f'EspEmbedNet on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a cuda '
@@ -339,10 +370,15 @@ class EspEmbedNet:
         self._arena = torch.from_numpy(arena).to(dev)
         self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
         self._fwd = _lib.fn('tmpnn_espnet_fwd')
+        self._sparse = bool(centres)
+        self._cws: Dict[Tuple[int, int, int], torch.Tensor] = {}             # the smaller workspaces of centres()
+        self._cgen: Dict[Tuple[int, int, int], int] = {}                      # calls of centres() per shape: a handle's validity
 
     @classmethod
-    def from_state_dict(cls, sd, device='cuda:0') -> 'EspEmbedNet':
-        return cls(sd, device)
+    def from_state_dict(cls, sd, device='cuda:0', centres: bool = False) -> 'EspEmbedNet':
+        """centres=True: `net(images)` returns `net.centres(images)`, the handle VisHead.rows reads per detection, in the dense
+        map's place (inference: OnlineVis, VisInference, SequenceFeatures.attach_vis run sparse with nothing else changed)."""
+        return cls(sd, device, centres)
 
     def state_dict(self):
         """The tensors `from_state_dict` was given, under their names."""
@@ -356,7 +392,7 @@ class EspEmbedNet:
             raise NotImplementedError('eval-mode network: train the CNN in torch')
         return self
 
-    def __call__(self, images, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _check_images(self, images) -> Tuple[int, int, int]:
         if not isinstance(images, torch.Tensor) or images.device.type != 'cuda':
             raise RuntimeError('EspEmbedNet: images on the host: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path)')
         if images.device != self.device or images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
@@ -368,6 +404,37 @@ class EspEmbedNet:
             raise ValueError('EspEmbedNet: images must be contiguous')
         if T < 1:
             raise ValueError('EspEmbedNet: an empty batch')
+        return T, H, W
+
+    def centres(self, images) -> 'EspCentres':
+        """The trunk of the net on `images` (as __call__ takes and checks them): 65 launches that leave the encoder outputs at
+        1/2 and 1/4 size and the C-channel map at 1/8 size in a workspace of this (T, H, W), allocated at the first call of the
+        shape and smaller than the dense call's by its four tail maps.  The handle answers `logits_at(pix)`.  It reads that
+        workspace, so it is valid until the net's next centres() call of the same shape (using it later raises).  C <= 256."""
+        T, H, W = self._check_images(images)
+        if self.C > MAX_CENTRES_C:
+            raise ValueError(f'EspEmbedNet.centres: C={self.C}; the per-centre tail serves C <= {MAX_CENTRES_C}: take the dense '
+                             'call, net(images), of a net built with centres=False')
+        ws = self._cws.get((T, H, W))
+        if ws is None:
+            nbytes = int(_lib.fn('tmpnn_espnet_centres_ws_bytes')(T, H, W, self.C))
+            if nbytes == 0 or T * H * W >= 2 ** 31:
+                raise ValueError(f'EspEmbedNet: a batch of {T} x {H} x {W} with C={self.C} is too large for one call (T <= 65535, '
+                                 'max(C, 160) H W < 2^31, T H W < 2^31)')
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._cws[(T, H, W)] = ws
+        _lib.call('tmpnn_espnet_trunk', self._arena.data_ptr(), self.C, images.data_ptr(), T, H, W, ws.data_ptr(), ws.numel(),
+                  _lib.raw_stream(self.device))
+        gen = self._cgen.get((T, H, W), 0) + 1
+        self._cgen[(T, H, W)] = gen
+        return EspCentres(self, ws, T, H, W, gen)
+
+    def __call__(self, images, out: Optional[torch.Tensor] = None):
+        if self._sparse:
+            if out is not None:
+                raise ValueError('EspEmbedNet: out given to a net built with centres=True (it returns a handle, not a map)')
+            return self.centres(images)
+        T, H, W = self._check_images(images)
         ws = self._ws.get((T, H, W))
         if ws is None:
             nbytes = int(_lib.fn('tmpnn_espnet_ws_bytes')(T, H, W, self.C))
@@ -386,3 +453,41 @@ class EspEmbedNet:
         if rc != 0:
             raise RuntimeError(f'tmpnn_espnet_fwd failed (code {rc}): {_lib.last_error()}')
         return out
+
+
+class EspCentres:
+    """What `EspEmbedNet.centres(images)` returns: the net's answer to `images`, read per pixel.
+
+        h.T, h.C, h.H, h.W, h.shape == (T, C, H, W)     the map it stands for
+        logits, flags = h.logits_at(pix)                pix [D] int32 on the device, pix = (t H + cy) W + cx
+                                                        -> logits [D, C] float32 = net(images)[t, :, cy, cx] bit for bit (one
+                                                        launch on the current stream, no host wait), flags [D] int32: 1 where
+                                                        a pix lay outside [0, T H W) and was clamped into it
+
+    VisHead.rows takes the handle in the map's place.  It holds no map: it reads the workspace the trunk filled, which the net's
+    next centres() call of the same (T, H, W) overwrites -- the handle is valid until then, and logits_at raises afterwards."""
+
+    def __init__(self, net: EspEmbedNet, ws: torch.Tensor, T: int, H: int, W: int, gen: int):
+        self._net, self._ws, self._gen = net, ws, gen
+        self.T, self.C, self.H, self.W = T, net.C, H, W
+        self.shape = (T, net.C, H, W)
+        self.device = net.device
+
+    def logits_at(self, pix, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        net = self._net
+        if net._cgen.get((self.T, self.H, self.W)) != self._gen:
+            raise RuntimeError("EspCentres: the net's centres() has run again on this shape and overwritten what this handle reads")
+        if (not isinstance(pix, torch.Tensor) or pix.device != self.device or pix.dtype != torch.int32 or pix.dim() != 1
+                or not pix.is_contiguous()):
+            raise ValueError(f'EspCentres.logits_at: pix [D] int32 contiguous on {self.device} expected')
+        D = int(pix.shape[0])
+        if out is None:
+            out = torch.empty((D, self.C), dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32
+              or tuple(out.shape) != (D, self.C) or not out.is_contiguous()):
+            raise ValueError(f'EspCentres.logits_at: out [{D}, {self.C}] float32 contiguous on {self.device} expected')
+        flags = torch.empty(D, dtype=torch.int32, device=self.device)
+        if D:
+            _lib.call('tmpnn_espnet_centres', net._arena.data_ptr(), self.C, self.T, self.H, self.W, self._ws.data_ptr(),
+                      self._ws.numel(), pix.data_ptr(), D, out.data_ptr(), flags.data_ptr(), _lib.raw_stream(self.device))
+        return out, flags

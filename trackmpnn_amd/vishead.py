@@ -239,7 +239,7 @@ class VisHead:
                                                                         reaches the CNN through `maps`
         head.record()                                               -> the counts of the last call (one host read)
 
-    maps [T, 128, Hm, Wm] float32 on the device; box [D, 4], map_of [D], im_hw [D, 2] or (h, w), track [D], offsets [B + 1];
+    maps [T, 128, Hm, Wm] float32 on the device (rows() also takes an espnet.EspCentres); box [D, 4], map_of [D], im_hw [D, 2] or (h, w), track [D], offsets [B + 1];
     D <= MAX_DETS = 131 072 per call; map_of, track and offsets are int32 on the device (host arrays outside int32 raise):
     device tensors are used as they are and nothing then waits for the device; host tensors and arrays are uploaded."""
 
@@ -261,16 +261,26 @@ class VisHead:
         self._stats = torch.from_numpy(np.concatenate([self.mean, self.std])).to(dev)
         self._last: Optional[_VisCall] = None
 
-    # ---- one forward: two launches
+    # ---- one forward: two launches over a map; three (pixels, the CNN's tail at them, rows) over an EspCentres
     def _launch(self, maps, box, map_of, im_hw, track, offsets, out, col) -> _VisCall:
         dev = self.device
-        if not isinstance(maps, torch.Tensor) or maps.device.type != 'cuda':
-            raise RuntimeError('VisHead: maps on the host: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path)')
-        if maps.device != dev or maps.dim() != 4 or maps.shape[1] != VIS_COLS or maps.dtype != torch.float32:
-            raise ValueError(f'VisHead: maps [T, {VIS_COLS}, Hm, Wm] float32 on {dev} expected, got {tuple(maps.shape)} {maps.dtype} '
-                             f'on {maps.device}')
-        mp = maps.detach().contiguous()
-        T, _, Hm, Wm = (int(v) for v in mp.shape)
+        from .espnet import EspCentres
+        sparse = isinstance(maps, EspCentres)
+        if sparse:
+            if track is not None or offsets is not None:
+                raise ValueError('VisHead.forward: an EspCentres carries no map for the backward to fill: train over the dense '
+                                 'call, net(images) of a net built with centres=False (rows() takes the handle)')
+            if maps.device != dev or maps.C != VIS_COLS:
+                raise ValueError(f'VisHead: an EspCentres with C = {VIS_COLS} on {dev} expected, got C = {maps.C} on {maps.device}')
+            mp, (T, _, Hm, Wm) = maps, maps.shape
+        else:
+            if not isinstance(maps, torch.Tensor) or maps.device.type != 'cuda':
+                raise RuntimeError('VisHead: maps on the host: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path)')
+            if maps.device != dev or maps.dim() != 4 or maps.shape[1] != VIS_COLS or maps.dtype != torch.float32:
+                raise ValueError(f'VisHead: maps [T, {VIS_COLS}, Hm, Wm] float32 on {dev} expected, got {tuple(maps.shape)} '
+                                 f'{maps.dtype} on {maps.device}')
+            mp = maps.detach().contiguous()
+            T, _, Hm, Wm = (int(v) for v in mp.shape)
         if T < 1 or Hm < 1 or Wm < 1 or T * Hm * Wm >= _I32:
             raise ValueError(f'VisHead: maps of {T} x {Hm} x {Wm} pixels (1 .. 2^31 - 1 expected)')
         bx = _dev_tensor(box, torch.float32, dev, 'box')
@@ -322,19 +332,29 @@ class VisHead:
         call.D, call.B, call.maps_shape, call.fbuf, call.ibuf = D, B, tuple(mp.shape), fbuf, ibuf
         call.keep = (mp, bx, mo, hw, tr, of, rows, self._stats)
         call.c = _lib.CVisHead(T, Hm, Wm, B, D, self.input_h, self.input_w, self.down_ratio, im_h, im_w, ld, col, 0,
-                               mp.data_ptr(), bx.data_ptr(), mo.data_ptr(), _lib.ptr(hw), _lib.ptr(tr), _lib.ptr(of),
+                               None if sparse else mp.data_ptr(), bx.data_ptr(), mo.data_ptr(), _lib.ptr(hw), _lib.ptr(tr), _lib.ptr(of),
                                self._stats.data_ptr(), self._stats.data_ptr() + 4 * VIS_COLS, rows.data_ptr(),
                                fp, fp + 4 * D * VIS_COLS, fp + 4 * D * (VIS_COLS + 2), ip, ip + 4 * D, ip + 8 * D, ip + 12 * D,
                                fp + 4 * D * (VIS_COLS + 3), ip + 16 * D)
-        _lib.call('tmpnn_vis_head_fwd', C.byref(call.c), _lib.raw_stream(dev))
         call.rows, call.logits = rows, fbuf[:D * VIS_COLS].view(D, VIS_COLS)
+        if sparse:
+            _lib.call('tmpnn_vis_head_pixels', C.byref(call.c), _lib.raw_stream(dev))
+            _, esp_flags = mp.logits_at(ibuf[:D], out=call.logits)          # (every pix is inside the map: the flags stay 0)
+            call.keep += (esp_flags,)
+            _lib.call('tmpnn_vis_head_rows_from_logits', C.byref(call.c), _lib.raw_stream(dev))
+        else:
+            _lib.call('tmpnn_vis_head_fwd', C.byref(call.c), _lib.raw_stream(dev))
         call.loss = fbuf[D * (VIS_COLS + 3):]
         self._last = call
         return call
 
     def rows(self, maps, box, map_of, im_hw, out: Optional[torch.Tensor] = None, col: int = 0) -> torch.Tensor:
         """The standardised 'vis' columns of D detections: a new [D, 128] tensor, or `out` [D, F] (any row stride) with its
-        columns col .. col + 127 written and the others untouched.  No autograd graph is built."""
+        columns col .. col + 127 written and the others untouched.  No autograd graph is built.
+
+        `maps` may be an espnet.EspCentres (EspEmbedNet.centres, C = 128) in the tensor's place: the head then computes the
+        pixels, asks the handle for the logits at them and forms the rows from those -- three launches, no host wait, the same
+        bits in rows, last_logits() and record() as over the dense map."""
         with torch.no_grad():
             return self._launch(maps, box, map_of, im_hw, None, None, out, col).rows
 
@@ -348,6 +368,10 @@ class VisHead:
         `embed_record()` then gives the embedding loss's counts of the call."""
         if track is None or offsets is None:
             raise ValueError('VisHead.forward: track and offsets are needed (rows() is the call without a loss)')
+        from .espnet import EspCentres
+        if isinstance(maps, EspCentres):
+            raise ValueError('VisHead.forward: an EspCentres carries no map for the backward to fill: train over the dense call, '
+                             'net(images) of a net built with centres=False (rows() takes the handle)')
         if not (isinstance(loss, str) and loss == 'identity'):
             crit = self._embedding(loss)
             got = _VisEmbedFn.apply(maps, self, crit, box, map_of, im_hw, track, offsets, (out, col if out is not None else 0))
