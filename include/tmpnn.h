@@ -84,7 +84,10 @@ extern "C" {
                                    tmpnn_espnet_fwd (entry points added, none changed);
                                still 13, for the same reason: + tmpnn_espnet_centres_ws_bytes, tmpnn_espnet_trunk,
                                    tmpnn_espnet_centres, tmpnn_vis_head_pixels, tmpnn_vis_head_rows_from_logits (entry points
-                                   added, none changed) */
+                                   added, none changed);
+                               still 13, for the same reason: + tmpnn_espnet_train_param_floats, tmpnn_espnet_train_table,
+                                   tmpnn_espnet_train_ws_bytes, tmpnn_espnet_train_bwd_ws_bytes, tmpnn_espnet_refold,
+                                   tmpnn_espnet_train_fwd, tmpnn_espnet_train_bwd (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1744,6 +1747,41 @@ int tmpnn_espnet_trunk(const float* arena, int C, const float* images, int T, in
                        tmpnn_stream stream);
 int tmpnn_espnet_centres(const float* arena, int C, int T, int H, int W, const void* ws, size_t ws_bytes, const int32_t* pix, int D,
                          float* logits, int32_t* flags, tmpnn_stream stream);
+/* Training the decoder behind merge_l3 with everything in front of it frozen (csrc/espnet_train.hip; host definition:
+ * trackmpnn_amd.espnet.espnet_decoder_grads_host).  The function differentiated is tmpnn_espnet_fwd's: running statistics, both
+ * Dropout2d the identity (fine-tuning with frozen statistics).  Trained: 9 tensors, float32, in ONE flat parameter buffer without
+ * padding, in the order of the state dict:
+ *   project_l3.1.conv.weight [C][128] | act_l3.bn.weight [C] | act_l3.bn.bias [C] | act_l3.act.weight [C] |
+ *   project_l2.conv.weight [C][64 + C] | project_l2.bn.weight [C] | project_l2.bn.bias [C] | project_l2.act.weight [C] |
+ *   project_l1.1.conv.weight [C][32 + C]
+ * `stats` holds the frozen statistics of the two norms: act_l3 running_mean [C] | running_var [C] | project_l2 running_mean [C] |
+ * running_var [C].  `grads` has the parameter buffer's layout; the backward ADDS into it.
+ *   tmpnn_espnet_train_param_floats  the length of the parameter buffer (0: C outside 1 .. 1024)
+ *   tmpnn_espnet_train_table         rows [n][3] int64 for the first min(n, cap) tensors: (offset in the parameter buffer, element
+ *                                    count, offset in the weight arena of the segment the tensor is folded into); returns n = 9
+ *                                    (TMPNN_EINVAL < 0: C outside 1 .. 1024)
+ *   tmpnn_espnet_train_ws_bytes      the workspace of tmpnn_espnet_train_fwd: tmpnn_espnet_fwd's, then what the backward needs kept
+ *                                    (the pre-activations of act_l3 and project_l2); 0: a shape that is refused
+ *   tmpnn_espnet_train_bwd_ws_bytes  the scratch of tmpnn_espnet_train_bwd (float64 partial sums included); 0 likewise
+ *   tmpnn_espnet_refold              one launch: rewrites the arena segments of the three trained layers from params and stats
+ *                                    (weights transposed, scale and shift folded in float64 and rounded once: the bits the host
+ *                                    packing gives); nothing is copied through the host
+ *   tmpnn_espnet_train_fwd           tmpnn_espnet_fwd's 70 launches (the same host code and kernels; the two trained layers that end
+ *                                    in a PReLU also store the value in front of it); out has tmpnn_espnet_fwd's bits
+ *   tmpnn_espnet_train_bwd           after tmpnn_espnet_train_fwd on the same workspace: d_out [T][C][H][W] -> grads, and, when
+ *                                    d_l1 [T][32][H/2][W/2] and d_l2 [T][64][H/4][W/4] are given (both or neither), the gradients
+ *                                    at the encoder taps out_l1 and out_l2 (overwritten).  13 launches whatever T is, no atomics,
+ *                                    every sum in a fixed order: equal bits for equal inputs.  The same checks as tmpnn_espnet_fwd. */
+size_t tmpnn_espnet_train_param_floats(int C);
+int tmpnn_espnet_train_table(int C, int64_t* rows, int cap);
+size_t tmpnn_espnet_train_ws_bytes(int T, int H, int W, int C);
+size_t tmpnn_espnet_train_bwd_ws_bytes(int T, int H, int W, int C);
+int tmpnn_espnet_refold(float* arena, int C, const float* params, const float* stats, tmpnn_stream stream);
+int tmpnn_espnet_train_fwd(const float* arena, int C, const float* images, int T, int H, int W, void* ws, size_t ws_bytes, float* out,
+                           tmpnn_stream stream);
+int tmpnn_espnet_train_bwd(const float* arena, int C, const float* params, const float* stats, int T, int H, int W, const void* ws,
+                           size_t ws_bytes, const float* d_out, void* bws, size_t bws_bytes, float* grads, float* d_l1, float* d_l2,
+                           tmpnn_stream stream);
 
 /* ---- comparison builds only (-DTMPNN_KEEP_VARIANTS; tools/build_variant.sh) ------------------------------------------------
  * Superseded forms kept for A/B runs: the two-kernel backward of the wide cells (the shipped path takes both W_ih products on

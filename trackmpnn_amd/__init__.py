@@ -28,7 +28,7 @@ from .track_mpnn import SparseAttention, TrackMPNN
 from .tracking import TrackGraph
 from .vishead import VisHead, vis_centres_host, vis_head_host, vis_pixels_host
 from .embedloss import EmbeddingLoss, embedding_loss_host
-from .espnet import EspCentres, EspEmbedNet, espnet_centres_host, espnet_host
+from .espnet import EspCentres, EspEmbedNet, EspTrainNet, espnet_centres_host, espnet_decoder_grads_host, espnet_host
 from .train_batch import AllChunksSkipped, LossWindows, TrainBatch, build_train_batch, build_train_batch_device
 
 __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'create_targets', 'CELoss', 'FocalLoss', 'FrameGraph', 'CallPlan', 'graph_from_adjacency', 'graph_from_edges',
@@ -46,4 +46,5 @@ __all__ = ['TrackMPNN', 'CapturedWindow', 'TrackGraph', 'SparseAttention', 'crea
            'synth_result_sequence', 'EvalPrep', 'PrepRules', 'KITTI_CAR', 'KITTI_PEDESTRIAN', 'evalprep_frame_host', 'evalprep_host',
            'evalprep_ioa_host', 'synth_prep_sequence', 'SequenceFeatures', 'SequenceSample', 'sequence_features_host',
            'sequence_vis_host', 'listed_features_host', 'VisInference', 'validate_store', 'infer_store', 'EmbeddingLoss',
-           'embedding_loss_host', 'EspEmbedNet', 'espnet_host', 'EspCentres', 'espnet_centres_host']
+           'embedding_loss_host', 'EspEmbedNet', 'espnet_host', 'EspCentres', 'espnet_centres_host', 'EspTrainNet',
+           'espnet_decoder_grads_host']

@@ -12,13 +12,18 @@
     EspCentres              `net.centres(images)`: the net run up to its C-channel map at 1/8 size (tmpnn_espnet_trunk), and
                             `.logits_at(pix)` the rest of the decoder at the pixels asked for (tmpnn_espnet_centres), equal bit
                             for bit to the dense map there
+    espnet_decoder_grads_host(sd, images, d_maps)   the gradients of the 36 decoder tensors and at the four encoder taps by
+                            torch autograd over espnet_host's ops: the DEFINITION of the decoder's backward
+    EspTrainNet             the same forward with a backward on the device (tmpnn_espnet_train_fwd / _bwd / tmpnn_espnet_refold;
+                            csrc/espnet_train.hip): fine-tuning with frozen statistics, the decoder behind merge_l3 trainable
+                            (trained_param_names: 9 of the 36 tensors of decoder_param_names), everything in front of it frozen
 
 The sparse path.  VisHead reads one pixel per detection, and everything behind the 1/8-size map is pointwise convs and x2 bilinear
 steps: one output pixel depends on 2 x 2 pixels of merge_l1, 3 x 3 of merge_l2 and their taps at 1/8 size.  So for inference
 `EspEmbedNet.from_state_dict(sd, device, centres=True)` makes `net(images)` return an EspCentres in the map's place, which
 VisHead.rows takes as it takes the map; the dense tail's five launches, their four workspace maps (2 C (P4 + P2) floats an image)
-and the [T, C, H, W] result are not made.  Training through VisHead.forward keeps the dense map (its backward hands d(maps) to a
-torch CNN).
+and the [T, C, H, W] result are not made.  Training through VisHead.forward keeps the dense map (its backward hands d(maps) to
+EspTrainNet's backward, or to a torch CNN).
 
 The net.  Encoder (widths 32 / 64 / 128 / 256 at 1/2, 1/4, 1/8, 1/16 of the input):
     level1      3x3 stride-2 conv 3 -> 32, BN, PReLU
@@ -38,7 +43,13 @@ PReLU), project_l3 (1x1 128 -> C), act_l3 (BN, PReLU), x2, project_l2 (1x1 64 + 
 project_l1 (1x1 32 + C -> C, nothing else, over cat[out_l1, up]), x2.  Every bilinear is align_corners=True.  Every BatchNorm uses
 its running statistics and both Dropout2d are the identity.
 
-Out of scope: training the CNN (backward, batch statistics, Dropout2d: train it in torch and hand the state dict over), the
+Training (EspTrainNet).  The reference draws the line itself: EESPNet_Seg.net is the ImageNet-pretrained encoder, everything else
+is initialised for this task.  EspTrainNet differentiates exactly the eval forward above -- running statistics, not updated, and
+Dropout2d the identity: fine-tuning with frozen statistics -- with respect to the decoder behind merge_l3 (project_l3, act_l3,
+project_l2, project_l1); proj_L4_C and pspMod are frozen with the encoder in this version (tests/golden/espnet_grad already pins
+their gradients for the one that completes the decoder).
+
+Out of scope: batch statistics, Dropout2d in training mode, the encoder's backward (and, for now, proj_L4_C's and pspMod's), the
 reference's other backbone (dla34 / DCNv2), s != 1, ImageNet classification checkpoints (they hold level5 and a classifier).
 """
 from __future__ import annotations
@@ -164,9 +175,14 @@ def espnet_host(sd, images, dtype=torch.float64, taps: bool = False):
     _check_hw(int(images.shape[2]), int(images.shape[3]))
     dev = images.device
     x = images.detach().to(dtype)
+    out, tp = _host_forward(lambda k: sd[k].detach().to(device=dev, dtype=dtype), x)
+    return (out, tp) if taps else out
 
-    def g(k):
-        return sd[k].detach().to(device=dev, dtype=dtype)
+
+def _host_forward(g, x, tap=None):
+    """(maps, taps and merges) of the eval forward on x [T, 3, H, W]; g(name) gives a tensor of the state dict in x's dtype on
+    x's device (espnet_host hands detached ones over, espnet_decoder_grads_host leaves that require a gradient).  tap(t): what the
+    decoder reads in the place of each encoder output t (espnet_decoder_grads_host cuts the graph there)."""
 
     def bn(v, p):
         return F.batch_norm(v, g(p + '.running_mean'), g(p + '.running_var'), g(p + '.weight'), g(p + '.bias'), False, 0.0, BN_EPS)
@@ -218,6 +234,8 @@ def espnet_host(sd, images, dtype=torch.float64, taps: bool = False):
     out_l4 = down(out_l3, 'net.level4_0', 9, img16)
     for i in range(7):
         out_l4 = eesp(out_l4, f'net.level4.{i}', 1, 7, False)
+    if tap is not None:
+        out_l1, out_l2, out_l3, out_l4 = tap(out_l1), tap(out_l2), tap(out_l3), tap(out_l4)
 
     p4 = cbr(out_l4, 'proj_L4_C')
     feats = eesp(torch.cat([out_l3, up(p4)], 1), 'pspMod.0', 1, 7, False)
@@ -231,10 +249,8 @@ def espnet_host(sd, images, dtype=torch.float64, taps: bool = False):
     merge_l2 = cbr(torch.cat([out_l2, up(m3)], 1), 'project_l2')
     merge_l1 = conv(torch.cat([out_l1, up(merge_l2)], 1), 'project_l1.1')
     out = up(merge_l1)
-    if taps:
-        return out, {'out_l1': out_l1, 'out_l2': out_l2, 'out_l3': out_l3, 'out_l4': out_l4, 'merge_l3': merge_l3,
-                     'merge_l2': merge_l2, 'merge_l1': merge_l1}
-    return out
+    return out, {'out_l1': out_l1, 'out_l2': out_l2, 'out_l3': out_l3, 'out_l4': out_l4, 'merge_l3': merge_l3,
+                 'merge_l2': merge_l2, 'merge_l1': merge_l1}
 
 
 def espnet_centres_host(sd, images, pix, dtype=torch.float64):
@@ -248,6 +264,51 @@ def espnet_centres_host(sd, images, pix, dtype=torch.float64):
     px = px.to(out.device)
     t, rem = px // (H * W), px % (H * W)
     return out[t, :, rem // W, rem % W]
+
+
+# ---- training the decoder: names and the host definition ---------------------------------------------------------------------
+def decoder_param_names(C: int) -> Tuple[str, ...]:
+    """The 36 tensors of the reference's decoder that an optimizer sees (proj_L4_C, pspMod, project_l3, act_l3, project_l2,
+    project_l1; no running statistic), in the order of espnet_spec(C)."""
+    return tuple(k for k in espnet_spec(C) if not k.startswith('net.') and not k.endswith(('running_mean', 'running_var')))
+
+
+def trained_param_names(C: int) -> Tuple[str, ...]:
+    """The tensors EspTrainNet trains: the decoder behind merge_l3 (project_l3, act_l3, project_l2, project_l1: 9 tensors).  The
+    other 27 of decoder_param_names (proj_L4_C, pspMod) are frozen with the encoder."""
+    return tuple(k for k in decoder_param_names(C) if k.startswith(('project_l3.', 'act_l3.', 'project_l2.', 'project_l1.')))
+
+
+def espnet_decoder_grads_host(sd, images, d_maps, dtype=torch.float64) -> Dict[str, torch.Tensor]:
+    """{name: gradient} of sum(maps * d_maps) for the 36 tensors of decoder_param_names and for the four encoder taps 'out_l1' ..
+    'out_l4' (the gradient that reaches each tap through the decoder: where an encoder backward would start), in `dtype` on the
+    device of `images`.  maps = espnet_host(sd, images, dtype): torch autograd over the same ops, running statistics and all.  The
+    definition EspTrainNet's backward is tested against."""
+    C = check_state_dict(sd)
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError('espnet_decoder_grads_host: images [T, 3, H, W] expected')
+    _check_hw(int(images.shape[2]), int(images.shape[3]))
+    dev = images.device
+    names = decoder_param_names(C)
+    leaves = {k: sd[k].detach().to(device=dev, dtype=dtype).clone().requires_grad_(True) for k in names}
+    cut = []
+
+    def g(k):
+        return leaves[k] if k in leaves else sd[k].detach().to(device=dev, dtype=dtype)
+
+    def tap(t):
+        cut.append(t.detach().requires_grad_(True))
+        return cut[-1]
+
+    with torch.enable_grad():
+        out, _ = _host_forward(g, images.detach().to(dtype), tap)
+        d = torch.as_tensor(d_maps).detach().to(device=dev, dtype=dtype)
+        if tuple(d.shape) != tuple(out.shape):
+            raise ValueError(f'espnet_decoder_grads_host: d_maps of shape {tuple(d.shape)}; {tuple(out.shape)} expected')
+        grads = torch.autograd.grad((out * d).sum(), [leaves[k] for k in names] + cut)
+    res = dict(zip(names, grads[:len(names)]))
+    res.update(zip(('out_l1', 'out_l2', 'out_l3', 'out_l4'), grads[len(names):]))
+    return res
 
 
 def _check_hw(H: int, W: int) -> None:
@@ -491,3 +552,232 @@ class EspCentres:
             _lib.call('tmpnn_espnet_centres', net._arena.data_ptr(), self.C, self.T, self.H, self.W, self._ws.data_ptr(),
                       self._ws.numel(), pix.data_ptr(), D, out.data_ptr(), flags.data_ptr(), _lib.raw_stream(self.device))
         return out, flags
+
+
+# ---- training the decoder on the device --------------------------------------------------------------------------------------
+class _EspTrainFn(torch.autograd.Function):
+    """maps = net(images) with a backward on the device.  The parameters are inputs, so plain autograd works (the gradients come
+    back as views of one fresh flat buffer); where every p.grad already aliases one flat buffer in the net's layout (GradBucket(net))
+    the kernels add into it directly and autograd receives None: the in-place convention of functional.INPLACE_GRADS / GradBucket,
+    valid for a plain loss.backward()."""
+
+    @staticmethod
+    def forward(ctx, net, images, taps, out, *params):
+        ctx.net, ctx.taps = net, bool(taps)
+        ctx.key, ctx.gen = net._forward(images, out)
+        return net._out
+
+    @staticmethod
+    def backward(ctx, d_maps):
+        net = ctx.net
+        grads = net._backward(ctx.key, ctx.gen, d_maps, ctx.taps)
+        return (None, None, None, None) + tuple(grads)
+
+
+class EspTrainNet(torch.nn.Module):
+    """EESPNet_Seg(classes=C, s=1) on the device with a trainable decoder tail: FINE-TUNING WITH FROZEN STATISTICS.
+
+        net = EspTrainNet.from_state_dict(sd)           sd: the torch module's state_dict()
+        maps = net(images)                              [T, C, H, W] float32, the bits of EspEmbedNet for the same weights; under
+                                                        torch.no_grad() just the forward, else maps carry a grad_fn
+        opt = torch.optim.Adam(net.parameters(), 5e-4, weight_decay=5e-4)      or BucketAdam(net, GradBucket(net), ...)
+        loss.backward(); opt.step()                     the backward runs on the device (tmpnn_espnet_train_bwd, 13 launches)
+        train_epoch(..., vis=VisTraining(head, frames, net, opt))              a training step with no torch CNN in it
+
+    The function differentiated is exactly the eval forward (espnet_host): every BatchNorm uses its running statistics and does not
+    update them, both Dropout2d are the identity; train() and eval() return the net and compute the same function.
+    Trained: the decoder behind merge_l3 -- project_l3.1.conv, act_l3.{bn, act}, project_l2.{conv, bn, act}, project_l1.1.conv: the
+    9 tensors of trained_param_names(C), as torch.nn.Parameter views of ONE flat float32 buffer in espnet_spec order under the
+    reference's names.  Frozen: every net.* tensor (the pretrained encoder), every running statistic, and -- the cut of this version
+    -- proj_L4_C and pspMod (the other 27 tensors of decoder_param_names(C)); they are no parameters, so no optimizer moves them.
+    Out of scope: batch statistics, Dropout2d in training mode, the encoder's backward.
+
+        net(images, tap_grads=True)                     after the backward, net.tap_grads = {'out_l1': [T, 32, H/2, W/2],
+                                                        'out_l2': [T, 64, H/4, W/4], 'out_l3': None, 'out_l4': None}: the gradients at
+                                                        the encoder taps this version reaches (buffers of the shape, overwritten by
+                                                        the next such backward).  tap_grads=False skips those channels' launches' work.
+        net.state_dict()                                the current tensors under the reference's names, frozen ones included:
+                                                        loads with strict=True into the reference module and into EspEmbedNet
+        net.snapshot(centres=False)                     an EspEmbedNet of the current weights (centres=True for validation)
+
+    The weight arena follows the parameters: when their version counter has moved (an optimizer step, any in-place write), the next
+    forward rewrites the trained layers' segments in one launch on the device (tmpnn_espnet_refold: float64, rounded once, the bits
+    of pack_arena); a write that autograd cannot see (`p.data`) needs net.refold().  Workspaces are allocated at the first call of a
+    (T, H, W); then a step allocates only its result (and, outside the in-place convention, the flat gradient).  The backward reads
+    what the forward left in the workspace of its shape: one backward per forward, before the next forward of that shape (it raises
+    otherwise).  Sums run in a fixed order without atomics: equal inputs give equal bits."""
+
+    inplace_param_grads = False          # GradBucket(net) sets it; the backward recognises the bucket by its addresses anyway
+
+    def __init__(self, sd, device='cuda:0'):
+        super().__init__()
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError(f'EspTrainNet on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a cuda '
+                               'device')
+        self.C = C = check_state_dict(sd)
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        self.device = dev
+        self._names = trained_param_names(C)
+        table = train_table(C)
+        spec = espnet_spec(C)
+        if len(table) != len(self._names) or any(int(n) != int(np.prod(spec[k])) for (_, n, _), k in zip(table, self._names)):
+            raise RuntimeError('espnet: the library trains other tensors than trained_param_names lists')
+        self._frozen = OrderedDict((k, v.detach().clone()) for k, v in sd.items() if k not in self._names)
+        self._keys = list(sd.keys())
+        n = int(_lib.fn('tmpnn_espnet_train_param_floats')(C))
+        host = np.zeros(n, np.float32)
+        for (o, cnt, _), k in zip(table, self._names):
+            host[o:o + cnt] = sd[k].detach().cpu().numpy().astype(np.float32).ravel()
+        self._flat = torch.from_numpy(host).to(dev)
+        self._params: 'OrderedDict[str, torch.nn.Parameter]' = OrderedDict()
+        for (o, cnt, _), k in zip(table, self._names):
+            self._params[k] = torch.nn.Parameter(self._flat[o:o + cnt].view(spec[k]))
+        stats = [sd[f'{p}.{k}'].detach().cpu().numpy().astype(np.float32) for p in ('act_l3.bn', 'project_l2.bn')
+                 for k in ('running_mean', 'running_var')]
+        self._stats = torch.from_numpy(np.concatenate(stats)).to(dev)
+        self._arena = torch.from_numpy(pack_arena(sd, C)).to(dev)
+        self._folded = self._version()
+        self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+        self._bws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+        self._taps: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._gen: Dict[Tuple[int, int, int], int] = {}
+        self._out = None
+        self.tap_grads: Optional[Dict[str, Optional[torch.Tensor]]] = None
+
+    @classmethod
+    def from_state_dict(cls, sd, device='cuda:0') -> 'EspTrainNet':
+        return cls(sd, device)
+
+    # ---- torch.nn.Module's surface --------------------------------------------------------------------------------------------
+    def named_parameters(self, prefix: str = '', recurse: bool = True, remove_duplicate: bool = True):
+        for k, p in self._params.items():
+            yield (prefix + '.' if prefix else '') + k, p
+
+    def state_dict(self, *args, **kwargs):
+        """The current tensors under the reference's names (copies), the frozen ones and num_batches_tracked as they were given."""
+        if args or kwargs:
+            raise TypeError('EspTrainNet.state_dict takes no arguments')
+        return OrderedDict((k, self._params[k].detach().clone() if k in self._params else self._frozen[k]) for k in self._keys)
+
+    def load_state_dict(self, *args, **kwargs):
+        raise NotImplementedError('EspTrainNet: build a new net with EspTrainNet.from_state_dict(sd)')
+
+    def _apply(self, fn, recurse=True):
+        raise NotImplementedError('EspTrainNet lives on the device it was built for (no .to / .cuda / .float)')
+
+    def snapshot(self, centres: bool = False) -> EspEmbedNet:
+        """An eval-mode EspEmbedNet of the current weights (it packs its own arena: a copy, not a view)."""
+        return EspEmbedNet.from_state_dict(self.state_dict(), self.device, centres)
+
+    # ---- the device side ------------------------------------------------------------------------------------------------------
+    def _version(self) -> int:
+        return self._flat._version                  # the parameters are views of the flat buffer: one counter for all
+
+    def refold(self) -> None:
+        """Rewrite the trained layers' arena segments from the parameters (one launch, no host copy)."""
+        _lib.call('tmpnn_espnet_refold', self._arena.data_ptr(), self.C, self._flat.data_ptr(), self._stats.data_ptr(),
+                  _lib.raw_stream(self.device))
+        self._folded = self._version()
+
+    def _sized(self, cache, fn_name, key):
+        buf = cache.get(key)
+        if buf is None:
+            nbytes = int(_lib.fn(fn_name)(*key, self.C))
+            if nbytes == 0:
+                raise ValueError(f'EspTrainNet: a batch of {key[0]} x {key[1]} x {key[2]} with C={self.C} is too large for one call '
+                                 '(T <= 65535, max(C, 160) H W < 2^31)')
+            buf = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return buf
+
+    def _forward(self, images, out):
+        key = EspEmbedNet._check_images(self, images)
+        T, H, W = key
+        ws = self._sized(self._ws, 'tmpnn_espnet_train_ws_bytes', key)
+        if self._version() != self._folded:
+            self.refold()
+        if out is None:
+            out = torch.empty((T, self.C, H, W), dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32
+              or tuple(out.shape) != (T, self.C, H, W) or not out.is_contiguous()):
+            raise ValueError(f'EspTrainNet: out [{T}, {self.C}, {H}, {W}] float32 contiguous on {self.device} expected')
+        _lib.call('tmpnn_espnet_train_fwd', self._arena.data_ptr(), self.C, images.data_ptr(), T, H, W, ws.data_ptr(), ws.numel(),
+                  out.data_ptr(), _lib.raw_stream(self.device))
+        gen = self._gen.get(key, 0) + 1
+        self._gen[key] = gen
+        self._out = out
+        return key, gen
+
+    def forward(self, images, tap_grads: bool = False, out: Optional[torch.Tensor] = None):
+        if not torch.is_grad_enabled():
+            self._forward(images, out)
+            maps, self._out = self._out, None
+            return maps
+        if out is not None:
+            raise ValueError('EspTrainNet: out is taken under torch.no_grad() only (a map with a grad_fn is the call\'s own)')
+        maps = _EspTrainFn.apply(self, images, tap_grads, out, *self._params.values())
+        self._out = None
+        return maps
+
+    def _backward(self, key, gen, d_maps, taps: bool):
+        if self._gen.get(key) != gen:
+            raise RuntimeError('EspTrainNet: the net ran forward again on this shape before the backward of the earlier call; its '
+                               'saved state is overwritten (one backward per forward, before the next forward of the shape)')
+        if self._version() != self._folded:
+            raise RuntimeError('EspTrainNet: the parameters changed between the forward and its backward')
+        T, H, W = key
+        d = d_maps.detach()
+        if d.dtype != torch.float32 or not d.is_contiguous():
+            d = d.to(torch.float32).contiguous()
+        ws = self._ws[key]
+        bws = self._sized(self._bws, 'tmpnn_espnet_train_bwd_ws_bytes', key)
+        params = list(self._params.values())
+        g0 = params[0].grad
+        inplace = g0 is not None
+        if inplace:
+            at = g0.data_ptr()
+            for p in params:
+                g = p.grad
+                if (g is None or g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous()
+                        or g.shape != p.shape or g.data_ptr() != at):
+                    inplace = False
+                    break
+                at += 4 * p.numel()
+        flat = None
+        if not inplace:
+            flat = torch.zeros_like(self._flat)
+        d1 = d2 = None
+        if taps:
+            tg = self._taps.get(key)
+            if tg is None:
+                tg = self._taps[key] = (torch.empty((T, 32, H // 2, W // 2), dtype=torch.float32, device=self.device),
+                                        torch.empty((T, 64, H // 4, W // 4), dtype=torch.float32, device=self.device))
+            d1, d2 = tg
+        _lib.call('tmpnn_espnet_train_bwd', self._arena.data_ptr(), self.C, self._flat.data_ptr(), self._stats.data_ptr(), T, H, W,
+                  ws.data_ptr(), ws.numel(), d.data_ptr(), bws.data_ptr(), bws.numel(),
+                  g0.data_ptr() if inplace else flat.data_ptr(), d1.data_ptr() if taps else None, d2.data_ptr() if taps else None,
+                  _lib.raw_stream(self.device))
+        self._gen[key] = gen + 1                      # the backward turned d(act) into d(pre-activation) in place: once only
+        if taps:
+            self.tap_grads = {'out_l1': d1, 'out_l2': d2, 'out_l3': None, 'out_l4': None}
+        if inplace:
+            return [None] * len(params)
+        out, o = [], 0
+        for p in params:
+            out.append(flat[o:o + p.numel()].view_as(p))
+            o += p.numel()
+        return out
+
+
+def train_table(C: int):
+    """[(offset in the flat parameter buffer, element count, offset of the arena segment the tensor is folded into)] of the
+    tensors EspTrainNet trains, in the order of trained_param_names(C) (tmpnn_espnet_train_table; needs no GPU)."""
+    f = _lib.fn('tmpnn_espnet_train_table')
+    n = int(f(int(C), None, 0))
+    if n < 0:
+        raise ValueError(f'espnet: {_lib.last_error()}')
+    rows = np.zeros((n, 3), np.int64)
+    if int(f(int(C), rows.ctypes.data, n)) != n:
+        raise RuntimeError(f'tmpnn_espnet_train_table: {_lib.last_error()}')
+    return [tuple(int(v) for v in r) for r in rows]

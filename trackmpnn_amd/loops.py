@@ -178,8 +178,9 @@ class VisTraining:
     """What train_epoch needs for a store with 'vis' features (the reference's default, train.py:132: loss_d + loss_c + loss_f)."""
     head: Any               # vishead.VisHead: the CNN's input size, down ratio and the 128 'vis' statistics
     frames: Any             # frames.FrameStore: the resized frames of the store's sequences, in the store's order
-    embed_net: Any          # the embedding CNN: images [T, 3, H, W] -> maps [T, 128, Hm, Wm]
-    embed_opt: Any          # its optimizer (zero_grad / step next to the tracker's)
+    embed_net: Any          # the embedding CNN: images [T, 3, H, W] -> maps [T, 128, Hm, Wm] with a grad_fn (any callable: a
+                            # torch module, or espnet.EspTrainNet, whose forward and backward run on the library's kernels)
+    embed_opt: Any          # its optimizer (zero_grad / step next to the tracker's): torch.optim.Adam or BucketAdam over its parameters
     embed_loss: Any = 'identity'    # loss_d: 'identity' (FairMOTLoss), 'embedding' or an embedloss.EmbeddingLoss (its deltas)
 
 
@@ -199,6 +200,7 @@ def train_epoch(model, sampler, opt, batch_size: int, epoch: int, tp_classifier:
     both optimizers' zero_grad, train_chunks, loss_d[batch.kept].sum().backward() (the identity loss of the chunks the batch
     kept: the reference `continue`s past a skipped chunk before its backward, train.py:56-67), both optimizers' step.
     vis.embed_loss chooses loss_d: the identity loss (the default) or the reference's EmbeddingLoss over the gathered logits.
+    With vis.embed_net an espnet.EspTrainNet the step holds no torch CNN: its decoder tail trains with frozen statistics.
     The monitor takes the kept chunks' loss_d in one launch (TrainMonitor.fold_embed: 'avg_loss_d' and 'avg_loss_total', the
     reference's "Average embedding loss for epoch" and its total, train.py:157-171)."""
     batch_size = int(batch_size)
