@@ -87,7 +87,8 @@ extern "C" {
                                    added, none changed);
                                still 13, for the same reason: + tmpnn_espnet_train_param_floats, tmpnn_espnet_train_table,
                                    tmpnn_espnet_train_ws_bytes, tmpnn_espnet_train_bwd_ws_bytes, tmpnn_espnet_refold,
-                                   tmpnn_espnet_train_fwd, tmpnn_espnet_train_bwd (entry points added, none changed) */
+                                   tmpnn_espnet_train_fwd, tmpnn_espnet_train_bwd (entry points added, none changed);
+                               still 13, for the same reason: + tmpnn_reduce_slabs (entry point added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -398,6 +399,13 @@ int tmpnn_rows_linear(const int32_t* rows, int R, const float* in, int ld_in, in
 
 /* out [cols][rows] = in[rows][cols]^T (weight re-layout for tmpnn_gru_fwd) */
 int tmpnn_transpose(const float* in, int rows, int cols, float* out, tmpnn_stream stream);
+
+/* dst[i] (+)= sum over s < nslab of slabs[s*stride + i], i < n, in a fixed order of plain fp32 adds (one launch): up to 64 slabs
+ * one after the other (t = 0; t += slab s, s ascending); more than 64 in two levels, the same sum over each group of 32
+ * consecutive slabs and then over the group sums in ascending order.  accumulate: dst[i] = dst[i] + t, else dst[i] = t.
+ * stride >= n; floats between n and stride are never read.  The reduction behind every per-block partial sum of the library. */
+int tmpnn_reduce_slabs(const float* slabs, size_t stride, int nslab, float* dst, size_t n, int accumulate,
+                       tmpnn_stream stream);
 
 /* ---- rows C, D: input transform on the NEW rows (models/track_mpnn.py:45-52, 59-61) -------
  * Lin1 -> BatchNorm1d -> ReLU -> Lin2, evaluated only on the nd new det rows (the new edge

@@ -366,49 +366,112 @@ __global__ void k_transpose(const float* __restrict__ in, int rows, int cols, fl
     }
 }
 
-__global__ void k_reduce_slabs(const float* __restrict__ slabs, size_t stride, int nslab,
-                               float* __restrict__ dst, size_t n, int accumulate) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
+// The ordered slab sums of up to four segments (SlabSegs, common.h) in one launch.  A block owns a run of consecutive elements
+// of one segment (row-major over its rows x cols) and every sum is a chain of plain fp32 adds in a fixed order:
+//   one level  (TWO = false): one thread per element, s = 0; s += slab k's term, k ascending.  blockDim.x elements per block.
+//   two levels (TWO = true):  32 elements per block; lane group g of the block's G (32 lanes: a 128-byte read per slab row) forms
+//     the sums of the slab groups g, g + G, ... (32 consecutive slabs each, k ascending) and leaves them in LDS; after the barrier
+//     the first lane group adds the group sums in ascending group order.  More than RS_GCAP groups go through LDS in rounds, the
+//     running sum staying in its thread, so the order does not depend on the count.
+// A slab's term is src[o], or with pair_off src[o] + src[o + pair_off]; in the two-level order the two are group sums.
+constexpr int RS_GCAP = 64;
+
+// a = 0; a += p[k * stride], k0 <= k < k1 <= k0 + 32.  A full group issues its 32 loads before the first add: the loop is bound by
+// the latency of a load, and a group is the whole work of its lane group
+__device__ __forceinline__ float sum_slab_group(const float* __restrict__ p, size_t stride, int k0, int k1) {
+    float a = 0.f;
+    if (k1 - k0 == 32) {
+        float v[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) v[j] = p[(size_t)(k0 + j) * stride];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) a += v[j];
+    } else {
 #pragma unroll 8
-    for (int k = 0; k < nslab; ++k) s += slabs[(size_t)k * stride + i];
-    dst[i] = accumulate ? dst[i] + s : s;
+        for (int k = k0; k < k1; ++k) a += p[(size_t)k * stride];
+    }
+    return a;
 }
 
-// fold groups of 32 slabs: out[g][i] = sum_{k in group g} slabs[k][i]
-__global__ void k_fold_slabs(const float* __restrict__ slabs, size_t stride, int nslab, float* __restrict__ out,
-                             size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int k0 = blockIdx.y * 32, k1 = min(nslab, k0 + 32);
+template <bool TWO>
+__global__ __launch_bounds__(1024) void k_reduce_segs(const SlabSegs t, int nslab) {
+    const int epb = TWO ? 32 : (int)blockDim.x;
+    long blk = blockIdx.x;
+    int si = 0;
+    for (; si < t.nseg - 1; ++si) {
+        const long nb = (t.s[si].rows * t.s[si].cols + epb - 1) / epb;
+        if (blk < nb) break;
+        blk -= nb;
+    }
+    const SlabSeg g = t.s[si];
+    const long n = g.rows * g.cols;
+    const int lane = TWO ? (threadIdx.x & 31) : threadIdx.x;
+    const long e = blk * epb + lane;
+    const bool valid = e < n;
+    const long r = valid ? e / g.cols : 0, c = valid ? e % g.cols : 0;
+    const float* __restrict__ p = g.src + (size_t)(r * g.src_ld + c);
+    const bool pair = g.pair_off != 0;
     float s = 0.f;
+    if constexpr (!TWO) {
+        if (!valid) return;
+        if (pair) {
+#pragma unroll 4
+            for (int k = 0; k < nslab; ++k) s += p[(size_t)k * g.stride] + p[(size_t)k * g.stride + g.pair_off];
+        } else {
 #pragma unroll 8
-    for (int k = k0; k < k1; ++k) s += slabs[(size_t)k * stride + i];
-    out[(size_t)blockIdx.y * n + i] = s;
+            for (int k = 0; k < nslab; ++k) s += p[(size_t)k * g.stride];
+        }
+    } else {
+        __shared__ float gs[2][RS_GCAP][32];
+        const int lg = threadIdx.x >> 5, nlg = blockDim.x >> 5;
+        const int ng = (nslab + 31) / 32;
+        for (int g0 = 0; g0 < ng; g0 += RS_GCAP) {
+            const int gcnt = min(RS_GCAP, ng - g0);
+            for (int gi = lg; gi < gcnt; gi += nlg) {
+                const int k0 = (g0 + gi) * 32, k1 = min(nslab, k0 + 32);
+                float a = 0.f, b = 0.f;
+                if (valid) {
+                    a = sum_slab_group(p, g.stride, k0, k1);
+                    if (pair) b = sum_slab_group(p + g.pair_off, g.stride, k0, k1);
+                }
+                gs[0][gi][lane] = a;
+                gs[1][gi][lane] = b;
+            }
+            __syncthreads();
+            if (lg == 0) {
+                if (pair) for (int gi = 0; gi < gcnt; ++gi) s += gs[0][gi][lane] + gs[1][gi][lane];
+                else for (int gi = 0; gi < gcnt; ++gi) s += gs[0][gi][lane];
+            }
+            __syncthreads();
+        }
+        if (lg != 0 || !valid) return;
+    }
+    float* d = g.dst + (size_t)(r * g.dst_ld + c);
+    *d = g.accumulate ? *d + s : s;
 }
 
 size_t reduce_slabs_ws_floats(int nslab, size_t n) { return nslab > 64 ? (size_t)ceil_div(nslab, 32) * n : 0; }
 
-int launch_fold_slabs(const float* slabs, size_t stride, int nslab, float* out, size_t n, hipStream_t st) {
-    hipLaunchKernelGGL(k_fold_slabs, dim3(ceil_div((long)n, 256), ceil_div(nslab, 32)), dim3(256), 0, st, slabs, stride, nslab,
-                       out, n);
-    return check_launch("fold_slabs");
+int launch_reduce_segs(const SlabSegs& t, int nslab, bool two_level, hipStream_t st) {
+    // one level: one 64-lane wave per block, so that a few thousand elements still spread over the CUs
+    const int epb = two_level ? 32 : 64;
+    long nb = 0;
+    for (int i = 0; i < t.nseg; ++i) nb += ceil_div(t.s[i].rows * t.s[i].cols, (long)epb);
+    if (nb == 0) return TMPNN_OK;
+    TM_REQUIRE(nb <= 0x7fffffffL, "reduce_slabs: %ld blocks", nb);
+    // two levels: a lane group per slab group, up to 32 of them (whole waves); beyond that a lane group takes several in turn
+    const int ng = ceil_div(nslab, 32), nlg = ng >= 32 ? 32 : (ng + 1) & ~1;
+    if (two_level) hipLaunchKernelGGL(k_reduce_segs<true>, dim3((unsigned)nb), dim3(32 * nlg), 0, st, t, nslab);
+    else hipLaunchKernelGGL(k_reduce_segs<false>, dim3((unsigned)nb), dim3(64), 0, st, t, nslab);
+    return check_launch("reduce_slabs");
 }
 
 int launch_reduce_slabs(const float* slabs, size_t stride, int nslab, float* dst, size_t n, int accumulate,
                         hipStream_t st, float* ws2) {
     if (n == 0) return TMPNN_OK;
-    if (nslab > 64 && ws2 != nullptr) {
-        int rc = launch_fold_slabs(slabs, stride, nslab, ws2, n, st);
-        if (rc) return rc;
-        slabs = ws2;
-        stride = n;
-        nslab = ceil_div(nslab, 32);
-    }
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(ceil_div((long)n, 256)), dim3(256), 0, st, slabs, stride, nslab, dst,
-                       n, accumulate);
-    return check_launch("reduce_slabs");
+    SlabSegs t;
+    t.add(slabs, stride, dst, 1, (long)n, 0, 0, accumulate);
+    return launch_reduce_segs(t, nslab, slabs_two_level(nslab) && ws2 != nullptr, st);
 }
 
 static int check_graph(const tmpnn_graph* g) {
@@ -989,6 +1052,16 @@ int tmpnn_segsum_bwd(const tmpnn_graph* g, const float* d_out, int ld_dout, floa
                      int accumulate, tmpnn_stream stream) {
     TM_SLICED(H, H, ld_dout, ld_din, gather(g, d_out + c0, ld_dout, d_in + c0, ld_din, w, accumulate, false, stream));
     return gather(g, d_out, ld_dout, d_in, ld_din, H, accumulate, false, stream);
+}
+
+int tmpnn_reduce_slabs(const float* slabs, size_t stride, int nslab, float* dst, size_t n, int accumulate,
+                       tmpnn_stream stream) {
+    TM_REQUIRE(nslab > 0 && stride >= n, "reduce_slabs: nslab=%d stride=%zu n=%zu", nslab, stride, n);
+    if (n == 0) return TMPNN_OK;
+    TM_REQUIRE(slabs && dst, "reduce_slabs: null pointer");
+    SlabSegs t;
+    t.add(slabs, stride, dst, 1, (long)n, 0, 0, accumulate);
+    return launch_reduce_segs(t, nslab, slabs_two_level(nslab), as_stream(stream));
 }
 
 int tmpnn_transpose(const float* in, int rows, int cols, float* out, tmpnn_stream stream) {

@@ -126,13 +126,34 @@ inline int eval_check_store(const char* fn, int S, int64_t n_gt, int64_t n_det, 
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// sum over `nslab` slabs of `n` floats each: dst[i] (+)= sum_s slabs[s*stride + i]   (deterministic)
-// More than 64 slabs are first folded 32:1 into `ws2` (reduce_slabs_ws_floats(nslab, n) floats).
+// sum over `nslab` slabs of `n` floats each: dst[i] (+)= sum_s slabs[s*stride + i]   (deterministic, one launch)
+// Up to 64 slabs are added one after the other; more than 64 (with `ws2` given) in two levels: the sum of each group of 32
+// consecutive slabs, then the group sums in ascending order.  The groups' sums live in LDS: `ws2` only selects the order
+// (reduce_slabs_ws_floats(nslab, n) floats, the fold scratch of the former two-launch form, are still what callers reserve).
 size_t reduce_slabs_ws_floats(int nslab, size_t n);
 int launch_reduce_slabs(const float* slabs, size_t stride, int nslab, float* dst, size_t n, int accumulate,
                         hipStream_t st, float* ws2 = nullptr);
-// the 32:1 fold alone: out[g*n + i] = sum over the g-th group of 32 slabs, g < ceil(nslab / 32)
-int launch_fold_slabs(const float* slabs, size_t stride, int nslab, float* out, size_t n, hipStream_t st);
+
+// The same sums for several blocks of the same `nslab` slabs in ONE launch, each scattered into a matrix of its own:
+// dst[r*dst_ld + c] (+)= sum_s src[s*stride + r*src_ld + c], r < rows, c < cols.  With pair_off != 0 the term of a slab (or, in
+// the two-level order, of a group of 32) is src[..] + src[.. + pair_off]: the two column halves of the zero-state cell's slabs.
+struct SlabSeg {
+    const float* src; size_t stride;
+    float* dst;
+    long rows, cols, src_ld, dst_ld, pair_off;
+    int accumulate;
+};
+struct SlabSegs {
+    SlabSeg s[4];
+    int nseg = 0;
+    void add(const float* src, size_t stride, float* dst, long rows, long cols, long src_ld, long dst_ld, int accumulate,
+             long pair_off = 0) {
+        s[nseg++] = SlabSeg{src, stride, dst, rows, cols, src_ld, dst_ld, pair_off, accumulate};
+    }
+};
+// two_level: the order for more than 64 slabs (what launch_reduce_slabs chooses from nslab and ws2)
+int launch_reduce_segs(const SlabSegs& t, int nslab, bool two_level, hipStream_t st);
+inline bool slabs_two_level(int nslab) { return nslab > 64; }
 
 // Generic small dense product on the vector ALU (tiny operands only: input transform, attention
 // projections).  C[crow(m)*ldc + n] (+)= sum_k A[arow(m)*sam + k*sak] * B[k*sbk + n*sbn] (+ bias[n])

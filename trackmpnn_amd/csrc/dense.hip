@@ -649,6 +649,12 @@ __global__ void k_heads_finish(const float* __restrict__ parts, size_t stride, i
     scores[i] = 1.0f / (1.0f + expf(-y));
 }
 
+typedef float df32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld_nt(const float4* p) {
+    const df32x4 v = __builtin_nontemporal_load(reinterpret_cast<const df32x4*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
 // d_h[i] (+)= dy_i * w_type ; per-block partial dw_node/dw_edge [C], db_node, db_edge
 // block = 256 threads: cpt = C/4 threads per row (float4), slots = 256/cpt rows per pass.
 // partial layout per block: [2][C] then [2]
@@ -671,9 +677,10 @@ __global__ __launch_bounds__(256) void k_heads_bwd(const float* __restrict__ h, 
     const long r0 = (long)blockIdx.x * rows_per_block;
     const long r1 = min((long)N, r0 + rows_per_block);
     if (active) {
-        // four rows per trip with every load issued up front: one row per trip leaves the loop latency-bound
-        // (a dependent scalar + 16-byte load chain per row and ~200 trips per thread)
-        constexpr int UR = 4;
+        // eight rows per trip with every load issued up front: one row per trip leaves the loop latency-bound
+        // (a dependent scalar + 16-byte load chain per row and ~200 trips per thread).  h is read once and not again before
+        // it has left every cache: non-temporal loads
+        constexpr int UR = 8;
         for (long i0 = r0 + slot; i0 < r1; i0 += (long)slots * UR) {
             float dyv[UR];
             bool ev[UR], live[UR];
@@ -690,7 +697,7 @@ __global__ __launch_bounds__(256) void k_heads_bwd(const float* __restrict__ h, 
                 }
                 dyv[u] = live[u] ? dy : 0.f;
                 ev[u] = is_edge[ic] != 0;
-                xv[u] = *reinterpret_cast<const float4*>(h + (size_t)ic * ld_h + c4);
+                xv[u] = ld_nt(reinterpret_cast<const float4*>(h + (size_t)ic * ld_h + c4));
             }
 #pragma unroll
             for (int u = 0; u < UR; ++u) {
@@ -730,19 +737,6 @@ __global__ __launch_bounds__(256) void k_heads_bwd(const float* __restrict__ h, 
         else for (int k = 0; k < slots; ++k) s += sm[(size_t)slots * 2 * C + k * 2 + (j - 2 * C)];
         out[j] = s;
     }
-}
-
-// scatter the reduced [2C+2] vector into the four gradient buffers (+=)
-__global__ void k_heads_bwd_final(const float* __restrict__ red, int C, float* __restrict__ dw_node,
-                                  float* __restrict__ db_node, float* __restrict__ dw_edge,
-                                  float* __restrict__ db_edge) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= 2 * C + 2) return;
-    const float s = red[j];
-    if (j < C) dw_node[j] += s;
-    else if (j < 2 * C) dw_edge[j - C] += s;
-    else if (j == 2 * C) db_node[0] += s;
-    else db_edge[0] += s;
 }
 
 static int heads_rows_per_block(int N) {
@@ -952,13 +946,15 @@ int tmpnn_heads_bwd(const float* h, int ld_h, int C, int N, const uint8_t* is_ed
                        d_logits, d_scores, dy_out, d_h, ld_dh, accumulate, rpb, reinterpret_cast<float*>(ws));
     int rc = check_launch("heads_bwd");
     if (rc) return rc;
+    // the blocks' [2C + 2] partials straight into the four gradient buffers (+=), in one launch
     const size_t nred = 2 * (size_t)C + 2;
-    float* part = reinterpret_cast<float*>(ws);
-    float* red = part + (size_t)nblk * nred;
-    if ((rc = launch_reduce_slabs(part, nred, nblk, red, nred, 0, st, red + nred))) return rc;
-    hipLaunchKernelGGL(k_heads_bwd_final, dim3(ceil_div(2 * C + 2, 256)), dim3(256), 0, st, red, C, dw_node, db_node,
-                       dw_edge, db_edge);
-    return check_launch("heads_bwd_final");
+    const float* part = reinterpret_cast<const float*>(ws);
+    SlabSegs t;
+    t.add(part, nred, dw_node, 1, C, 0, 0, 1);
+    t.add(part + C, nred, dw_edge, 1, C, 0, 0, 1);
+    t.add(part + 2 * C, nred, db_node, 1, 1, 0, 0, 1);
+    t.add(part + 2 * C + 1, nred, db_edge, 1, 1, 0, 0, 1);
+    return launch_reduce_segs(t, nblk, slabs_two_level(nblk), st);
 }
 
 }  // extern "C"

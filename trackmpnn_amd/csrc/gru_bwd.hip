@@ -1068,36 +1068,15 @@ __global__ __launch_bounds__(256, 2) void k_gru_bwd_weights_chunk(GruBwdWArgs a,
 
 // dW_ih[j][k] += sum_rs slab[rs][j][k], k < IN (row stride ld_dwih: a concat cell's launch owns one column half);
 // with `full` also dW_hh[j][k-IN] += ... and the biases likewise (the concat cell: only from the launch that computed them)
-__global__ void k_gru_reduce_w(const float* __restrict__ slab_w, const float* __restrict__ slab_b, int n_rs,
-                               int IN, int H, float* __restrict__ dW_ih, int ld_dwih, float* __restrict__ dW_hh,
-                               float* __restrict__ db_ih, float* __restrict__ db_hh, int full) {
-    const int XH = IN + H;
-    const size_t nW = (size_t)3 * H * XH;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nW) {
-        const int j = (int)(i / XH), col = (int)(i % XH);
-        if (col >= IN && !full) return;
-        float s = 0.f;
-        for (int k = 0; k < n_rs; ++k) s += slab_w[(size_t)k * nW + i];
-        if (col < IN) dW_ih[(size_t)j * ld_dwih + col] += s;
-        else dW_hh[(size_t)j * H + (col - IN)] += s;
-    } else if (full && i < nW + (size_t)6 * H) {
-        const int b = (int)(i - nW);
-        float s = 0.f;
-        for (int k = 0; k < n_rs; ++k) s += slab_b[(size_t)k * 6 * H + b];
-        if (b < 3 * H) db_ih[b] += s;
-        else db_hh[b - 3 * H] += s;
-    }
-}
-
 int launch_gru_reduce_w(const GruSlabs& s, int IN, int H, float* dW_ih, int ld_dwih, float* dW_hh, float* db_ih, float* db_hh,
                         int full, hipStream_t st) {
-    GruSlabs::Read r;
-    int rc = s.folded(full != 0, st, &r);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_gru_reduce_w, dim3(ceil_div((long)(s.nW + s.nB), 256)), dim3(256), 0, st, r.w, r.b, r.n, IN, H, dW_ih,
-                       ld_dwih, dW_hh, db_ih, db_hh, full);
-    return check_launch("gru_reduce_w");
+    SlabSegs t;
+    t.add(s.w, s.nW, dW_ih, 3 * H, IN, IN + H, ld_dwih, 1);
+    if (full) {
+        t.add(s.w + IN, s.nW, dW_hh, 3 * H, H, IN + H, H, 1);
+        s.add_bias(t, H, db_ih, db_hh);
+    }
+    return launch_reduce_segs(t, s.n_rs, slabs_two_level(s.n_rs), st);
 }
 
 

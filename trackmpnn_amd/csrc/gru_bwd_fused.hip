@@ -886,7 +886,7 @@ __global__ __launch_bounds__(512) void k_gru_bwd_two(GruBwdFusedArgs a, int ntil
 // is the W_ih side of k_gru_bwd_two, spread over all eight waves of the block:
 //   * wave (role, q): data product d_msg = d_gi W_ih for the 16 columns 16 q .. of the tile's rows 16 role .. + 15 (the same
 //     W^T slice in registers as k_gru_bwd_two), and dW_ih tiles jt0 + {0,1,2} / tt for the K-step (row half) `role` only; the
-//     role-1 partials go to the slab's (unused) W_hh columns and the reduction adds the two halves (k_gru_reduce_w_zs);
+//     role-1 partials go to the slab's (unused) W_hh columns and the reduction adds the two halves (SlabSeg::pair_off);
 //   * the bias gradients are f32 column sums taken in the staging: a thread keeps the four sums of its row position and
 //     columns (dr, dz, dn, dn r; db_ih = [dr|dz|dn], db_hh = [dr|dz|dn r]) and the block folds its 32 row positions in order
 //     at the end;
@@ -1238,25 +1238,6 @@ __global__ __launch_bounds__(512) void k_gru_bwd_zs(GruBwdFusedArgs a, const flo
     }
 }
 
-// k_gru_bwd_zs's slabs: dW_ih[j][k] += sum_rs (slab[rs][j][k] + slab[rs][j][H + k]) (the two K-steps); biases as k_gru_reduce_w
-__global__ void k_gru_reduce_w_zs(const float* __restrict__ slab_w, const float* __restrict__ slab_b, int n_rs, int H,
-                                  float* __restrict__ dW_ih, float* __restrict__ db_ih, float* __restrict__ db_hh) {
-    const size_t nI = (size_t)3 * H * H, nW = 2 * nI;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nI) {
-        const size_t o = (i / H) * (2 * H) + (i % H);
-        float s = 0.f;
-        for (int k = 0; k < n_rs; ++k) s += slab_w[(size_t)k * nW + o] + slab_w[(size_t)k * nW + o + H];
-        dW_ih[i] += s;
-    } else if (i < nI + (size_t)6 * H) {
-        const int b = (int)(i - nI);
-        float s = 0.f;
-        for (int k = 0; k < n_rs; ++k) s += slab_b[(size_t)k * 6 * H + b];
-        if (b < 3 * H) db_ih[b] += s;
-        else db_hh[b - 3 * H] += s;
-    }
-}
-
 }  // namespace tmpnn
 
 using namespace tmpnn;
@@ -1325,7 +1306,7 @@ static int gru_bwd_fused_concat(GruBwdFusedArgs a, const GruSlabs& slabs, int H,
                 launch_k<&k_gru_bwd_two<2, U, F, HHS>>(dim3(slabs.n_rs), dim3(512), 163840, st, a, ntiles);
         }, up, Flag{fuse && half == 0}, Flag{half == 0});
         if ((rc = check_launch("gru_bwd_fused_concat"))) return rc;
-        // (the W_hh block and the bias slabs are folded and added by launch A only)
+        // (the W_hh block and the bias slabs are added by launch A only)
         if ((rc = launch_gru_reduce_w(slabs, H, H, dW_ih + (size_t)half * H, 2 * H, dW_hh, db_ih, db_hh, half == 0, st))) return rc;
     }
     return TMPNN_OK;
@@ -1438,12 +1419,12 @@ int tmpnn_gru_bwd_fused_zero_state(const int32_t* rows, int R, const int32_t* sr
     }, up_sel(d_hout, dy), Flag{rc_gates});
     int rc = check_launch("gru_bwd_fused_zero_state");
     if (rc) return rc;
-    // the slabs' two K-step halves are added by a reduce of their own
-    GruSlabs::Read r;
-    if ((rc = slabs.folded(true, st, &r))) return rc;
-    hipLaunchKernelGGL(k_gru_reduce_w_zs, dim3(ceil_div((long)(3 * H * H + slabs.nB), 256)), dim3(256), 0, st, r.w, r.b, r.n, H,
-                       dW_ih, db_ih, db_hh);
-    return check_launch("gru_reduce_w_zs");
+    // dW_ih[j][k] += sum_rs (slab[rs][j][k] + slab[rs][j][H + k]): the slabs' two K-step halves are added by the reduction
+    // (more than 64 slabs: the halves of each group of 32 are summed apart and added per group); biases as launch_gru_reduce_w
+    SlabSegs t;
+    t.add(slabs.w, slabs.nW, dW_ih, 3 * H, H, 2 * H, H, 1, H);
+    slabs.add_bias(t, H, db_ih, db_hh);
+    return launch_reduce_segs(t, n_rs, slabs_two_level(n_rs), st);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // The launch layer of the GRU backward entry points (csrc/gru_bwd.hip, csrc/gru_bwd_fused.hip), host code only: runtime flags
-// to template arguments, the launch of one instantiation, the slab workspace with its fold, and the checks of the upstream
-// gradient.  An entry point reads: validate -> describe the launch -> dispatch -> fold and reduce.
+// to template arguments, the launch of one instantiation, the slab workspace with its reduction, and the checks of the upstream
+// gradient.  An entry point reads: validate -> describe the launch -> dispatch -> reduce.
 #pragma once
 #include "gru_common.h"
 #include <type_traits>
@@ -32,35 +32,28 @@ void launch_k(dim3 grid, dim3 block, size_t shm, hipStream_t st, const A&... arg
 }
 
 // The weight-gradient slabs of one launch at the front of a workspace: n_rs partial sums [3H][IN+H] (w) and [2][3H] (b), one per
-// block or row slab, then room to fold them 32:1 when there are more than 64.
+// block or row slab.  (bytes() still reserves the fold scratch of the former two-launch reduction behind them: callers size their
+// workspaces with it; the one-launch reduction keeps its group sums in LDS and leaves that room unused.)
 struct GruSlabs {
     int n_rs;
     size_t nW, nB;
-    float *w, *b, *fold;
+    float *w, *b;
     GruSlabs(void* ws, int n_rs_, int IN, int H)
         : n_rs(n_rs_), nW((size_t)3 * H * (IN + H)), nB((size_t)6 * H), w(reinterpret_cast<float*>(ws)),
-          b(w + (size_t)n_rs_ * nW), fold(b + (size_t)n_rs_ * nB) {}
+          b(w + (size_t)n_rs_ * nW) {}
     static size_t bytes(int n_rs, int IN, int H) {
         const size_t per = (size_t)3 * H * (IN + H) + (size_t)6 * H;
         return ((size_t)n_rs * per + reduce_slabs_ws_floats(n_rs, per)) * sizeof(float);
     }
-    // what the final reduce reads: the slabs themselves, or (more than 64) their 32:1 fold; `bias` = 0 leaves the b slabs alone
-    // and gives the reduce none to read (Read::b = NULL)
-    struct Read { const float* w; const float* b; int n; };
-    int folded(bool bias, hipStream_t st, Read* r) const {
-        *r = Read{w, bias ? b : nullptr, n_rs};
-        if (n_rs <= 64) return TMPNN_OK;
-        const int ng = ceil_div(n_rs, 32);
-        float* fb = fold + (size_t)ng * nW;
-        int rc = launch_fold_slabs(w, nW, n_rs, fold, nW, st);
-        if (rc == TMPNN_OK && bias) rc = launch_fold_slabs(b, nB, n_rs, fb, nB, st);
-        *r = Read{fold, bias ? fb : nullptr, ng};
-        return rc;
+    // the bias slabs' two segments of a reduction: db_ih += b[0:3H], db_hh += b[3H:6H]
+    void add_bias(SlabSegs& t, int H, float* db_ih, float* db_hh) const {
+        t.add(b, nB, db_ih, 1, 3 * H, 0, 0, 1);
+        t.add(b + 3 * H, nB, db_hh, 1, 3 * H, 0, 0, 1);
     }
 };
 
-// fold and final reduce (k_gru_reduce_w, csrc/gru_bwd.hip): dW_ih[j][0:IN] (row stride ld_dwih) += the W_ih block of the slabs;
-// with `full`, dW_hh, db_ih and db_hh += theirs as well
+// the slabs' ordered sums in one launch (launch_reduce_segs, csrc/agg.hip; more than 64 slabs: 32 at a time, then the groups):
+// dW_ih[j][0:IN] (row stride ld_dwih) += the W_ih block of the slabs; with `full`, dW_hh, db_ih and db_hh += theirs as well
 int launch_gru_reduce_w(const GruSlabs& s, int IN, int H, float* dW_ih, int ld_dwih, float* dW_hh, float* db_ih, float* db_hh,
                         int full, hipStream_t st);
 
