@@ -88,7 +88,10 @@ extern "C" {
                                still 13, for the same reason: + tmpnn_espnet_train_param_floats, tmpnn_espnet_train_table,
                                    tmpnn_espnet_train_ws_bytes, tmpnn_espnet_train_bwd_ws_bytes, tmpnn_espnet_refold,
                                    tmpnn_espnet_train_fwd, tmpnn_espnet_train_bwd (entry points added, none changed);
-                               still 13, for the same reason: + tmpnn_reduce_slabs (entry point added, none changed) */
+                               still 13, for the same reason: + tmpnn_reduce_slabs (entry point added, none changed);
+                               still 13, for the same reason: + tmpnn_espnet_dec_param_floats, tmpnn_espnet_dec_table,
+                                   tmpnn_espnet_dec_ws_bytes, tmpnn_espnet_dec_bwd_ws_bytes, tmpnn_espnet_dec_refold,
+                                   tmpnn_espnet_dec_fwd, tmpnn_espnet_dec_bwd (entry points added, none changed) */
 
 #define TMPNN_OK 0
 #define TMPNN_EINVAL (-1)   /* bad shape / null pointer / unsupported width */
@@ -1790,6 +1793,38 @@ int tmpnn_espnet_train_fwd(const float* arena, int C, const float* images, int T
 int tmpnn_espnet_train_bwd(const float* arena, int C, const float* params, const float* stats, int T, int H, int W, const void* ws,
                            size_t ws_bytes, const float* d_out, void* bws, size_t bws_bytes, float* grads, float* d_l1, float* d_l2,
                            tmpnn_stream stream);
+/* The same with the WHOLE decoder trained: proj_L4_C and pspMod as well, the encoder (every net.* tensor) still frozen.  Seven
+ * siblings of the entry points above with the same arguments and checks; what differs:
+ *   the parameter buffer     the 36 decoder tensors in state-dict order without padding:
+ *                            proj_L4_C.conv.weight [128][256] | .bn.weight [128] | .bn.bias [128] | .act.weight [128] |
+ *                            pspMod.0.proj_1x1.conv.weight [32][64] | .bn.weight [32] | .bn.bias [32] | .act.weight [32] |
+ *                            pspMod.0.spp_dw.0 .. 3.conv.weight 4 x [32][9] | pspMod.0.conv_1x1_exp.conv.weight [128][32] | .bn.weight
+ *                            [128] | .bn.bias [128] | pspMod.0.br_after_cat.bn.weight [128] | .bn.bias [128] | .act.weight [128] |
+ *                            pspMod.0.module_act.weight [128] | pspMod.1.stages.0 .. 3.conv.weight 4 x [128][9] |
+ *                            pspMod.1.project.conv.weight [128][640] | .bn.weight [128] | .bn.bias [128] | .act.weight [128] | the 9
+ *                            tensors of the tail as above
+ *   stats                    running_mean [c] | running_var [c] of the 7 norms in that order: proj_L4_C.bn (128), pspMod.0.proj_1x1.bn
+ *                            (32), pspMod.0.conv_1x1_exp.bn (128), pspMod.0.br_after_cat.bn (128), pspMod.1.project.bn (128), act_l3.bn
+ *                            (C), project_l2.bn (C)
+ *   tmpnn_espnet_dec_table   returns n = 36; a grouped conv weight's segment is Wt [cin / g][cout], a depthwise weight's segment the
+ *                            tensor as it lies, bn.weight's the folded scale, bn.bias's the folded shift, a slope's the slopes
+ *   tmpnn_espnet_dec_ws_bytes      tmpnn_espnet_train_ws_bytes', then the pre-activations of proj_L4_C, pspMod.0.proj_1x1,
+ *                            pspMod.0.conv_1x1_exp and pspMod.1.project and the four pooled maps of the PSP chain
+ *   tmpnn_espnet_dec_refold  one launch over all 26 trained segments
+ *   tmpnn_espnet_dec_fwd     tmpnn_espnet_fwd's 70 launches and bits; the PSP chain writes its four pooled maps to four places
+ *   tmpnn_espnet_dec_bwd     48 launches whatever T is (the first 13 are tmpnn_espnet_train_bwd's, with the same bits for the tail's 9
+ *                            tensors and for d_l1 and d_l2); d_l1, d_l2, d_l3 [T][128][H/8][W/8], d_l4 [T][256][H/16][W/16]: all
+ *                            four or none (then 47 launches, and no parameter gradient changes a bit) */
+size_t tmpnn_espnet_dec_param_floats(int C);
+int tmpnn_espnet_dec_table(int C, int64_t* rows, int cap);
+size_t tmpnn_espnet_dec_ws_bytes(int T, int H, int W, int C);
+size_t tmpnn_espnet_dec_bwd_ws_bytes(int T, int H, int W, int C);
+int tmpnn_espnet_dec_refold(float* arena, int C, const float* params, const float* stats, tmpnn_stream stream);
+int tmpnn_espnet_dec_fwd(const float* arena, int C, const float* images, int T, int H, int W, void* ws, size_t ws_bytes, float* out,
+                         tmpnn_stream stream);
+int tmpnn_espnet_dec_bwd(const float* arena, int C, const float* params, const float* stats, int T, int H, int W, const void* ws,
+                         size_t ws_bytes, const float* d_out, void* bws, size_t bws_bytes, float* grads, float* d_l1, float* d_l2,
+                         float* d_l3, float* d_l4, tmpnn_stream stream);
 
 /* ---- comparison builds only (-DTMPNN_KEEP_VARIANTS; tools/build_variant.sh) ------------------------------------------------
  * Superseded forms kept for A/B runs: the two-kernel backward of the wide cells (the shipped path takes both W_ih products on

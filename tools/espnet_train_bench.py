@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Time one training step of the embedding CNN's decoder: forward + backward + Adam step (run by hand; nothing asserts a time).
 
-    python tools/espnet_train_bench.py [--C 128] [--hw 384 1280] [--T 1 8] [--steps 10] [--repeats 5] [--only device|torch]
+    python tools/espnet_train_bench.py [--C 128] [--hw 384 1280] [--T 1 8] [--steps 10] [--repeats 5] [--scope tail [decoder]]
+                                       [--only device|torch]
 
-device      EspTrainNet + GradBucket + BucketAdam: the library's path (70 forward launches, 1 refold, 13 backward launches, 1 Adam
-            launch and the bucket's zero fill per step, whatever T is)
-torch       the path a user had before: espnet_host's ops in float32 on the device with autograd on the same trained tensors and
-            torch.optim.Adam (the encoder runs without a graph in both)
+device      EspTrainNet + GradBucket + BucketAdam: the library's path (70 forward launches, 1 refold, 13 backward launches -- 48
+            with scope='decoder' --, 1 Adam launch and the bucket's zero fill per step, whatever T is); one path per --scope
+            given, named `device` for the tail and `device/decoder` for the whole decoder
+torch       the path a user had before: espnet_host's ops in float32 on the device with autograd on the trained tensors of the
+            last --scope given and torch.optim.Adam (the encoder runs without a graph in all)
 d_maps is what VisHead's backward hands over: 16 centres per frame, every other pixel zero.  Seeded weights (tests/espnet_cases.py),
-random images.  Per T the two paths alternate `repeats` times; each measurement is device events around `steps` back-to-back steps
+random images.  Per T the paths alternate `repeats` times; each measurement is device events around `steps` back-to-back steps
 after a warm-up of 3.  Prints one line per measurement and a JSON summary (median and range in ms per step).  --only runs one path
 alone (for a kernel trace of its own).
 """
@@ -41,8 +43,8 @@ def sparse_d_maps(T, C, H, W, dev, seed=0):
     return d.to(dev)
 
 
-def device_step(sd, images, d, dev):
-    net = EspTrainNet.from_state_dict(sd, dev)
+def device_step(sd, images, d, dev, scope='tail'):
+    net = EspTrainNet.from_state_dict(sd, dev, scope=scope)
     bucket = GradBucket(net)
     opt = BucketAdam(net, bucket, lr=LR, weight_decay=WD)
 
@@ -53,8 +55,8 @@ def device_step(sd, images, d, dev):
     return step
 
 
-def torch_step(sd, images, d, dev):
-    names = trained_param_names(int(sd['project_l3.1.conv.weight'].shape[0]))
+def torch_step(sd, images, d, dev, scope='tail'):
+    names = trained_param_names(int(sd['project_l3.1.conv.weight'].shape[0]), scope)
     frozen = {k: v.to(dev) for k, v in sd.items() if k not in names and v.dtype.is_floating_point}
     leaves = {k: torch.nn.Parameter(sd[k].to(dev)) for k in names}
     opt = torch.optim.Adam(list(leaves.values()), LR, weight_decay=WD)
@@ -87,6 +89,7 @@ def main():
     ap.add_argument('--T', type=int, nargs='+', default=(1, 8))
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--scope', nargs='+', choices=('tail', 'decoder'), default=('tail',))
     ap.add_argument('--only', choices=('device', 'torch'))
     args = ap.parse_args()
     dev = torch.device('cuda:0')
@@ -96,7 +99,12 @@ def main():
     for T in args.T:
         images = torch.randn((T, 3, H, W), generator=torch.Generator().manual_seed(T)).to(dev)
         d = sparse_d_maps(T, args.C, H, W, dev)
-        paths = {k: f(sd, images, d, dev) for k, f in (('device', device_step), ('torch', torch_step)) if args.only in (None, k)}
+        paths = {}
+        if args.only in (None, 'device'):
+            for scope in args.scope:
+                paths['device' if scope == 'tail' else 'device/' + scope] = device_step(sd, images, d, dev, scope)
+        if args.only in (None, 'torch'):
+            paths['torch'] = torch_step(sd, images, d, dev, args.scope[-1])
         for step in paths.values():
             for _ in range(3):
                 step()
@@ -110,7 +118,7 @@ def main():
         summary[f'T={T}'] = {k: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v)) for k, v in times.items()}
         del paths
         torch.cuda.empty_cache()
-    print(json.dumps(dict(C=args.C, H=H, W=W, steps=args.steps, repeats=args.repeats, ms_per_step=summary)))
+    print(json.dumps(dict(C=args.C, H=H, W=W, steps=args.steps, repeats=args.repeats, scope=list(args.scope), ms_per_step=summary)))
 
 
 if __name__ == '__main__':

@@ -383,6 +383,14 @@ _SIGNATURES = {
     'tmpnn_espnet_train_fwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'tmpnn_espnet_train_bwd': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                        c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tmpnn_espnet_dec_param_floats': (c_size_t, [c_int]),
+    'tmpnn_espnet_dec_table': (c_int, [c_int, c_void_p, c_int]),
+    'tmpnn_espnet_dec_ws_bytes': (c_size_t, [c_int] * 4),
+    'tmpnn_espnet_dec_bwd_ws_bytes': (c_size_t, [c_int] * 4),
+    'tmpnn_espnet_dec_refold': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'tmpnn_espnet_dec_fwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'tmpnn_espnet_dec_bwd': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                     c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tmpnn_dgraph_ints': (c_size_t, [c_int]),
     'tmpnn_dgraph_bind': (c_int, [c_void_p, c_int, c_int, _DGP]),
     'tmpnn_graph_from_coo': (c_int, [c_int, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, _DGP, c_void_p]),

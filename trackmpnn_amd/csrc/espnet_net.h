@@ -166,14 +166,14 @@ __global__ __launch_bounds__(ESP_THREADS) void k_esp_reinf(const float* __restri
 
 // out[t][co][pix] = prelu((sum_k x[t][g kg + k][pix] wt[k][co]) scale[co] + shift[co] (+ res[t][co][pix]), slope[co]); res may be
 // `out` itself (each element is read and then written by its one owner), so neither carries __restrict__.
-// SAVE (the training forward): the value in front of the PReLU goes to pre[t][co][pix] (batch stride out_bs) as well.
+// SAVE (the training forward): the value in front of the PReLU goes to pre[t][co][pix] (batch stride pre_bs) as well.
 template <int CO_T, int UNROLL, bool SAVE = false>
 __global__ __launch_bounds__(ESP_THREADS) void k_esp_pw(const float* __restrict__ a, size_t a_bs, int ca, const float* __restrict__ b,
                                                         size_t b_bs, int cin, int cout, int groups, int P,
                                                         const float* __restrict__ wt, const float* __restrict__ scale,
                                                         const float* __restrict__ shift, const float* __restrict__ slope,
                                                         const float* res, size_t res_bs, float* out, size_t out_bs,
-                                                        float* __restrict__ pre = nullptr) {
+                                                        float* __restrict__ pre = nullptr, size_t pre_bs = 0) {
     const int pix = blockIdx.x * ESP_THREADS + threadIdx.x;
     const int kg = cin / groups, cpg = cout / groups;
     const int tiles = (cpg + CO_T - 1) / CO_T;
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(ESP_THREADS) void k_esp_pw(const float* __restrict_
             const int co = co0 + j;
             float v = esp_norm(acc[j], scale[co], shift[co]);
             if (res) v += res[t * res_bs + (size_t)co * P + pix];
-            if constexpr (SAVE) pre[t * out_bs + (size_t)co * P + pix] = v;
+            if constexpr (SAVE) pre[t * pre_bs + (size_t)co * P + pix] = v;
             out[t * out_bs + (size_t)co * P + pix] = prelu(v, slope[co]);
         }
     }
@@ -645,13 +645,14 @@ void run_pw(Run& r, const Pw& p, const float* a, size_t a_bs, int ca, const floa
     if (r.rc) return;
     const int cpg = p.cout / p.groups;
     if (pre) {                                   // the training forward of a trained layer: the same tile, the same chain over k
+        const size_t pre_bs = (size_t)p.cout * P;
         if (pw_wide(p, P)) {
             k_esp_pw<32, 2, true><<<grid_px(P, p.groups * (cpg / 32), r.T), ESP_THREADS, 0, r.st>>>(
-                a, a_bs, ca, b, b_bs, p.cin, p.cout, p.groups, P, p.wt, p.scale, p.shift, p.slope, res, res_bs, out, out_bs, pre);
+                a, a_bs, ca, b, b_bs, p.cin, p.cout, p.groups, P, p.wt, p.scale, p.shift, p.slope, res, res_bs, out, out_bs, pre, pre_bs);
         } else {
             const int tiles = (cpg + 7) / 8;
             k_esp_pw<8, 8, true><<<grid_px(P, p.groups * tiles, r.T), ESP_THREADS, 0, r.st>>>(
-                a, a_bs, ca, b, b_bs, p.cin, p.cout, p.groups, P, p.wt, p.scale, p.shift, p.slope, res, res_bs, out, out_bs, pre);
+                a, a_bs, ca, b, b_bs, p.cin, p.cout, p.groups, P, p.wt, p.scale, p.shift, p.slope, res, res_bs, out, out_bs, pre, pre_bs);
         }
         ESP_CHECK(r, "pointwise conv");
         return;
@@ -696,12 +697,13 @@ constexpr int DIL_1234[4] = {1, 2, 3, 4};      // r_lim >= 9: kernel sizes 3 5 7
 constexpr int DIL_1123[4] = {1, 1, 2, 3};      // r_lim = 7: 3 5 7 3, sorted 3 3 5 7
 
 // EESP of stride 1: in [T][nin][h][w] (second source b for the channels from ca on) -> out [T][..][nout][h][w] (batch stride out_bs)
+// pre_red, pre_exp (the training forward): where the two pointwise convs leave the values in front of their PReLUs, dense [T][c][h w]
 void run_eesp(Run& r, const Eesp& e, const int* dil, const float* a, size_t a_bs, int ca, const float* b, size_t b_bs, int h, int w,
-              bool residual, float* out, size_t out_bs, const Ws& s) {
+              bool residual, float* out, size_t out_bs, const Ws& s, float* pre_red = nullptr, float* pre_exp = nullptr) {
     const int P = h * w, n = e.dw.n;
-    run_pw(r, e.proj, a, a_bs, ca, b, b_bs, P, nullptr, 0, s.red, (size_t)n * P);
+    run_pw(r, e.proj, a, a_bs, ca, b, b_bs, P, nullptr, 0, s.red, (size_t)n * P, pre_red);
     run_dw(r, e.dw, dil, 1, s.red, h, w, s.cat);
-    run_pw(r, e.exp, s.cat, (size_t)4 * n * P, 4 * n, nullptr, 0, P, residual ? a : nullptr, a_bs, out, out_bs);
+    run_pw(r, e.exp, s.cat, (size_t)4 * n * P, 4 * n, nullptr, 0, P, residual ? a : nullptr, a_bs, out, out_bs, pre_exp);
 }
 
 // DownSampler: in [T][nin][h][w], img: the pyramid image at (h / 2, w / 2) -> out [T][nout][h / 2][w / 2]
@@ -735,9 +737,18 @@ int check_call(const char* who, const void* arena, const void* images, const voi
     return TMPNN_OK;
 }
 
+// What a training forward keeps for its backward, each dense [T][c][pixels]; a null pointer keeps nothing there.
+//   pre3      project_l3 / act_l3 in front of the PReLU [T][C][P8]
+//   pre4, pre_red, pre_exp, pre_psp   the same of proj_L4_C [128][P16], pspMod.0.proj_1x1 [32][P8], pspMod.0.conv_1x1_exp / module_act
+//             [128][P8] and pspMod.1.project [128][P8]
+//   pooled    the four pooled maps of the PSP chain, which the plain forward ping-pongs through pool_a / pool_b (all four or none)
+struct TrainKeep {
+    float *pre3 = nullptr, *pre4 = nullptr, *pre_red = nullptr, *pre_exp = nullptr, *pre_psp = nullptr;
+    float* pooled[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
 // The trunk: every launch of the forward up to and including m3 (65), shared by tmpnn_espnet_fwd and tmpnn_espnet_trunk.
-// pre3 (the training forward): where project_l3 / act_l3 leaves its pre-activation, [T][C][P8].
-int run_trunk(const Net& n, const Ws& s, const float* images, int T, int H, int W, int C, hipStream_t st, float* pre3 = nullptr) {
+int run_trunk(const Net& n, const Ws& s, const float* images, int T, int H, int W, int C, hipStream_t st, const TrainKeep& keep = TrainKeep()) {
     Run r{st, T, 0};
     const int h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, h8 = H / 8, w8 = W / 8, h16 = H / 16, w16 = W / 16;
     const size_t P2 = (size_t)h2 * w2, P4 = (size_t)h4 * w4, P8 = (size_t)h8 * w8, P16 = (size_t)h16 * w16;
@@ -766,10 +777,10 @@ int run_trunk(const Net& n, const Ws& s, const float* images, int T, int H, int 
     }
     const float* out_l4 = cur;
     // decoder
-    run_pw(r, n.proj4, out_l4, 256 * P16, 256, nullptr, 0, (int)P16, nullptr, 0, s.p4, ESP_PSP * P16);
+    run_pw(r, n.proj4, out_l4, 256 * P16, 256, nullptr, 0, (int)P16, nullptr, 0, s.p4, ESP_PSP * P16, keep.pre4);
     run_bilinear(r, s.p4, ESP_PSP * P16, ESP_PSP, h16, w16, s.up4, ESP_PSP * P8, h8, w8);
     const size_t psp_bs = 5 * ESP_PSP * P8;
-    run_eesp(r, n.psp_e, DIL_1123, out_l3, 128 * P8, 128, s.up4, ESP_PSP * P8, h8, w8, false, s.psp, psp_bs, s);
+    run_eesp(r, n.psp_e, DIL_1123, out_l3, 128 * P8, 128, s.up4, ESP_PSP * P8, h8, w8, false, s.psp, psp_bs, s, keep.pre_red, keep.pre_exp);
     {
         const float* prev = s.psp;
         size_t prev_bs = psp_bs;
@@ -778,6 +789,7 @@ int run_trunk(const Net& n, const Ws& s, const float* images, int T, int H, int 
         for (int k = 0; k < 4; ++k) {
             const int qh = (ph + 1) / 2, qw = (pw + 1) / 2;
             const size_t q_bs = (size_t)ESP_PSP * qh * qw;
+            if (keep.pooled[k]) pa = keep.pooled[k];
             run_pool(r, prev, prev_bs, ESP_PSP, ph, pw, pa, q_bs, nullptr);
             if (r.rc) return r.rc;
             k_esp_psp_up<<<grid_px(P8, ESP_PSP, T), ESP_THREADS, 0, r.st>>>(pa, q_bs, qh, qw, n.psp_w[k], s.psp + (size_t)(k + 1) * ESP_PSP * P8,
@@ -787,8 +799,8 @@ int run_trunk(const Net& n, const Ws& s, const float* images, int T, int H, int 
             std::swap(pa, pb);
         }
     }
-    run_pw(r, n.psp_proj, s.psp, psp_bs, 5 * ESP_PSP, nullptr, 0, (int)P8, nullptr, 0, s.pspo, ESP_PSP * P8);
-    run_pw(r, n.proj3, s.pspo, ESP_PSP * P8, ESP_PSP, nullptr, 0, (int)P8, nullptr, 0, s.m3, C * P8, pre3);
+    run_pw(r, n.psp_proj, s.psp, psp_bs, 5 * ESP_PSP, nullptr, 0, (int)P8, nullptr, 0, s.pspo, ESP_PSP * P8, keep.pre_psp);
+    run_pw(r, n.proj3, s.pspo, ESP_PSP * P8, ESP_PSP, nullptr, 0, (int)P8, nullptr, 0, s.m3, C * P8, keep.pre3);
     return r.rc;
 }
 

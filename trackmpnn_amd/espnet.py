@@ -14,9 +14,10 @@
                             for bit to the dense map there
     espnet_decoder_grads_host(sd, images, d_maps)   the gradients of the 36 decoder tensors and at the four encoder taps by
                             torch autograd over espnet_host's ops: the DEFINITION of the decoder's backward
-    EspTrainNet             the same forward with a backward on the device (tmpnn_espnet_train_fwd / _bwd / tmpnn_espnet_refold;
-                            csrc/espnet_train.hip): fine-tuning with frozen statistics, the decoder behind merge_l3 trainable
-                            (trained_param_names: 9 of the 36 tensors of decoder_param_names), everything in front of it frozen
+    EspTrainNet             the same forward with a backward on the device (tmpnn_espnet_train_fwd / _bwd / tmpnn_espnet_refold and
+                            their tmpnn_espnet_dec_* siblings; csrc/espnet_train.hip): fine-tuning with frozen statistics;
+                            scope='tail' (the default) trains the decoder behind merge_l3 (9 of the 36 tensors of
+                            decoder_param_names), scope='decoder' all 36; the encoder is frozen in both
 
 The sparse path.  VisHead reads one pixel per detection, and everything behind the 1/8-size map is pointwise convs and x2 bilinear
 steps: one output pixel depends on 2 x 2 pixels of merge_l1, 3 x 3 of merge_l2 and their taps at 1/8 size.  So for inference
@@ -45,12 +46,11 @@ its running statistics and both Dropout2d are the identity.
 
 Training (EspTrainNet).  The reference draws the line itself: EESPNet_Seg.net is the ImageNet-pretrained encoder, everything else
 is initialised for this task.  EspTrainNet differentiates exactly the eval forward above -- running statistics, not updated, and
-Dropout2d the identity: fine-tuning with frozen statistics -- with respect to the decoder behind merge_l3 (project_l3, act_l3,
-project_l2, project_l1); proj_L4_C and pspMod are frozen with the encoder in this version (tests/golden/espnet_grad already pins
-their gradients for the one that completes the decoder).
+Dropout2d the identity: fine-tuning with frozen statistics -- with respect to the decoder: with scope='tail' the part behind
+merge_l3 (project_l3, act_l3, project_l2, project_l1; proj_L4_C and pspMod frozen with the encoder), with scope='decoder' all of it,
+which is what the reference's optimizer moves outside the encoder; the gradients then reach all four encoder taps.
 
-Out of scope: batch statistics, Dropout2d in training mode, the encoder's backward (and, for now, proj_L4_C's and pspMod's), the
-reference's other backbone (dla34 / DCNv2), s != 1, ImageNet classification checkpoints (they hold level5 and a classifier).
+Out of scope: batch statistics, Dropout2d in training mode, the encoder's backward, the reference's other backbone (dla34 / DCNv2), s != 1, ImageNet classification checkpoints (they hold level5 and a classifier).
 """
 from __future__ import annotations
 
@@ -273,10 +273,27 @@ def decoder_param_names(C: int) -> Tuple[str, ...]:
     return tuple(k for k in espnet_spec(C) if not k.startswith('net.') and not k.endswith(('running_mean', 'running_var')))
 
 
-def trained_param_names(C: int) -> Tuple[str, ...]:
-    """The tensors EspTrainNet trains: the decoder behind merge_l3 (project_l3, act_l3, project_l2, project_l1: 9 tensors).  The
-    other 27 of decoder_param_names (proj_L4_C, pspMod) are frozen with the encoder."""
+SCOPES = ('tail', 'decoder')
+
+
+def _check_scope(scope) -> str:
+    if scope not in SCOPES:
+        raise ValueError(f'espnet: scope={scope!r}; one of {SCOPES} expected')
+    return scope
+
+
+def trained_param_names(C: int, scope: str = 'tail') -> Tuple[str, ...]:
+    """The tensors EspTrainNet trains.  scope='tail': the decoder behind merge_l3 (project_l3, act_l3, project_l2, project_l1: 9
+    tensors), the other 27 of decoder_param_names (proj_L4_C, pspMod) frozen with the encoder.  scope='decoder': all 36."""
+    if _check_scope(scope) == 'decoder':
+        return decoder_param_names(C)
     return tuple(k for k in decoder_param_names(C) if k.startswith(('project_l3.', 'act_l3.', 'project_l2.', 'project_l1.')))
+
+
+def trained_norm_names(C: int, scope: str = 'tail') -> Tuple[str, ...]:
+    """The BatchNorms among the trained tensors, in the state dict's order: their running statistics are what the library takes
+    as `stats` (running_mean | running_var of each)."""
+    return tuple(k[:-len('.weight')] for k in trained_param_names(C, scope) if k.endswith('bn.weight'))
 
 
 def espnet_decoder_grads_host(sd, images, d_maps, dtype=torch.float64) -> Dict[str, torch.Tensor]:
@@ -575,9 +592,10 @@ class _EspTrainFn(torch.autograd.Function):
 
 
 class EspTrainNet(torch.nn.Module):
-    """EESPNet_Seg(classes=C, s=1) on the device with a trainable decoder tail: FINE-TUNING WITH FROZEN STATISTICS.
+    """EESPNet_Seg(classes=C, s=1) on the device with a trainable decoder: FINE-TUNING WITH FROZEN STATISTICS.
 
-        net = EspTrainNet.from_state_dict(sd)           sd: the torch module's state_dict()
+        net = EspTrainNet.from_state_dict(sd)           sd: the torch module's state_dict(); trains the decoder's tail
+        net = EspTrainNet.from_state_dict(sd, dev, scope='decoder')            trains the whole decoder (below)
         maps = net(images)                              [T, C, H, W] float32, the bits of EspEmbedNet for the same weights; under
                                                         torch.no_grad() just the forward, else maps carry a grad_fn
         opt = torch.optim.Adam(net.parameters(), 5e-4, weight_decay=5e-4)      or BucketAdam(net, GradBucket(net), ...)
@@ -592,10 +610,15 @@ class EspTrainNet(torch.nn.Module):
     -- proj_L4_C and pspMod (the other 27 tensors of decoder_param_names(C)); they are no parameters, so no optimizer moves them.
     Out of scope: batch statistics, Dropout2d in training mode, the encoder's backward.
 
+    scope='decoder': all 36 tensors of decoder_param_names(C) are parameters (proj_L4_C and pspMod as well: what the reference's
+    optimizer moves outside the encoder), views of one flat buffer in that order; the backward is tmpnn_espnet_dec_bwd (48
+    launches, the first 13 the tail's with the tail's bits), tap_grads holds all four taps ('out_l3' [T, 128, H/8, W/8], 'out_l4'
+    [T, 256, H/16, W/16]), and everything else said here holds unchanged.  An unknown scope raises ValueError.
+
         net(images, tap_grads=True)                     after the backward, net.tap_grads = {'out_l1': [T, 32, H/2, W/2],
                                                         'out_l2': [T, 64, H/4, W/4], 'out_l3': None, 'out_l4': None}: the gradients at
-                                                        the encoder taps this version reaches (buffers of the shape, overwritten by
-                                                        the next such backward).  tap_grads=False skips those channels' launches' work.
+                                                        the encoder taps the scope reaches (buffers of the shape, overwritten by the
+                                                        next such backward; scope='decoder' fills all four).  tap_grads=False skips those channels' launches' work.
         net.state_dict()                                the current tensors under the reference's names, frozen ones included:
                                                         loads with strict=True into the reference module and into EspEmbedNet
         net.snapshot(centres=False)                     an EspEmbedNet of the current weights (centres=True for validation)
@@ -609,8 +632,13 @@ class EspTrainNet(torch.nn.Module):
 
     inplace_param_grads = False          # GradBucket(net) sets it; the backward recognises the bucket by its addresses anyway
 
-    def __init__(self, sd, device='cuda:0'):
+    def __init__(self, sd, device='cuda:0', scope: str = 'tail'):
         super().__init__()
+        self.scope = _check_scope(scope)
+        self._ep = {'tail': ('tmpnn_espnet_train_ws_bytes', 'tmpnn_espnet_train_bwd_ws_bytes', 'tmpnn_espnet_refold',
+                             'tmpnn_espnet_train_fwd', 'tmpnn_espnet_train_bwd', 'tmpnn_espnet_train_param_floats'),
+                    'decoder': ('tmpnn_espnet_dec_ws_bytes', 'tmpnn_espnet_dec_bwd_ws_bytes', 'tmpnn_espnet_dec_refold',
+                                'tmpnn_espnet_dec_fwd', 'tmpnn_espnet_dec_bwd', 'tmpnn_espnet_dec_param_floats')}[scope]
         dev = torch.device(device)
         if dev.type != 'cuda':
             raise RuntimeError(f'EspTrainNet on {dev}: trackmpnn_amd runs on the MI355X HIP kernels only (no CPU path): pass a cuda '
@@ -619,14 +647,14 @@ class EspTrainNet(torch.nn.Module):
         if dev.index is None:
             dev = torch.device('cuda', torch.cuda.current_device())
         self.device = dev
-        self._names = trained_param_names(C)
-        table = train_table(C)
+        self._names = trained_param_names(C, scope)
+        table = train_table(C, scope)
         spec = espnet_spec(C)
         if len(table) != len(self._names) or any(int(n) != int(np.prod(spec[k])) for (_, n, _), k in zip(table, self._names)):
             raise RuntimeError('espnet: the library trains other tensors than trained_param_names lists')
         self._frozen = OrderedDict((k, v.detach().clone()) for k, v in sd.items() if k not in self._names)
         self._keys = list(sd.keys())
-        n = int(_lib.fn('tmpnn_espnet_train_param_floats')(C))
+        n = int(_lib.fn(self._ep[5])(C))
         host = np.zeros(n, np.float32)
         for (o, cnt, _), k in zip(table, self._names):
             host[o:o + cnt] = sd[k].detach().cpu().numpy().astype(np.float32).ravel()
@@ -634,21 +662,21 @@ class EspTrainNet(torch.nn.Module):
         self._params: 'OrderedDict[str, torch.nn.Parameter]' = OrderedDict()
         for (o, cnt, _), k in zip(table, self._names):
             self._params[k] = torch.nn.Parameter(self._flat[o:o + cnt].view(spec[k]))
-        stats = [sd[f'{p}.{k}'].detach().cpu().numpy().astype(np.float32) for p in ('act_l3.bn', 'project_l2.bn')
+        stats = [sd[f'{p}.{k}'].detach().cpu().numpy().astype(np.float32) for p in trained_norm_names(C, scope)
                  for k in ('running_mean', 'running_var')]
         self._stats = torch.from_numpy(np.concatenate(stats)).to(dev)
         self._arena = torch.from_numpy(pack_arena(sd, C)).to(dev)
         self._folded = self._version()
         self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
         self._bws: Dict[Tuple[int, int, int], torch.Tensor] = {}
-        self._taps: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._taps: Dict[Tuple[int, int, int], Tuple[torch.Tensor, ...]] = {}
         self._gen: Dict[Tuple[int, int, int], int] = {}
         self._out = None
         self.tap_grads: Optional[Dict[str, Optional[torch.Tensor]]] = None
 
     @classmethod
-    def from_state_dict(cls, sd, device='cuda:0') -> 'EspTrainNet':
-        return cls(sd, device)
+    def from_state_dict(cls, sd, device='cuda:0', scope: str = 'tail') -> 'EspTrainNet':
+        return cls(sd, device, scope)
 
     # ---- torch.nn.Module's surface --------------------------------------------------------------------------------------------
     def named_parameters(self, prefix: str = '', recurse: bool = True, remove_duplicate: bool = True):
@@ -677,7 +705,7 @@ class EspTrainNet(torch.nn.Module):
 
     def refold(self) -> None:
         """Rewrite the trained layers' arena segments from the parameters (one launch, no host copy)."""
-        _lib.call('tmpnn_espnet_refold', self._arena.data_ptr(), self.C, self._flat.data_ptr(), self._stats.data_ptr(),
+        _lib.call(self._ep[2], self._arena.data_ptr(), self.C, self._flat.data_ptr(), self._stats.data_ptr(),
                   _lib.raw_stream(self.device))
         self._folded = self._version()
 
@@ -694,7 +722,7 @@ class EspTrainNet(torch.nn.Module):
     def _forward(self, images, out):
         key = EspEmbedNet._check_images(self, images)
         T, H, W = key
-        ws = self._sized(self._ws, 'tmpnn_espnet_train_ws_bytes', key)
+        ws = self._sized(self._ws, self._ep[0], key)
         if self._version() != self._folded:
             self.refold()
         if out is None:
@@ -702,7 +730,7 @@ class EspTrainNet(torch.nn.Module):
         elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32
               or tuple(out.shape) != (T, self.C, H, W) or not out.is_contiguous()):
             raise ValueError(f'EspTrainNet: out [{T}, {self.C}, {H}, {W}] float32 contiguous on {self.device} expected')
-        _lib.call('tmpnn_espnet_train_fwd', self._arena.data_ptr(), self.C, images.data_ptr(), T, H, W, ws.data_ptr(), ws.numel(),
+        _lib.call(self._ep[3], self._arena.data_ptr(), self.C, images.data_ptr(), T, H, W, ws.data_ptr(), ws.numel(),
                   out.data_ptr(), _lib.raw_stream(self.device))
         gen = self._gen.get(key, 0) + 1
         self._gen[key] = gen
@@ -731,7 +759,7 @@ class EspTrainNet(torch.nn.Module):
         if d.dtype != torch.float32 or not d.is_contiguous():
             d = d.to(torch.float32).contiguous()
         ws = self._ws[key]
-        bws = self._sized(self._bws, 'tmpnn_espnet_train_bwd_ws_bytes', key)
+        bws = self._sized(self._bws, self._ep[1], key)
         params = list(self._params.values())
         g0 = params[0].grad
         inplace = g0 is not None
@@ -747,20 +775,20 @@ class EspTrainNet(torch.nn.Module):
         flat = None
         if not inplace:
             flat = torch.zeros_like(self._flat)
-        d1 = d2 = None
+        shapes = ((32, 2), (64, 4), (_PSP, 8), (2 * _PSP, 16))[:4 if self.scope == 'decoder' else 2]
+        tg = (None,) * len(shapes)
         if taps:
             tg = self._taps.get(key)
             if tg is None:
-                tg = self._taps[key] = (torch.empty((T, 32, H // 2, W // 2), dtype=torch.float32, device=self.device),
-                                        torch.empty((T, 64, H // 4, W // 4), dtype=torch.float32, device=self.device))
-            d1, d2 = tg
-        _lib.call('tmpnn_espnet_train_bwd', self._arena.data_ptr(), self.C, self._flat.data_ptr(), self._stats.data_ptr(), T, H, W,
+                tg = self._taps[key] = tuple(torch.empty((T, c, H // f, W // f), dtype=torch.float32, device=self.device)
+                                             for c, f in shapes)
+        _lib.call(self._ep[4], self._arena.data_ptr(), self.C, self._flat.data_ptr(), self._stats.data_ptr(), T, H, W,
                   ws.data_ptr(), ws.numel(), d.data_ptr(), bws.data_ptr(), bws.numel(),
-                  g0.data_ptr() if inplace else flat.data_ptr(), d1.data_ptr() if taps else None, d2.data_ptr() if taps else None,
+                  g0.data_ptr() if inplace else flat.data_ptr(), *(g.data_ptr() if taps else None for g in tg),
                   _lib.raw_stream(self.device))
         self._gen[key] = gen + 1                      # the backward turned d(act) into d(pre-activation) in place: once only
         if taps:
-            self.tap_grads = {'out_l1': d1, 'out_l2': d2, 'out_l3': None, 'out_l4': None}
+            self.tap_grads = dict(zip(('out_l1', 'out_l2', 'out_l3', 'out_l4'), tg + (None,) * (4 - len(tg))))
         if inplace:
             return [None] * len(params)
         out, o = [], 0
@@ -770,14 +798,15 @@ class EspTrainNet(torch.nn.Module):
         return out
 
 
-def train_table(C: int):
+def train_table(C: int, scope: str = 'tail'):
     """[(offset in the flat parameter buffer, element count, offset of the arena segment the tensor is folded into)] of the
-    tensors EspTrainNet trains, in the order of trained_param_names(C) (tmpnn_espnet_train_table; needs no GPU)."""
-    f = _lib.fn('tmpnn_espnet_train_table')
+    tensors EspTrainNet trains, in the order of trained_param_names(C, scope) (tmpnn_espnet_train_table / tmpnn_espnet_dec_table;
+    needs no GPU)."""
+    f = _lib.fn('tmpnn_espnet_train_table' if _check_scope(scope) == 'tail' else 'tmpnn_espnet_dec_table')
     n = int(f(int(C), None, 0))
     if n < 0:
         raise ValueError(f'espnet: {_lib.last_error()}')
     rows = np.zeros((n, 3), np.int64)
     if int(f(int(C), rows.ctypes.data, n)) != n:
-        raise RuntimeError(f'tmpnn_espnet_train_table: {_lib.last_error()}')
+        raise RuntimeError(f'espnet train_table: {_lib.last_error()}')
     return [tuple(int(v) for v in r) for r in rows]
