@@ -417,7 +417,8 @@ int tmpnn_reduce_slabs(const float* slabs, size_t stride, int nslab, float* dst,
  * batch; one segment reproduces the reference):
  *   xdet [nd][ld_x] gathered det-row features (group columns start at xdet), F inputs
  *   seg_ptr [S+1] det rows of segment s are [seg_ptr[s], seg_ptr[s+1]); seg_cnt [S] = ALL new
- *   rows of the segment (dets + zero rows)
+ *   rows of the segment (dets + zero rows).  A segment may hold no det rows (seg_ptr[s] == seg_ptr[s+1]: a window
+ *   that contributes zero rows only), provided seg_cnt[s] >= 2.
  *   training: batch stats (biased var, eps 1e-5) written to mean/rstd [S][H] and running stats
  *   updated sequentially over segments with momentum 0.1 (unbiased var); else running stats.
  *   y_save [nd][H] = Lin1 output (saved for backward); out rows written to

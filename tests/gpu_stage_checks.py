@@ -824,7 +824,8 @@ def run_all(report=print):
             for k, v in check_input_bn(H, F_, training, S=S, fused=True).items():
                 rec(f'input_tf (one launch) H={H} F={F_} S={S} train={training} {k}', v, 2e-4)
     # the wave-owned form (training, H = 64, F <= 16, segments of <= 32 det rows, no gradient with respect to x): many
-    # segments, tiles of one to a dozen segments, several groups per workgroup
+    # segments, tiles of one to eight segments, up to 141 groups of 64 segments -- one per workgroup on a device of 256 CUs
+    # (a workgroup's second group needs S > 64 CUs: tests/test_intf_shapes_gpu.py)
     for F_, S, maxn in ((8, 150, 33), (13, 700, 12), (8, 40, 2), (16, 9000, 8)):
         for k, v in check_input_bn(64, F_, True, S=S, fused=True, maxn=maxn, dx=False).items():
             rec(f'input_tf (wave-owned) H=64 F={F_} S={S} rows<{maxn} {k}', v, 2e-4)

@@ -227,8 +227,12 @@ __global__ __launch_bounds__(IT_NT) void k_it_bwd(ItBwdArgs a) {
         else { sb = s1; ra = sa * IT_CH; rb = min(a.nd, ra + IT_CH); }
         const int nr = rb - ra;
         // ---- d_out (gathered), yhat and a (recomputed).  Every load of a thread's <= IT_CH / NSUB rows is requested
-        //      before the first is used: the row id -> d_out chain is two dependent round trips, taken once, not per row
-        {
+        //      before the first is used: the row id -> d_out chain is two dependent round trips, taken once, not per row.
+        //      A chunk of empty segments (nr == 0, training only: a window that contributes zero rows but no det) has no
+        //      row to clamp to -- min(.., nr - 1) would be row ra - 1, before out_row and y_save when ra == 0 -- and loads
+        //      nothing; nr is uniform over the block.  Its segments still get dy0 = 0 and d_xzero = 0 below.  (Eval mode
+        //      walks ceil(nd / IT_CH) groups, so ra < nd and nr >= 1 there.)
+        if (nr > 0) {
             constexpr int RPT = IT_CH / NSUB;
             int orow[RPT], sg[RPT];
 #pragma unroll
